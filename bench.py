@@ -11,8 +11,13 @@ resident in HBM.  Independent per-video fits shard one per rank with no data-pat
 carries only the barrier, the max-over-ranks time and the per-rank rates.  Rank 0 prints ONE JSON line.
 
 The headline `value` is the engine's 16-bit mode (--precision fp16: IEEE-half activations and MFMA operands, fp32
-accumulate, fp32 master weights / merge / loss / Adam, dynamic loss scale).  The reference trains in fp32, so the same
-line carries the fp32 engine's own record under "fp32" (same step, same video, exact-fp32 MFMA), measured in this run.
+accumulate, fp32 master weights / merge / loss / Adam, dynamic loss scale).  A plain run measures only that: setup, burn-in,
+W warm-up and K timed steps, then the line.  --full adds everything else to the same line, measured in the same run: the
+per-kernel roofline table, the sustained 3-epoch rate, the 1080p geometry, the fp32 engine's own record under "fp32" (the
+reference trains in fp32; same step, same video, exact-fp32 MFMA) and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path handed back after its last timed step (rank 0) as float32 .npy files: see
+dump_outputs.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launch form (--mode, reported as config.launch_mode): "stream" (default) enqueues the steps through orn_engine_train_steps --
 plain launches; in the 16-bit modes the last block's weight gradient -> slab reduction -> merge backward -> Adam -> next merge
@@ -50,6 +55,7 @@ SYM = {'fwd_last': 'k_conv_fwd_nhwc_bf16<4, 2, 2, 2, 3, 96, false>', 'fwd': 'k_c
        'dgrad_split': 'k_conv_nhwc_bf16<8, 1, 1, 3, 2, 96, false> + k_dgrad_finish',
        'dgrad_narrow': 'k_conv_nhwc_bf16<8, 1, 1, 1, 2, 96, true>', 'wgrad': 'k_wgrad_nhwc_bf16_all',
        'wgrad_reduce': 'k_wgrad_bf16_reduce_all'}
+DUMP_SAMPLE = 1 << 21     # entries of each Adam moment --dump-outputs writes (parameters + both moments in full: 87 MiB at 720p)
 
 
 def layer_geo(cfg):
@@ -322,6 +328,26 @@ def timed_leg(eng, steps, warmup, graph, dist, device_sync):
     return dt, own, eng.stats(warmup + steps)
 
 
+def dump_outputs(eng, stats, path):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float32 .npy files in `path` (45 MiB at
+    720p): params.npy, the whole parameter arena (state-dict order, every tensor padded to 256 B); adam_m_sample.npy /
+    adam_v_sample.npy, the Adam moments at DUMP_SAMPLE positions drawn once with seed 0 and kept in index order (the same positions
+    in every run of a geometry); last_step_stats.npy, the engine's stats row of the last timed step (loss, L1, MSE, SSIM, PSNR, lr,
+    frame, step).  The --cpu-stub engine has no arena: only its stats row is written."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {'last_step_stats': stats[-1].float().numpy()}
+    if hasattr(eng, 'params'):
+        n = eng.params.numel()
+        pick = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(eng.params.device)
+        out['params'] = eng.params.float().cpu().numpy()
+        out['adam_m_sample'] = eng.adam_m[pick].float().cpu().numpy()
+        out['adam_v_sample'] = eng.adam_v[pick].float().cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def worker(args):
     import torch
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -349,6 +375,8 @@ def worker(args):
     if not stub:
         burn_in(eng, args.burn_in, graph)
     dt, own, stats = timed_leg(eng, args.steps, args.warmup, graph, dist, device_sync)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, stats, args.dump_outputs)
     psnr_last = float(stats[args.warmup:, 4].mean())
     ok = bool(torch.isfinite(stats[:, 0]).all())
     per_rank = [args.steps / own]
@@ -381,6 +409,7 @@ def worker(args):
         if not stub:
             sc = eng.scale_state()
             out['config']['loss_scale'] = {'scale': sc['scale'], 'steps_skipped': sc['skipped'], 'halvings': sc['backoffs']}
+        if not stub and args.full:
             kern = conv_kernels(eng, args.precision, cfg)
             dom = next(k for k in kern if k['gflop_per_step'] > 0)   # dominant by time (among the kernels that do MFMA work)
             step_us = dt / args.steps * 1e6
@@ -515,14 +544,18 @@ def main():
                     help='setup replays of the step before the warm-up, state restored afterwards (see burn_in); 0 = off')
     ap.add_argument('--precision', default=os.environ.get('ORN_PRECISION', 'fp16'), choices=['fp32', 'bf16', 'fp16'])
     ap.add_argument('--config', default='720p', choices=sorted(CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline table, sustained and 1080p legs, fp32 record and CPU baseline (off: the headline leg only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', dest='dump_outputs',
+                    help='write the outputs of the last timed step as .npy files to DIR (see dump_outputs)')
     ap.add_argument('--fp32-steps', type=int, default=66, help='timed steps of the fp32 record (at most --steps)')
-    ap.add_argument('--no-fp32', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-fp32', action='store_true', help='with --full: no fp32 record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
     ap.add_argument('--mode', default='stream', choices=['stream', 'graph', 'eager'],
                     help='stream (default): orn_engine_train_steps, plain launches, the last block\'s weight-gradient chain pipelined on the '
                          'engine\'s second stream; graph: hipGraph replay of the serial step; eager: one orn_engine_train_step call per step')
     ap.add_argument('--no-graph', action='store_true', help='same as --mode eager')
-    ap.add_argument('--quick', action='store_true', help='headline leg and its roofline only (probes): no sustained / 1080p legs')
+    ap.add_argument('--quick', action='store_true', help='with --full: no sustained / 1080p legs (probes)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'])
     ap.add_argument('--cpu-stub', action='store_true', help='no GPU: exercise launcher + reduction only (tests)')
     args = ap.parse_args()

@@ -1,8 +1,12 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# Before torch loads MKL: the golden vectors hold CPU results of MKL's COMPATIBLE branch (tools/make_golden.py), the one branch
+# MKL runs alike on every x86 host -- its AVX2 / AVX-512 branches are Intel-only, so AMD and Intel hosts would differ in the last bit
+os.environ['MKL_CBWR'] = 'COMPATIBLE'
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

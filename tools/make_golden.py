@@ -15,8 +15,12 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
+# MKL's COMPATIBLE branch, single-threaded: the one setting in which MKL computes the same bits on every x86 host (its
+# AVX2 / AVX-512 branches are Intel-only); tests/conftest.py and tests/test_oracle_golden.py run the oracle the same way
+os.environ['MKL_CBWR'] = 'COMPATIBLE'
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 REF = '/root/reference'
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden')
@@ -400,7 +404,7 @@ def golden_prune(ref_model, ref_utils):
 
 def main():
     os.makedirs(OUT, exist_ok=True)
-    torch.set_num_threads(8)
+    torch.set_num_threads(1)
     ref_model, ref_utils = _import_reference()
     if len(sys.argv) > 1 and sys.argv[1] == 'prune':      # regenerate only the G9 fixture
         golden_prune(ref_model, ref_utils)
