@@ -231,6 +231,12 @@ struct OrnScaleState {
     int32_t good;          // (entry 0) clean steps since the last change of scale, credited once they have run
     int32_t backoffs;      // (entry 0) times the scale was halved
     int32_t launched;      // (entry 0) steps of the group launched at the last advance
+    // pipelined step (orn_engine_train_steps): the side branch's copy of a step's state keeps the caller's-stream Adam's skip
+    // decision apart from its own detectors, which run behind that decision (flag); a detection of the side branch alone skips
+    // the side stream's update only (a late-only skip) and is counted in entry 0
+    int32_t mirrored;      // (side copy) the caller's-stream Adam launch of this step skipped it; the side branch's launch follows
+    int32_t late_skipped;  // (entry 0) late-only skips so far (Adam's bias corrections count them: the lower blocks did update)
+    int32_t late_seen;     // (entry 0) late_skipped as the last advance saw it: a difference backs the scale off
 };
 #define ORN_SCALE_GROWTH_INTERVAL 2000
 __device__ __forceinline__ void orn_flag_nonfinite(OrnScaleState *sc, float v)
@@ -285,7 +291,10 @@ __device__ __forceinline__ void orn_loss_finalize_block(const OrnLossFinalJob &j
         j.stats[0] = loss * j.loss_scale; j.stats[1] = l1; j.stats[2] = mse; j.stats[3] = ss; j.stats[4] = psnr;
         j.stats[5] = 0.f; j.stats[6] = 0.f; j.stats[7] = 0.f;
         if (j.cur_copy && j.cur) *j.cur_copy = *j.cur;
-        if (j.sc_copy && j.sc) { j.sc_copy->gs = j.sc->gs; j.sc_copy->inv_gs = j.sc->inv_gs; j.sc_copy->gs_max = j.sc->gs_max; j.sc_copy->flag = 0; }
+        if (j.sc_copy && j.sc) {
+            j.sc_copy->gs = j.sc->gs; j.sc_copy->inv_gs = j.sc->inv_gs; j.sc_copy->gs_max = j.sc->gs_max;
+            j.sc_copy->flag = 0; j.sc_copy->mirrored = 0;
+        }
         if (j.ring) {                                  // engine: publish into the per-step ring (slot from the cursor)
             float *r = j.ring + (size_t)j.cur->slot * 8;
             r[0] = loss * j.loss_scale; r[1] = l1; r[2] = mse; r[3] = ss; r[4] = psnr;

@@ -78,8 +78,9 @@ struct orn_engine {
     //                           of 216), is complete: its slabs may be reduced, its input buffer overwritten
     //   ev_join   side -> main: the last block's merged kernel (and the head's parameters) of the next step are ready
     // cur_side / sc_side: this step's schedule entry and loss scale, copied by the loss's finalize stage (the main stream advances
-    // to the next step while the side branch still reads them); sc_side->flag also collects what the side branch's own two
-    // detectors raise behind the main commit (include/orn.h, the loss-scale comment).
+    // to the next step while the side branch still reads them); sc_side->mirrored holds the caller's-stream Adam's skip decision,
+    // sc_side->flag what the side branch's own detectors raise, two of them behind that decision (include/orn.h, the loss-scale
+    // comment): the side branch's Adam launch skips on either and counts a skip of the flag alone in sc[0].late_skipped.
     hipStream_t side;
     hipEvent_t ev_fork, ev_adam, ev_wgrad, ev_join, ev_below;
     OrnStepCur *cur_side;
@@ -414,7 +415,7 @@ extern "C" int orn_engine_set_target_stats(orn_engine *e, const float *stats)
     return 0;
 }
 
-// Loss-scale state: out8 = {gs, 1/gs, gs_max, flag, skipped, good, backoffs, 0} (host floats; synchronises the device).
+// Loss-scale state: out8 = {gs, 1/gs, gs_max, flag, skipped, good, backoffs, late-only skips} (host floats; synchronises the device).
 extern "C" int orn_engine_scale_state(orn_engine *e, float *out8)
 {
     ORN_REQUIRE(e && out8, "engine_scale_state: null pointer");
@@ -425,8 +426,9 @@ extern "C" int orn_engine_scale_state(orn_engine *e, float *out8)
     const OrnScaleState &s = sa[0];
     int any = 0;                                      // flag: a step since the last advance met a non-finite value
     for (int r = 0; r < ORN_SCALE_SLOTS; ++r) any |= sa[r].flag;
+    any |= s.late_skipped != s.late_seen ? 1 : 0;    // a late-only skip the next advance has still to fold into the scale
     out8[0] = s.gs; out8[1] = s.inv_gs; out8[2] = s.gs_max; out8[3] = (float)any; out8[4] = (float)s.skipped;
-    out8[5] = (float)s.good; out8[6] = (float)s.backoffs; out8[7] = 0.f;
+    out8[5] = (float)s.good; out8[6] = (float)s.backoffs; out8[7] = (float)s.late_skipped;
     return 0;
 }
 
@@ -469,6 +471,10 @@ __global__ void k_advance(const orn_step_sched *__restrict__ sched, int32_t *cur
         int nflag = 0;
         for (int r = 0; r < ORN_SCALE_SLOTS; ++r)
             if (sc[r].flag) { nflag += 1; sc[r].flag = 0; }
+        // late-only skips of the pipelined step (the side branch's Adam launch counts them, possibly after this advance has run:
+        // then the next one backs off).  A counter and not a flag: a flag would be read by the next step's Adam, which is clean
+        const int32_t late = __atomic_load_n(&sc->late_skipped, __ATOMIC_RELAXED);
+        if (late != sc->late_seen) { nflag += 1; sc->late_seen = late; }
         float gs = sc->gs;
         if (nflag) {
             gs = fmaxf(gs * 0.5f, 1.0f);
@@ -678,7 +684,7 @@ static int side_branch_backward(orn_engine *e, hipStream_t st)
     const orn_layer_desc &l = d.layer[nl - 1];
     float *G = e->grads;
     hipStream_t sd = e->side;
-    OrnScaleState *sc = e->sc_side;                     // this step's scale, copied by the loss's finalize stage; late detections
+    OrnScaleState *sc = e->sc_side;                     // this step's scale, copied by the loss's finalize stage; the branch's detections
     ORN_HIP(hipEventRecord(e->ev_fork, st));
     ORN_HIP(hipStreamWaitEvent(sd, e->ev_fork, 0));
     if (side_takes_below(e)) {      // (its dy is the output of the dgrad launch this branch forks behind; its slabs are reduced on the caller's stream)
@@ -702,7 +708,8 @@ static int side_branch_backward(orn_engine *e, hipStream_t st)
     return 0;
 }
 
-// Second half (enqueued behind the caller's Adam launch, whose skip decision it follows): Adam over the last block's and the head's
+// Second half (enqueued behind the caller's Adam launch, whose skip decision it follows; a detection of the branch's own skips it too, as
+// a late-only skip, counted in sc[0].late_skipped and folded into the scale by the next advance or the one after): Adam over the last block's and the head's
 // parameters, then the last block's merge forward (or, without ERB, its 16-bit operand copies) for the NEXT step.
 // more: another step follows in this call (the last step of a call skips the merge forward: the next call's first step merges every
 // block itself, the parameters may have been touched in between)
@@ -714,7 +721,7 @@ static int side_branch_update(orn_engine *e, bool more)
     const size_t lo = e->side_lo;
     ORN_HIP(hipStreamWaitEvent(sd, e->ev_adam, 0));
     ORN_TRY(orn_launch_adam(e->params + lo, e->grads + lo, e->m + lo, e->v + lo, (size_t)d.n_params - lo, 0.0, 1, e->cur_side, d.beta1, d.beta2,
-                            d.eps, 1.0f, sd, e->gmask ? e->gmask + lo : nullptr, e->sc_side, nullptr, nullptr, false));
+                            d.eps, 1.0f, sd, e->gmask ? e->gmask + lo : nullptr, e->sc_side, nullptr, nullptr, false, e->sc));
     if (!more) {
     } else if (d.erb) {
         const orn_engine::MergeSet &ms = e->mset[2];
@@ -863,6 +870,7 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
     }
     if (pipe) {
         // this stream's Adam launch covers everything below the last block; its skip decision is mirrored for the side branch's launch
+        // (into sc_side->mirrored: a word of its own, apart from the flag the side branch's detectors raise meanwhile)
         ORN_TRY(orn_launch_adam(P, G, e->m, e->v, e->side_lo, 0.0, 1, cur, d.beta1, d.beta2, d.eps, 1.0f, st, e->gmask, sc, e->sc, e->sc_side));
         ORN_HIP(hipEventRecord(e->ev_adam, st));
         return side_branch_update(e, more);

@@ -20,8 +20,9 @@ int orn_launch_adam(float *p, const float *g, float *m, float *v, size_t n, doub
                     double beta1, double beta2, double eps, float inv_gscale, hipStream_t st, const float *gmask = nullptr,
                     OrnScaleState *sc = nullptr,    // sc: skip the update while its flag is up
                     OrnScaleState *sc_master = nullptr,    // (engine: the entry that counts skipped steps; default sc itself)
-                    OrnScaleState *mirror = nullptr,       // (engine, deferred last block) the skip decision is also stored into mirror->flag
-                    bool count_skip = true);               // false: a skipped launch does not count (the step's other Adam launch does)
+                    OrnScaleState *mirror = nullptr,       // (engine, deferred last block) the skip decision is also stored into mirror->mirrored
+                    bool count_skip = true,                // false: a skipped launch does not count (the step's other Adam launch does)
+                    OrnScaleState *late = nullptr);        // (side branch) a skip of sc->flag alone, not mirrored, counts in late->late_skipped
 
 // orn_stage0.hip: the fp32 block below the first 16-bit one (tiny stem image), forward / backward as one launch each
 bool orn_stage0_supported(int C, int O, int H, int W, int s);

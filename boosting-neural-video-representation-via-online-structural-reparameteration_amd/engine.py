@@ -185,7 +185,9 @@ class TrainEngine:
         """Enqueue `n_steps` optimiser steps consuming the uploaded schedule (no host sync).
         graph=None (default): orn_engine_train_steps -- plain stream launches, pipelined over the engine's second stream where the
         engine can (16-bit modes; include/orn.h); graph=True: hipGraph replay of the serial step; graph=False: one
-        orn_engine_train_step call per step.  All three give bit-identical results."""
+        orn_engine_train_step call per step.  All three give bit-identical results, except for a step that only the pipelined form's
+        late overflow checks flag (a late-only skip: the serial forms skip the whole step, the pipelined form all but the lower
+        blocks' update; counted in scale_state()['late_skipped'], include/orn.h)."""
         if self.frames is None or self.sched is None:
             raise OrnError('set_video() and set_schedule() first')
         cur = torch.cuda.current_stream()
@@ -244,16 +246,18 @@ class TrainEngine:
     def applied_steps(self) -> int:
         """Optimiser steps that changed the parameters so far: enqueued steps minus the ones the non-finite guard skipped, in this
         engine (device counter) and in engines it replaced (`skipped_carry`, set by main_train's precision fall-back).  This is
-        torch.optim.Adam's 'step' of a checkpoint (include/orn.h).  Synchronises."""
+        torch.optim.Adam's 'step' of a checkpoint (include/orn.h).  A late-only skip of the pipelined form does not come off: the lower
+        blocks applied that step.  Synchronises."""
         return int(self.global_step - self.skipped_carry - self.scale_state()['skipped'])
 
     def scale_state(self) -> dict:
         """Dynamic loss scale / non-finite guard of the engine (device state; synchronises): scale, ceiling, flag, steps
-        skipped so far, clean steps since the last change, halvings."""
+        skipped so far, clean steps since the last change, halvings, late-only skips of the pipelined form so far (the last block's
+        and the head's update skipped, the lower blocks' applied; include/orn.h)."""
         out = (ctypes.c_float * 8)()
         check(lib().orn_engine_scale_state(self._h, out), 'orn_engine_scale_state')
         return {'scale': float(out[0]), 'ceiling': float(out[2]), 'flag': int(out[3]), 'skipped': int(out[4]),
-                'good': int(out[5]), 'backoffs': int(out[6])}
+                'good': int(out[5]), 'backoffs': int(out[6]), 'late_skipped': int(out[7])}
 
     def set_grad_scale(self, scale: float, ceiling: float = 0.0):
         """Override the live gradient scale of the 16-bit modes (and its ceiling if > 0)."""

@@ -184,6 +184,12 @@ class Snapshot:
             now.restore(eng)
 
 
+def steps_skipped(sc: dict) -> int:
+    """Steps the non-finite guard skipped so far, from TrainEngine.scale_state(): whole steps, plus the pipelined form's late-only
+    skips (the last block's and the head's update skipped; include/orn.h), which the dead-fit detector below must see too."""
+    return int(sc['skipped']) + int(sc['late_skipped'])
+
+
 def skipped_steps_warning(skipped_before: int, skipped_now: int, steps: int, precision: str, scale: float):
     """The non-finite guard leaves parameters and Adam state untouched by a step whose loss or gradients are not finite and
     backs the loss scale off; a few such steps are its normal work.  An epoch in which MOST steps were skipped means the fit
@@ -317,7 +323,7 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         eng.run(len(entries))
         st = eng.stats(len(entries))                                 # syncs once per epoch
         sc = eng.scale_state()                                       # (the stats read above has already synchronised)
-        warn = skipped_steps_warning(skipped_before, sc['skipped'], len(entries), precision, sc['scale'])
+        warn = skipped_steps_warning(skipped_before, steps_skipped(sc), len(entries), precision, sc['scale'])
         if warn and precision in FALLBACK:
             # The fit has left this precision's number range: skipped steps change nothing, so it
             # would burn the remaining epochs.  Go back to the start of this epoch and continue in the next wider
@@ -337,7 +343,7 @@ def fit_video(args, name, vid_index, rank, _inject=None):
             precision, skipped_before = wider, 0
             best_snap = None if best_snap is None else best_snap       # (arena-sized tensors: still valid for the new engine)
             continue
-        skipped_before = sc['skipped']
+        skipped_before = steps_skipped(sc)
         if warn:
             say(warn)
         train_psnr = st[:, 4].mean()
@@ -378,8 +384,9 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         from . import checkpoint
         say(f'Deploy Rep-Model Params: {checkpoint.deploy_param_count(model) / 1e6:.3f}M')
     sc = eng.scale_state()
-    if sc['skipped']:
-        say(f'loss scale: {sc["skipped"]} steps skipped (non-finite gradients), scale now {sc["scale"]:g}', console=False)
+    if steps_skipped(sc):
+        say(f'loss scale: {steps_skipped(sc)} steps skipped (non-finite gradients; {sc["late_skipped"]} of them late-only), '
+            f'scale now {sc["scale"]:g}', console=False)
     if precision != args.precision:
         say(f'precision: started in {args.precision}, finished in {precision}')
     say(f'Training complete in: {time.time() - start:.1f}s', console=False)

@@ -242,8 +242,9 @@ ORN_API int orn_engine_profile_step(orn_engine *e, const float *frames, const fl
  * 16-bit mode with at least two blocks on the fast path run them PIPELINED: the last block's weight gradient, its slab reduction,
  * merge backward, Adam update (with the head's) and next merge forward run on a second stream the engine owns, forked off at the end
  * of the backward and joined in front of that block's forward conv of the next step, so that this chain overlaps the latency-bound
- * launches of the step boundary.  Same arithmetic, same order of every sum: bit-identical to orn_engine_train_step.  All work is
- * joined back into `stream` before the call returns (stream order on `stream` covers it). */
+ * launches of the step boundary.  Same arithmetic, same order of every sum: bit-identical to orn_engine_train_step, except for a
+ * step that only the side branch's late detectors flag (a late-only skip, below: counted and reported by orn_engine_scale_state).
+ * All work is joined back into `stream` before the call returns (stream order on `stream` covers it). */
 ORN_API int orn_engine_train_steps(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
                            int32_t *cursor, float *stats_out, int32_t n_slots, int32_t n_steps, void *stream);
 /* Capture one train step into a hipGraph on `stream` and replay it n times (same arguments as above). */
@@ -254,7 +255,8 @@ ORN_API int orn_engine_train_steps_graph(orn_engine *e, const float *frames, con
  * model).  The 16-bit gradient tensors of precision 2 travel multiplied by a scale held in device memory (2^20 at creation;
  * 1 for the other precisions).  A step whose gradients (or loss) are not finite leaves parameters and Adam moments untouched
  * and halves the scale; 2000 clean steps double it again up to its initial value.  All of it happens on the device, inside
- * the captured step.  out8 (host): {scale, 1/scale, ceiling, flag, steps skipped, clean steps, halvings, 0}; synchronises.
+ * the captured step.  out8 (host): {scale, 1/scale, ceiling, flag, steps skipped, clean steps, halvings, late-only skips};
+ * synchronises.  flag includes a late-only skip the scale has not yet backed off for.
  * Where this differs from GradScaler:
  *  - granularity: the flag is PER STEP (one scale-state entry per step of the unrolled graph: an overflowing step skips itself
  *    only, the clean steps before and behind it in the same graph launch update the parameters), but the scale changes only
@@ -272,8 +274,12 @@ ORN_API int orn_engine_train_steps_graph(orn_engine *e, const float *frames, con
  *    sums is covered by the lower blocks' detectors: a non-finite dy of the last block reaches them through the dgrad chain), and
  *    the side stream's Adam launch (last block + head) follows that decision.  Two detectors of the side branch run BEHIND the
  *    decision: the last block's slab reduction (unreachable alone, by the argument above) and the fp16 copy of its merged-kernel
- *    gradient (|dWf| > 4).  If one of them fires alone, only the side stream's update of that step is skipped (the parameters stay
- *    finite; the step is not counted as skipped).  The serial forms skip the whole step in that case. */
+ *    gradient (|dWf| > 4).  If one of them fires alone (a LATE-ONLY skip), only the side stream's update of that step is skipped:
+ *    the lower blocks take it, the last block and the head do not, the parameters stay finite.  It is counted apart from the
+ *    skipped steps (out8[7]), and the scale backs off for it at the next advance or, when the side branch's Adam launch runs
+ *    behind that one, at the advance after it.  Adam's step numbers (device schedule, checkpoint) do not exclude it: the lower
+ *    blocks did apply the step.  This is the one case in which the pipelined form differs from the serial forms, which skip and
+ *    count the whole step. */
 ORN_API int orn_engine_scale_state(orn_engine *e, float *out8);
 /* Overrides the live scale (>= 1) and, if gs_max > 0, its ceiling: tests inject an overflowing step this way. */
 ORN_API int orn_engine_set_grad_scale(orn_engine *e, float gs, float gs_max);

@@ -27,3 +27,50 @@ def erb_inputs(C, O, seed):
         'rbr_1x1_3x3_1x1_branch_3x3.weight': _rand(g, O, 2 * C, 3, 3, scale=1 / math.sqrt(18 * C)),
         'rbr_1x1_3x3_1x1_branch_1x1_2.weight': _rand(g, O, O, 1, 1, scale=1 / math.sqrt(O)),
     }
+
+
+def pipelined_vs_oracle(eng, sd, frames, embeds, entries, calls, fc, strides, branch):
+    """Run the schedule `entries` [(frame, step, lr)] on `eng` as pipelined calls (TrainEngine.run's default form) of `calls` steps
+    each, and the same steps on the CPU oracle (cpu_ref.train_step in a loop, updating a copy of `sd` -- the engine's starting state
+    dict -- and its Adam moments in place).  Checks the stats columns that must be exact (lr, frame, step) and returns the measured
+    differences: worst relative loss error and PSNR error over the steps; worst per-tensor relative L2 of the last step's gradients
+    and of both Adam moments at the end; how far the engine's parameters moved (max |p - p0| in units of the largest lr), the share
+    of elements that end more than lr/2 from the oracle's, and the share of the oracle's elements that moved by more than lr/2."""
+    import numpy as np
+    from oracle import cpu_ref
+    eng.set_schedule(entries)
+    for n in calls:
+        eng.run(n)
+    torch.cuda.synchronize()
+    st = eng.stats(len(entries)).numpy()
+    p0 = {k: v.clone() for k, v in sd.items()}
+    sd = {k: v.clone() for k, v in sd.items()}
+    am = {k: torch.zeros_like(v) for k, v in sd.items()}
+    av = {k: torch.zeros_like(v) for k, v in sd.items()}
+    out = {'loss_rel': 0.0, 'psnr': 0.0}
+    for i, (f, step, lr) in enumerate(entries):
+        loss, psnr, grads = cpu_ref.train_step(sd, am, av, step, lr, embeds[f:f + 1], frames[f:f + 1], fc, strides, branch,
+                                               'Fusion6', 0.5)
+        assert st[i, 5] == np.float32(lr) and st[i, 6] == f and st[i, 7] == step, (i, st[i], (f, step, lr))
+        out['loss_rel'] = max(out['loss_rel'], abs(float(st[i, 0]) - loss.item()) / abs(loss.item()))
+        out['psnr'] = max(out['psnr'], abs(float(st[i, 4]) - psnr.item()))
+    P, G, M, V = (t.cpu() for t in (eng.params, eng.grads, eng.adam_m, eng.adam_v))
+
+    def worst(arena, ref):
+        rel = [(float((arena[off:off + n] - ref[k].flatten()).norm() / (ref[k].norm() + 1e-30)), k)
+               for k, (off, n) in eng.layout.items()]
+        return max(rel)
+    assert set(grads) == set(eng.layout)
+    (out['grad_rel'], out['grad_key']), (out['m_rel'], out['m_key']) = worst(G, grads), worst(M, am)
+    out['v_rel'], out['v_key'] = worst(V, av)
+    lr = max(e[2] for e in entries)
+    move = off = moved = total = 0
+    for k, (o, n) in eng.layout.items():
+        p = P[o:o + n]
+        move = max(move, float((p - p0[k].flatten()).abs().max()) / lr)
+        off += int(((p - sd[k].flatten()).abs() > lr / 2).sum())
+        moved += int(((sd[k] - p0[k]).abs() > lr / 2).sum())
+        total += n
+    out.update(move_lr=move, off_share=off / total, oracle_moved_share=moved / total)
+    out['finite'] = bool(torch.isfinite(P).all())
+    return out

@@ -435,15 +435,17 @@ def _oracle_full_step(geo='720p', bt='ERB'):
     return _ORACLE_STEP[key]
 
 
-def _check_full_step(orn, geo, bt, prec, n_grads):
+def _check_full_step(orn, geo, bt, prec, n_grads, graph=True):
+    """graph (16-bit modes): True, the hipGraph replay of the serial step; None, the pipelined form (TrainEngine.run's default), whose
+    side branch computes the last block's and the head's gradients and is joined at the end of the call.  fp32: one eager step."""
     o = _oracle_full_step(geo, bt)
     gen = _make_full(orn, geo, bt)
     gen.load_state_dict(o['sd'])
     eng = orn.engine.TrainEngine(gen, loss_type='Fusion6', beta=0.5, precision=prec)
     eng.set_video(o['frames'], o['embeds'])
     eng.set_schedule([(1, 1, 0.0)])
-    eng.run(1, graph=(prec != 'fp32'))
-    torch.cuda.synchronize()
+    eng.run(1, graph=graph if prec != 'fp32' else False)
+    torch.cuda.synchronize()                      # (the pipelined call's side branch is joined into the stream run() returns on)
     st = eng.stats(1)[0].numpy()
     grads = {k: eng.grads[off:off + n].clone().cpu() for k, (off, n) in eng.layout.items()}
     ref = o['ref']
@@ -453,7 +455,8 @@ def _check_full_step(orn, geo, bt, prec, n_grads):
     assert len(ref) == n_grads
     rel = sorted(((float((grads[k] - ref[k].flatten()).norm() / (ref[k].norm() + 1e-30)), k) for k in ref), reverse=True)
     assert rel[0][0] < tol_g, rel[:8]
-    assert eng.scale_state()['skipped'] == 0
+    s = eng.scale_state()
+    assert s['skipped'] == 0 and s['late_skipped'] == 0, s
 
 
 @pytest.mark.parametrize('prec', ['fp32', 'fp16', 'bf16'])
@@ -478,6 +481,61 @@ def test_1080p_fp32_gradients_vs_oracle(orn):
     """BASELINE config 3's geometry (ERB, 9_16_48, strides 5 3 2 2 2, 1920x1080) at FULL size: the fp32 engine's loss, PSNR and 51
     gradient tensors against the CPU oracle (the 16-bit engines are compared with the fp32 engine at this size in test_gpu_bf16)."""
     _check_full_step(orn, '1080p', 'ERB', 'fp32', 51)
+
+
+@pytest.mark.parametrize('cfg', [('720p', 'ERB', 'fp16', 51), ('720p', 'ERB', 'bf16', 51), ('720p', 'NeRV_vanilla', 'fp16', 16)],
+                         ids=['720p-ERB-fp16', '720p-ERB-bf16', '720p-vanilla-fp16'])
+def test_720p_pipelined_gradients_vs_oracle(orn, cfg):
+    """The PIPELINED form of the step (orn_engine_train_steps: the default of TrainEngine.run, bench.py and main_train) at FULL
+    size against the CPU oracle directly, with the tolerances of the hipGraph tests above: the last block's weight gradient, slab
+    reduction and merge backward and the head's dW / db finish run on the engine's second stream and are read after the join."""
+    geo, bt, prec, n = cfg
+    _check_full_step(orn, geo, bt, prec, n, graph=None)
+
+
+@pytest.mark.parametrize('graph', [True, None], ids=['graph', 'pipelined'])
+@pytest.mark.parametrize('prec', ['fp16', 'bf16'])
+def test_1080p_16bit_gradients_vs_oracle(orn, prec, graph):
+    """BASELINE config 3's geometry (ERB, 9_16_48, strides 5 3 2 2 2, a stride-3 block, 1920x1080) in the 16-bit modes, as the
+    hipGraph replay and as the pipelined step: loss, PSNR and all 51 gradient tensors against the CPU oracle (the same step
+    test_1080p_fp32_gradients_vs_oracle checks), at the 720p tests' 16-bit tolerances."""
+    _check_full_step(orn, '1080p', 'ERB', prec, 51, graph=graph)
+
+
+def full_720p_steps_vs_oracle(orn):
+    """BASELINE config 2 (720p ERB) in fp16: 3 pipelined steps in one call vs 3 steps of the CPU oracle (frames 2 0 1 of a
+    3-frame synthetic video, lr 1e-3 falling by 10 % a step)."""
+    from oracle import cpu_ref
+    from helpers import pipelined_vs_oracle
+    fc, strides, (h, w) = _GEO['720p']
+    gen = _make_full(orn, '720p', 'ERB')
+    sd = {k: v.detach().clone() for k, v in gen.state_dict().items()}
+    frames = cpu_ref.synthetic_video(3, h, w, seed=13)
+    embeds = cpu_ref.positional_encoding(torch.tensor([0.0, 1 / 3, 2 / 3]), 1.25, 40)
+    eng = orn.engine.TrainEngine(gen, loss_type='Fusion6', beta=0.5, precision='fp16')
+    eng.set_video(frames, embeds)
+    entries = [(2, 1, 1e-3), (0, 2, 9e-4), (1, 3, 8e-4)]
+    out = pipelined_vs_oracle(eng, sd, frames, embeds, entries, (3,), fc, strides, 'ERB')
+    s = eng.scale_state()
+    out['skips'] = s['skipped'] + s['late_skipped']
+    return out
+
+
+def test_720p_pipelined_steps_vs_oracle(orn):
+    """BASELINE config 2 at FULL size, 3 pipelined fp16 steps at lr > 0 against the CPU oracle (tests/helpers.pipelined_vs_oracle):
+    steps 2 and 3 run on the last block's merged kernel, half copies and Adam update from the previous step's side branch.
+    Measured on the MI355X: loss 1.5e-5 relative, PSNR 7.6e-6 dB, gradient 1.1e-3, m 9.5e-4, v 8.9e-4 relative L2 (worst tensor), no
+    parameter more than lr/2 from the oracle's; 69 % of the oracle's parameters moved by more than lr/2.  Tolerances: <= 3x that,
+    within the single-step fp16 ceilings (3e-4, 0.01 dB, 1e-2, 1e-2, 2e-2).  With the merge backward's parameter-side half copies
+    refreshed on the first step only (a planted fault), the gradient error here is 0.96."""
+    m = full_720p_steps_vs_oracle(orn)
+    assert m['skips'] == 0 and m['finite'], m
+    assert m['oracle_moved_share'] > 0.5, m
+    assert m['move_lr'] <= 2 * 3, m
+    tol = dict(loss_rel=4e-5, psnr=2e-5, grad_rel=3e-3, m_rel=2.5e-3, v_rel=2.5e-3)
+    for key, t in tol.items():
+        assert m[key] < t, (key, m)
+    assert m['off_share'] == 0.0, m
 
 
 def test_engine_merge_is_bit_exact(orn):

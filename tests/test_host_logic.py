@@ -339,3 +339,22 @@ def test_skipped_steps_warning():
     assert w and '132 of 132' in w and 'fp32' in w and 'bf16' in w
     w = mt.skipped_steps_warning(0, 100, 132, 'fp32', 1.0)
     assert w and 'bf16' not in w
+
+
+def test_late_only_skips_count_for_the_dead_fit_warning():
+    """The pipelined step's late-only skips (last block and head not updated, lower blocks updated; include/orn.h) count as skipped
+    steps for main_train's warning and precision fall-back: an epoch made of them alone must raise it, as the serial forms' whole
+    skips do."""
+    from orn_amd import main_train as mt
+
+    def sc(skipped, late):
+        return {'scale': 1.0, 'skipped': skipped, 'late_skipped': late}
+    assert mt.steps_skipped(sc(0, 0)) == 0
+    assert mt.steps_skipped(sc(3, 4)) == 7
+    before = mt.steps_skipped(sc(2, 1))
+    assert mt.skipped_steps_warning(before, mt.steps_skipped(sc(2, 3)), 132, 'fp16', 1.0) is None       # two late-only skips
+    w = mt.skipped_steps_warning(before, mt.steps_skipped(sc(2, 133)), 132, 'fp16', 1.0)                # every step late-only
+    assert w and '132 of 132' in w and 'bf16' in w
+    w = mt.skipped_steps_warning(before, mt.steps_skipped(sc(40, 40)), 132, 'fp16', 1.0)                # 38 + 39 of 132: a majority
+    assert w and '77 of 132' in w
+    assert mt.skipped_steps_warning(before, mt.steps_skipped(sc(40, 28)), 132, 'fp16', 1.0) is None    # 38 + 27 = 65: a minority
