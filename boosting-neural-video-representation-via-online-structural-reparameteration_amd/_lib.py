@@ -83,8 +83,12 @@ _SIGS = {
     'orn_engine_set_grad_scale': (c_int, [P, c_float, c_float]),
 }
 EXPORTS = tuple(_SIGS.keys())
-# probe-only entry points (include/orn_debug.h): resolved if present, never required
-_DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, [c_void_p])}
+# test and probe entry points (include/orn_debug.h): resolved if present, never required
+_DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, [c_void_p]),
+               'orn_debug_conv_fwd_bf16': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, P]),
+               'orn_debug_conv_fwd_f16': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, P]),
+               'orn_debug_conv_dgrad_bf16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
+               'orn_debug_conv_dgrad_f16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P])}
 
 _lib = None
 

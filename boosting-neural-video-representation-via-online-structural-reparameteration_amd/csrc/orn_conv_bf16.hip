@@ -791,8 +791,10 @@ size_t orn_wgrad_bf16_ws_floats(int H, int W, int O)
 // channels per pixel (zeros above C).
 static int wgrad_fill(WgradBP &p, const h16 *xpad, const h16 *dypad, int H, int W, int C, int O, int s, float *slabs, int smax)
 {
-    // O % 32: a ragged last 128-channel tile reads up to 96 channels past the last pixel's: dypad must be readable for 96
-    // elements behind its end (the engine and the per-op hooks pad it)
+    // O % 32: a ragged last 128-channel tile reads up to 96 channels past a pixel's O; behind the last interior pixel (H, W) they
+    // fall on dypad's border ring, so this kernel stays inside [H+2][W+2][O].  The 128 elements of slack orn.h asks for behind
+    // dypad (the engine and the per-op hooks allocate them) serve the dgrad's reads; tests/test_gpu_conv16_forms.py fills them
+    // with NaN.
     ORN_REQUIRE(C >= 1 && C <= 96 && O % 32 == 0 && O % (s * s) == 0, "wgrad_bf16: unsupported C=%d O=%d", C, O);
     p.dbg = g_conv_dbg;
     p.xpad = xpad; p.dypad = dypad; p.slabs = slabs; p.H = H; p.W = W; p.O = O;
@@ -1478,6 +1480,22 @@ extern "C" int HOOK(orn_dgrad_nhwc_bf16, orn_dgrad_nhwc_f16)(const void *dypad, 
 {
     return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp,
                                       nullptr, (hipStream_t)stream, C);
+}
+
+// Test entry points (include/orn_debug.h): the two conv launchers with the engine's full argument lists, so that a test reaches
+// every kernel form they select (the narrow c_real forms, the split dgrad + finish, the fp32 hand-off) with the engine's buffers.
+extern "C" int HOOK(orn_debug_conv_fwd_bf16, orn_debug_conv_fwd_f16)(const void *xpad, const void *wb, const float *bias_p, int H, int W,
+                                                                   int Cin, int O, int s, void *z, void *apad, int c_real, void *stream)
+{
+    return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad,
+                                    (hipStream_t)stream, c_real, nullptr);
+}
+extern "C" int HOOK(orn_debug_conv_dgrad_bf16, orn_debug_conv_dgrad_f16)(const void *dypad, const void *wd, int H, int W, int O, int C,
+                                                                       const void *zprev, void *dyprev, int sp, float *dx_f32, int c_real,
+                                                                       void *stream)
+{
+    return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32,
+                                      (hipStream_t)stream, c_real);
 }
 
 #ifdef ORN_CONV_STAMP

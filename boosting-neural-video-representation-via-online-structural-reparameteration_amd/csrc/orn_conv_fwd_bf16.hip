@@ -529,8 +529,10 @@ int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p
 {
     // O % 32: whole MFMA blocks; an O that is not a multiple of the 128-channel N tile gets a ragged last tile whose weight
     // DMA reads up to 96 rows past row O of each tap: `wb` must be readable for 96 * Cin elements behind its last row
-    // (orn_conv_bf16_wb_elems; the values are never used)
-    ORN_REQUIRE(Cin % CB_CK == 0 && O % 32 == 0 && O % (s * s) == 0, "conv_bf16_fwd: unsupported Cin=%d O=%d s=%d", Cin, O, s);
+    // (orn_conv_bf16_wb_elems; the values are never used).  Both epilogues store 8 consecutive channels of one sub-pixel: Cn % 8
+    // (s = 2 and 3 imply it; s = 4 does not, e.g. O = 160 gives Cn = 10)
+    ORN_REQUIRE(Cin % CB_CK == 0 && O % 32 == 0 && s >= 1 && O % (s * s) == 0 && (O / (s * s)) % 8 == 0,
+                "conv_bf16_fwd: unsupported Cin=%d O=%d s=%d", Cin, O, s);
     ConvFP p = {};
     p.dbg = g_convf_dbg;
 #ifdef ORN_CONV_STAMP

@@ -92,7 +92,7 @@ ORN_API int orn_conv3x3_ps_silu_bwd(const float *x, const float *wf, const float
                             size_t ws_bytes, void *stream);
 
 /* ---- A4 on the bf16 MFMA path (fp32 accumulate): same contract as the two calls above for B = 1,
- * C <= 96 (zero-padded to 96 in the staging), O % 32 == 0 and O % (s*s) == 0.  Inputs/outputs stay fp32 NCHW; the channels-last bf16
+ * C <= 96 (zero-padded to 96 in the staging), O % 32 == 0, O % (s*s) == 0 and (O/(s*s)) % 8 == 0.  Inputs/outputs stay fp32 NCHW; the channels-last bf16
  * staging (DESIGN.md "data layout") lives in `ws`, which the caller must zero-fill once before the
  * first use (the one-pixel borders are never written).  The engine uses the same kernels without the
  * layout conversions.  fwd: `a` may be NULL (the last block's form: z only), then `z` must not be. */
@@ -105,7 +105,8 @@ ORN_API int orn_conv3x3_ps_silu_bwd_bf16(const float *x, const float *wf, const 
 
 /* The forward conv kernel on the engine's own channels-last bf16 buffers (DESIGN.md "data layout"):
  * xpad [H+2][W+2][C] zero-bordered, wb [9][O'][C], bias_p [O'] (o' = (i*s+j)*Cn + n), z [H*s][W*s][Cn],
- * apad [H*s+2][W*s+2][Cn] or NULL.  C == 96; O % 32 == 0 (O % 96 == 0 for the two-work-group form the large layers take).
+ * apad [H*s+2][W*s+2][Cn] or NULL.  C == 96; O % 32 == 0 and Cn % 8 == 0 (O % 96 == 0 for the two-work-group form the large
+ * layers take; other O run the first form).
  * SLACK: the raw entry points of this group tile N by 96 or 128 channels and compute a ragged last tile on whatever lies behind
  * the operand (results of the missing channels are dropped, never stored).  When O % 128 != 0 the caller must therefore keep
  * `wb` / `wd` READABLE for 96*C elements past their [9][O'][C] / [9][C][O'] extent and `dypad` for 128 elements past its

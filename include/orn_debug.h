@@ -1,5 +1,6 @@
-/* orn_debug.h -- probe-only entry points of liborn.so (tools/probes).  NOT part of the drop-in boundary: nothing here has a
- * reference counterpart, and the flags make results WRONG (they exist to time parts of a kernel in isolation). */
+/* orn_debug.h -- test and probe entry points of liborn.so.  NOT part of the drop-in boundary: nothing here has a reference
+ * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
+ * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -9,6 +10,22 @@ extern "C" {
 /* Timing-only ablation flags of the 16-bit conv / wgrad kernels; effective only in a library built with -DORN_CONV_ABLATE
  * (the product build compiles the switches out).  0 restores normal operation. */
 ORN_API void orn_debug_set(int flags);
+/* The 16-bit conv launchers exactly as the engine calls them, bf16 and IEEE-half builds; buffers and conventions as
+ * orn_conv_nhwc_bf16_fwd / orn_dgrad_nhwc_bf16 in orn.h (same slack rules), plus the arguments the raw entry points fix:
+ *   fwd:   xpad holds Cin (= 96) channels per pixel, zero above the c_real real ones; c_real <= 32 with apad != NULL takes the
+ *          narrow form.  No head fusion.
+ *   dgrad: dx_f32 alone (zprev = dyprev = NULL): fp32 output slabs [Q][H][W][C], Q = O/96 when the image has fewer than 128
+ *          pixel tiles of 8 x 32 and O > 96, else 1 (their sum is dx); c_real <= 32 on a split launch writes channels [0, 32)
+ *          only.  zprev, dyprev and dx_f32 together (only where Q > 1): dx_f32 is the scratch of that split, which is
+ *          then finished into dyprev.  zprev, dyprev alone: the fused epilogue. */
+ORN_API int orn_debug_conv_fwd_bf16(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
+                                    void *z, void *apad, int c_real, void *stream);
+ORN_API int orn_debug_conv_fwd_f16(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
+                                   void *z, void *apad, int c_real, void *stream);
+ORN_API int orn_debug_conv_dgrad_bf16(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev,
+                                      void *dyprev, int sp, float *dx_f32, int c_real, void *stream);
+ORN_API int orn_debug_conv_dgrad_f16(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev,
+                                     void *dyprev, int sp, float *dx_f32, int c_real, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
