@@ -88,7 +88,8 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_conv_fwd_bf16': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, P]),
                'orn_debug_conv_fwd_f16': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, P]),
                'orn_debug_conv_dgrad_bf16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
-               'orn_debug_conv_dgrad_f16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P])}
+               'orn_debug_conv_dgrad_f16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
+               'orn_debug_merge_h16_bwd': (c_int, [c_int, P, P, P, P, P])}
 
 _lib = None
 

@@ -76,7 +76,9 @@ struct MhGroup { int n; int tile_start[MH_MAXP + 1]; MhProb p[MH_MAXP]; };
 // tiles are summed through LDS in wave order (fixed: run-to-run identical).  Rounds 1-2 gave every wave a tile of its own and
 // the whole K: the launch lasted as long as one wave's chain of dependent load batches (7 for K = 864, each a round trip to
 // HBM for operands written a launch ago), ~27 us for 3 GFLOP.
-__global__ void __launch_bounds__(256) k_mgemm_h16(const MhGroup *__restrict__ g, int total_tiles)
+// sc (optional): a dT half (mode 1) that is not finite raises its flag -- |W3^T dWf| > 4 overflows the 2^14 scale even where every
+// |dWf| <= 4 passed the pack's check -- so that the step is skipped instead of writing inf / NaN into dW2 and dW1.
+__global__ void __launch_bounds__(256) k_mgemm_h16(const MhGroup *__restrict__ g, int total_tiles, OrnScaleState *sc)
 {
     ORN_PRIO_HIGH();
     __shared__ float part[4][16][64];
@@ -162,6 +164,7 @@ __global__ void __launch_bounds__(256) k_mgemm_h16(const MhGroup *__restrict__ g
         const int c = n / 9, ij = n - c * 9;
         mh16 *t = p.dtt + (size_t)ij * p.st_t + c;                  // dTt[ij][m][c]
         mh16 *u = p.dtc + (size_t)ij * p.st_c + (size_t)c * p.ldc;   // dTc[ij][c][m]
+        bool bad = false;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int reg = 4 * wave + i, m = tm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
@@ -169,8 +172,10 @@ __global__ void __launch_bounds__(256) k_mgemm_h16(const MhGroup *__restrict__ g
                 const mh16 v = (mh16)sum[i];                         // = dT * 2^14 (B = G carried the scale)
                 t[(size_t)m * p.ldt] = v;
                 u[m] = v;
+                bad |= !(fabsf((float)v) <= 3.0e38f);
             }
         }
+        if (bad) orn_flag_nonfinite(sc, __builtin_nanf(""));
     }
 }
 
@@ -286,9 +291,65 @@ int orn_launch_merge_h16_bwd(const void *dev_tables, const void *host, hipStream
     hipLaunchKernelGGL(k_merge_pack, dim3(H->pack_blocks_grad), dim3(256), 0, st, pack, (int)MH_TAB_GRAD);     // G -> Gh, GT
     ORN_LAUNCH_CHECK("merge_pack");
     const MhGroup *g = (const MhGroup *)dev_tables;
-    hipLaunchKernelGGL(k_mgemm_h16, dim3(H->tiles[0]), dim3(256), 0, st, g, H->tiles[0]);
+    hipLaunchKernelGGL(k_mgemm_h16, dim3(H->tiles[0]), dim3(256), 0, st, g, H->tiles[0], pack.sc);      // dT: the pack's flag
     ORN_LAUNCH_CHECK("mgemm_h16(dW3,dT)");
-    hipLaunchKernelGGL(k_mgemm_h16, dim3(H->tiles[1]), dim3(256), 0, st, g + 1, H->tiles[1]);
+    hipLaunchKernelGGL(k_mgemm_h16, dim3(H->tiles[1]), dim3(256), 0, st, g + 1, H->tiles[1], (OrnScaleState *)nullptr);
     ORN_LAUNCH_CHECK("mgemm_h16(dW2,dW1)");
     return 0;
+}
+
+// ---- test entry point (include/orn_debug.h) ---------------------------------------------------------------------
+// The engine's sequence for one merge set, on buffers of its own: workspace zero-filled once, build, the parameter-side and
+// T -> Th pack jobs (the riders' mh_pack_block, here as launches of their own), the backward, the tail.
+extern "C" int orn_debug_merge_h16_bwd(int n, const int *co, const float *const *in, float *const *out, int *flag, void *stream)
+{
+    ORN_REQUIRE(n >= 1 && n <= ORN_MAX_LAYERS && co && in && out && flag, "debug_merge_h16_bwd: bad arguments");
+    for (int i = 0; i < n; ++i) ORN_REQUIRE(co[2 * i] >= 1 && co[2 * i + 1] >= 1, "debug_merge_h16_bwd: layer %d: C, O >= 1", i);
+    hipStream_t st = (hipStream_t)stream;
+    // workspace: scale state | GEMM tables | per layer: half copies, dW2 tap-major [9][O][2C], dW1 partials [9][2C][C]
+    const size_t a0 = 256, a1 = a0 + orn_align(orn_merge_h16_table_bytes());
+    size_t off[ORN_MAX_LAYERS][3], tot = a1;
+    for (int i = 0; i < n; ++i) {
+        const size_t C = co[2 * i], O = co[2 * i + 1];
+        off[i][0] = tot; tot += orn_align(orn_merge_h16_layer_halfs((int)C, (int)O) * 2);
+        off[i][1] = tot; tot += orn_align(9 * O * 2 * C * 4);
+        off[i][2] = tot; tot += orn_align(9 * 2 * C * C * 4);
+    }
+    char *ws = nullptr;
+    ORN_HIP(hipMalloc(&ws, tot));
+    void *host = malloc(orn_merge_h16_host_bytes());
+    int rc = host ? 0 : ORN_E_ARG;
+    OrnScaleState *sc = (OrnScaleState *)ws;
+    OrnMergeLayer L[ORN_MAX_LAYERS] = {};
+    OrnMergeMisc M[ORN_MAX_LAYERS] = {};
+    void *bufs[ORN_MAX_LAYERS];
+    for (int i = 0; i < n; ++i) {
+        const float *const *p = in + 6 * i;
+        float *const *q = out + 7 * i;
+        OrnMergeLayer &l = L[i];
+        l.C = co[2 * i]; l.O = co[2 * i + 1];
+        l.g = p[0]; l.T = const_cast<float *>(p[2]); l.w1 = p[3]; l.w2 = p[4]; l.w3 = p[5];
+        l.dw3 = q[0]; l.dw2 = q[1]; l.dw2t = (float *)(ws + off[i][1]); l.dw1p = (float *)(ws + off[i][2]);
+        bufs[i] = ws + off[i][0];
+        M[i] = OrnMergeMisc{};
+        M[i].C = l.C; M[i].O = l.O; M[i].g = l.g; M[i].dbf = p[1]; M[i].dw1p = l.dw1p;
+        M[i].dw1 = q[2]; M[i].d1x3 = q[3]; M[i].d3x1 = q[4]; M[i].db1x3 = q[5]; M[i].db3x1 = q[6];
+        M[i].dw2t = l.dw2t; M[i].dw2 = q[1];
+    }
+    OrnScaleState s0 = {};
+    s0.gs = s0.inv_gs = s0.gs_max = 1.0f;
+    hipError_t e = hipSuccess;
+    if (rc == 0 && (e = hipMemset(ws, 0, tot)) == hipSuccess) e = hipMemcpy(sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
+    if (rc == 0 && e != hipSuccess) { orn_set_error("debug_merge_h16_bwd: %s", hipGetErrorString(e)); rc = (int)e; }
+    if (rc == 0) rc = orn_merge_h16_build(ws + a0, host, n, L, bufs, sc);
+    if (rc == 0) rc = orn_launch_merge_h16_pack_jobs(host, MH_TAB_PAR, st);
+    if (rc == 0) rc = orn_launch_merge_h16_pack_jobs(host, MH_TAB_T, st);
+    if (rc == 0) rc = orn_launch_merge_h16_bwd(ws + a0, host, st, sc);
+    if (rc == 0) rc = orn_launch_merge_bwd_tail_all(n, M, st);
+    if (rc == 0 && (e = hipStreamSynchronize(st)) == hipSuccess) e = hipMemcpy(&s0, sc, sizeof(s0), hipMemcpyDeviceToHost);
+    if (rc == 0 && e != hipSuccess) { orn_set_error("debug_merge_h16_bwd: %s", hipGetErrorString(e)); rc = (int)e; }
+    if (rc == 0) *flag = s0.flag;
+    free(host);
+    (void)hipFree(ws);
+    return rc;
 }

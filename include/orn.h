@@ -265,19 +265,20 @@ ORN_API int orn_engine_train_steps_graph(orn_engine *e, const float *frames, con
  *    orn_engine_train_step advances every step): one halving per group however many of its steps overflowed;
  *  - Adam's step numbers of a group are fixed when it is launched: a step skipped INSIDE a group leaves the bias corrections of
  *    the at most 3 steps behind it one count ahead (the next group is exact again);
- *  - the merge backward of the 16-bit modes rounds the UN-scaled weight gradient times 2^14 to IEEE half: |dWf| > 4 raises the
- *    same flag, and no loss scale cures that.  Such a fit has diverged; main_train restores the start of the epoch and
- *    continues in a wider precision (bf16 keeps that operand format, fp32 does not have it);
+ *  - the merge backward of the 16-bit modes rounds the UN-scaled weight gradient times 2^14 to IEEE half, and carries
+ *    dT = W3^T dWf in half at the same scale: |dWf| > 4 and |W3^T dWf| > 4 raise the same flag, and no loss scale cures that.
+ *    Such a fit has diverged; main_train restores the start of the epoch and continues in a wider precision (bf16 keeps that
+ *    operand format, fp32 does not have it);
  *  - Adam's step count, in the device schedule and in the checkpoint's optimizer entry, excludes skipped steps;
  *  - orn_engine_train_steps (pipelined form) advances the schedule every step, like orn_engine_train_step.  The skip decision of a
  *    step is taken by the Adam launch on the caller's stream, behind every detector that runs there (the loss, the hand-off into
- *    the fp32 part, the lower blocks' slab reduction and merge-backward pack, the head's dW finish is on the side stream but the dy it
- *    sums is covered by the lower blocks' detectors: a non-finite dy of the last block reaches them through the dgrad chain), and
+ *    the fp32 part, the lower blocks' slab reduction and merge-backward half copies, the head's dW finish is on the side stream but
+ *    the dy it sums is covered by the lower blocks' detectors: a non-finite dy of the last block reaches them through the dgrad chain), and
  *    the side stream's Adam launch (last block + head) follows that decision.  Two detectors of the side branch run BEHIND the
- *    decision: the last block's slab reduction (unreachable alone, by the argument above) and the fp16 copy of its merged-kernel
- *    gradient (|dWf| > 4).  If one of them fires alone (a LATE-ONLY skip), only the side stream's update of that step is skipped:
- *    the lower blocks take it, the last block and the head do not, the parameters stay finite.  It is counted apart from the
- *    skipped steps (out8[7]), and the scale backs off for it at the next advance or, when the side branch's Adam launch runs
+ *    decision: the last block's slab reduction (unreachable alone, by the argument above) and the fp16 copies of its merged-kernel
+ *    gradient and of dT in its merge backward (|dWf| > 4, |W3^T dWf| > 4).  If one of them fires alone (a LATE-ONLY skip), only
+ *    the side stream's update of that step is skipped: the lower blocks take it, the last block and the head do not, the parameters
+ *    stay finite.  It is counted apart from the skipped steps (out8[7]), and the scale backs off for it at the next advance or, when the side branch's Adam launch runs
  *    behind that one, at the advance after it.  Adam's step numbers (device schedule, checkpoint) do not exclude it: the lower
  *    blocks did apply the step.  This is the one case in which the pipelined form differs from the serial forms, which skip and
  *    count the whole step. */

@@ -1,6 +1,7 @@
 /* orn_debug.h -- test and probe entry points of liborn.so.  NOT part of the drop-in boundary: nothing here has a reference
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
- * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them). */
+ * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
+ * the merge backward's (tests/test_gpu_merge16.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -26,6 +27,15 @@ ORN_API int orn_debug_conv_dgrad_bf16(const void *dypad, const void *wd, int H, 
                                       void *dyprev, int sp, float *dx_f32, int c_real, void *stream);
 ORN_API int orn_debug_conv_dgrad_f16(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev,
                                      void *dyprev, int sp, float *dx_f32, int c_real, void *stream);
+/* The merge backward of the 16-bit engine modes (ERB: dW3, dT, dW2, dW1 on half operand copies, then the slices) on n = 1..8
+ * layers in one set, with the launchers and the call sequence of the engine; workspace and scale state of its own, allocated
+ * and freed inside, `stream` synchronised.  Host arrays, per layer i:
+ *   co[2i ..]:  C, O
+ *   in[6i ..]:  G = dL/dWf [O][C][3][3], dbf [O], T [O][C][3][3], w1 [2C][C], w2 [O][2C][3][3], w3 [O][O]   (fp32, device)
+ *   out[7i ..]: dW3 [O][O], dW2 [O][2C][3][3], dW1 [2C][C], d1x3 [O][C][3], d3x1 [O][C][3], db1x3 [O], db3x1 [O]  (fp32, device)
+ * *flag: the flag word of the scale state after the call (1: a half copy of G or of dT was not finite).  Returns 0 or an
+ * error code. */
+ORN_API int orn_debug_merge_h16_bwd(int n, const int *co, const float *const *in, float *const *out, int *flag, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);

@@ -6,7 +6,8 @@ gradients the other test files pin to the CPU oracle."""
 import pytest
 import torch
 
-from helpers import pipelined_vs_oracle
+from helpers import GEOS, pipelined_vs_oracle
+from helpers import small_engine as _engine
 
 pytestmark = pytest.mark.gpu
 
@@ -17,31 +18,6 @@ def orn():
     from orn_amd import ops, model, utils, engine  # noqa: F401
     orn_amd._lib.lib()
     return orn_amd
-
-
-GEOS = {
-    # two blocks with 96 input channels: both on the 16-bit path, no fp32 block below them
-    'c96x2': dict(fc='3_4_96', strides=[2, 2], lower_width=96),
-    # the bench geometry in small: an fp32 first block (26 channels), a narrow block, two 96-channel blocks
-    'narrow_first': dict(fc='2_3_26', strides=[5, 2, 2, 2], lower_width=96),
-    # a stride-3 block in the middle (config 3's shape)
-    'stride3': dict(fc='2_3_26', strides=[5, 3, 2], lower_width=96),
-}
-
-
-def _engine(orn, prec, branch, geo, n_frames=5, seed=1):
-    from oracle import cpu_ref
-    g = GEOS[geo]
-    torch.manual_seed(seed)
-    gen = orn.model.Generator(embed_length=80, stem_dim_num='32_1', fc_hw_dim=g['fc'], expansion=1, num_blocks=1, norm='none',
-                              act='swish', bias=True, reduction=2, conv_type='conv', stride_list=g['strides'], sin_res=True,
-                              lower_width=g['lower_width'], sigmoid=False, deploy=False, branch_type=branch)
-    eng = orn.engine.TrainEngine(gen, loss_type='Fusion6', beta=0.5, precision=prec)
-    hw = eng.out_hw
-    frames = cpu_ref.synthetic_video(n_frames, hw[0], hw[1], seed=5)
-    embeds = cpu_ref.positional_encoding(torch.tensor([k / n_frames for k in range(n_frames)]), 1.25, 40)
-    eng.set_video(frames, embeds)
-    return eng
 
 
 def _run(orn, prec, branch, geo, mode, steps, calls):
