@@ -66,7 +66,7 @@ struct orn_engine {
     hipStream_t g_stream;
     // Pipelined form of the step (orn_engine_train_steps; 16-bit engines with >= 2 blocks on the fast path): the LAST block's
     // weight gradient, slab reduction, merge backward, Adam update and next merge forward run on a second stream (`side`),
-    // forked off the caller's stream inside the backward (side_fork_at: behind the last block's dgrad) and joined in front of the
+    // forked off the caller's stream inside the backward (fork_behind_dgrad, below) and joined in front of the
     // last block's forward conv of the NEXT step.  That chain -- one full-chip MFMA launch and a tail of small ones -- then runs beside the latency-bound
     // launches of the step boundary (merge backward / Adam / merge forward of the lower blocks, stem, first blocks) instead of
     // in front of them.  Same arithmetic as the serial step (bit-identical results); what it needs:
@@ -87,6 +87,10 @@ struct orn_engine {
     OrnScaleState *sc_side;
     size_t side_lo;                  // parameters [side_lo, n_params) belong to the side branch's Adam launch (last block + head)
     bool pipe_ok;                    // this engine can run the pipelined form
+    // The shape of the pipelined step, decided once in orn_engine_create (the measurements behind each choice are there)
+    bool side_below;                 // the side branch also takes the weight gradient of the block BELOW the last one (ahead of the last block's)
+    bool fork_behind_dgrad;          // the side branch forks behind the last block's dgrad; else behind the lower blocks' slab reduction
+    int last_smax;                   // split-K slab cap of the last block's weight gradient, in every form of the step (0: the default rule)
     bool side_busy;                  // a side branch is in flight (joined by the next step's forward or at the end of the call)
     // orn_engine_profile_step: HIP events around every forward conv launch of an eager step
     bool prof;
@@ -97,7 +101,26 @@ struct orn_engine {
 static_assert(ORN_SCALE_SLOTS >= ORN_GRAPH_UNROLL, "one scale-state entry per step of the unrolled graph");
 
 static inline size_t al(size_t floats) { return orn_align(floats * 4) / 4; }
-static bool side_takes_below(const orn_engine *e);
+
+// the five events of the pipelined step (struct orn_engine, `side`)
+static hipEvent_t orn_engine::*const SIDE_EVENTS[] = {&orn_engine::ev_fork, &orn_engine::ev_adam, &orn_engine::ev_wgrad, &orn_engine::ev_join,
+                                                      &orn_engine::ev_below};
+
+// Split-K slabs of the LAST block's weight gradient on an engine that can run the pipelined step: fewer, longer work-groups (one
+// per CU, or little more) leave room on every CU for the launches that run beside it.  Measured on the 720p step (tools/probes, round 4):
+// 40 / 32 / 24 slabs = 1.050 / 1.015..1.024 / 1.019..1.023 ms per pipelined step in the final form of the branch (DESIGN 4.7; 32 and 24
+// are equal within the noise of a box, 24 moves less data).  The serial forms of the step use the same count, so that all forms of
+// the step give bit-identical results.  (The block below the last keeps the default rule: 32 / 40 / 16 slabs for it were measured, none faster.)
+static constexpr int ORN_LAST_SMAX = 24;
+
+// the graph cache is dropped whenever what a captured step does (or is given) changes
+static void drop_graphs(orn_engine *e)
+{
+    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
+    if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
+    if (e->graph_exec_u) { (void)hipGraphExecDestroy(e->graph_exec_u); e->graph_exec_u = nullptr; }
+    if (e->graph_u) { (void)hipGraphDestroy(e->graph_u); e->graph_u = nullptr; }
+}
 
 extern "C" size_t orn_conv3x3_ps_silu_bwd_ws_bytes(int B, int C, int O, int H, int W);
 extern "C" size_t orn_erb_merge_bwd_ws_bytes(int C, int O);
@@ -271,7 +294,8 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     e->graph = nullptr; e->graph_exec = nullptr; e->graph_u = nullptr; e->graph_exec_u = nullptr;
     e->prof = false;
     for (int k = 0; k < 3; ++k) { e->mset[k].n = 0; e->mset[k].mh_host = nullptr; }
-    e->side = nullptr; e->ev_fork = e->ev_adam = e->ev_wgrad = e->ev_join = e->ev_below = nullptr;
+    e->side = nullptr;
+    for (auto ev : SIDE_EVENTS) e->*ev = nullptr;
     e->pipe_ok = false; e->side_busy = false; e->side_lo = 0;
     for (int i = 0; i < 4 * ORN_MAX_LAYERS + 4; ++i) e->prof_ev[i] = nullptr;
     e->ops = (d->precision == 2) ? orn_half_ops_f16() : orn_half_ops_bf16();
@@ -289,11 +313,11 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     }
     // Can this engine run the pipelined step?  16-bit mode with the last block AND the block below it on the fast path (the
     // hand-off points are their buffers), gradients present, and an arena in which the last block's tensors and the head's lie
-    // behind everything else (one Adam launch per stream).  ORN_NO_PIPELINE: tools/probes A/B.
+    // behind everything else (one Adam launch per stream).
     {
         const int nl = d->n_layers;
         const orn_layer_desc &ll = d->layer[nl - 1];
-        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v && orn_probe_env("ORN_NO_PIPELINE") == nullptr;
+        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v;
         if (ok) {
             const int64_t lo_all[9] = {ll.w3x3, ll.b3x3, ll.w3x1, ll.b3x1, ll.w1x3, ll.b1x3, ll.w1, ll.w2, ll.w3};
             int64_t lo = d->n_params;
@@ -311,15 +335,28 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
             // launches of the middle blocks -- but while such a queue exists, even idle, every OTHER stream of the process loses: the
             // fp32 engine's step, run next to an idle fp16 engine, went 6.66 -> 8.25 ms.  Default priority.)
             hipError_t rc = hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking);
-            hipEvent_t *evs[5] = {&e->ev_fork, &e->ev_adam, &e->ev_wgrad, &e->ev_join, &e->ev_below};
             // hipEventDisableSystemFence: these events order streams of ONE device; what the flag gives up is visibility to the host and
             // to other devices at the record (hip_runtime_api.h), which the caller's own synchronisation of its stream provides.  The
-            // record is then a lighter packet: ~4 us per step (3 records / waits on the caller's stream).  ORN_EVENT_FENCE=1: the default events.
-            const unsigned evflags = hipEventDisableTiming | (orn_probe_env("ORN_EVENT_FENCE") ? 0u : (unsigned)hipEventDisableSystemFence);
-            for (int k = 0; k < 5 && rc == hipSuccess; ++k) rc = hipEventCreateWithFlags(evs[k], evflags);
+            // record is then a lighter packet: ~4 us per step (3 records / waits on the caller's stream) against the default events.
+            for (auto ev : SIDE_EVENTS)
+                if (rc == hipSuccess) rc = hipEventCreateWithFlags(&(e->*ev), hipEventDisableTiming | hipEventDisableSystemFence);
             if (rc != hipSuccess) { orn_set_error("engine_create: side stream: %s", hipGetErrorString(rc)); orn_engine_destroy(e); return (int)rc; }
         }
         e->pipe_ok = ok;
+        e->last_smax = ok ? ORN_LAST_SMAX : 0;
+        // Where the side branch forks off the backward.  Measured on the 720p step with the last block alone on the branch, one box
+        // (tools/probes/mode_ab.sh; serial 1.079 ms): fork behind the head's backward 1.038, behind the dgrad of layer 4 (the last block)
+        // 1.058, 3 1.024, 2 1.032, 1 1.035, 0 1.067, behind the lower blocks' weight gradients and their reduction 1.050 ms -- the last
+        // block's own dgrad and the launch behind it are full-chip MFMA launches that the side branch's weight gradient only thrashes;
+        // behind them the caller's stream runs under-filled launches, and the earlier the branch starts the earlier it is back for the
+        // next forward.
+        // With a fast block between the last one and the first fast layer, the side stream also takes the weight gradient of the block
+        // below the last one (ahead of the last block's), and then forks one launch earlier, behind the last block's dgrad (whose output is
+        // that wgrad's dy): that wgrad (216 work-groups at 720p) runs beside the block's own dgrad launch (230 work-groups on 512 slots), and
+        // the lower blocks' batched wgrad on the caller's stream shrinks to a third (95 -> 40 us at 720p).  Same box: 1.037 -> 1.021 ms per
+        // step.  With exactly two blocks on the fast path the branch keeps the last block alone and forks behind the slab reduction.
+        e->side_below = ok && nl - 2 > e->ff;
+        e->fork_behind_dgrad = e->side_below;
     }
     if (!d->erb)
         for (int i = 0; i < d->n_layers; ++i) {
@@ -374,15 +411,11 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
 extern "C" void orn_engine_destroy(orn_engine *e)
 {
     if (!e) return;
-    if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
-    if (e->graph) (void)hipGraphDestroy(e->graph);
-    if (e->graph_exec_u) (void)hipGraphExecDestroy(e->graph_exec_u);
-    if (e->graph_u) (void)hipGraphDestroy(e->graph_u);
+    drop_graphs(e);
     for (int i = 0; i < 4 * ORN_MAX_LAYERS + 4; ++i)
         if (e->prof_ev[i]) (void)hipEventDestroy(e->prof_ev[i]);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
-    hipEvent_t evs[5] = {e->ev_fork, e->ev_adam, e->ev_wgrad, e->ev_join, e->ev_below};
-    for (int k = 0; k < 5; ++k) if (evs[k]) (void)hipEventDestroy(evs[k]);
+    for (auto ev : SIDE_EVENTS) if (e->*ev) (void)hipEventDestroy(e->*ev);
     for (int k = 0; k < 3; ++k) free(e->mset[k].mh_host);
     delete e;
 }
@@ -394,10 +427,7 @@ extern "C" int orn_engine_set_grad_mask(orn_engine *e, const float *mask)
     ORN_REQUIRE(e, "engine_set_grad_mask: null engine");
     ORN_REQUIRE((uintptr_t)mask % 16 == 0, "engine_set_grad_mask: mask must be 16-byte aligned");
     e->gmask = mask;
-    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
-    if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-    if (e->graph_exec_u) { (void)hipGraphExecDestroy(e->graph_exec_u); e->graph_exec_u = nullptr; }
-    if (e->graph_u) { (void)hipGraphDestroy(e->graph_u); e->graph_u = nullptr; }
+    drop_graphs(e);
     return 0;
 }
 
@@ -408,10 +438,7 @@ extern "C" int orn_engine_set_target_stats(orn_engine *e, const float *stats)
     ORN_REQUIRE(e, "engine_set_target_stats: null engine");
     ORN_REQUIRE((uintptr_t)stats % 16 == 0, "engine_set_target_stats: stats must be 16-byte aligned");
     e->tstats = stats;
-    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
-    if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-    if (e->graph_exec_u) { (void)hipGraphExecDestroy(e->graph_exec_u); e->graph_exec_u = nullptr; }
-    if (e->graph_u) { (void)hipGraphDestroy(e->graph_u); e->graph_u = nullptr; }
+    drop_graphs(e);
     return 0;
 }
 
@@ -509,9 +536,30 @@ __global__ void k_advance(const orn_step_sched *__restrict__ sched, int32_t *cur
 // forward needs no stored activation either
 static bool f32_head_on_z(const orn_engine *e)
 {
-    static const bool no_head_fuse = orn_probe_env("ORN_F32_HEAD_UNFUSED") != nullptr;       // tools/probes A/B
     const orn_engine_desc &d = e->d;
-    return e->ff >= d.n_layers && e->head_ws && d.layer[d.n_layers - 1].s == 2 && !no_head_fuse;
+    return e->ff >= d.n_layers && e->head_ws && d.layer[d.n_layers - 1].s == 2;
+}
+
+// The per-layer descriptors of the fast path's batched launches.  The slab cap of a layer's weight gradient comes from slab_cap()
+// alone, so a wgrad job and the reduction of its slabs cannot disagree (a mismatch would be a silent change of the summation order).
+static int slab_cap(const orn_engine *e, int i) { return i == e->d.n_layers - 1 ? e->last_smax : 0; }
+
+static OrnPrepLayer prep_layer(const orn_engine *e, int i)
+{
+    const orn_layer_desc &l = e->d.layer[i];
+    return OrnPrepLayer{e->L[i].wf, e->L[i].bf, l.O, l.C, l.s, e->L[i].wb, e->L[i].wd, e->L[i].biasp, ORN_FAST_C};
+}
+
+static OrnWgradJob wgrad_job(const orn_engine *e, int i)
+{
+    const orn_layer_desc &l = e->d.layer[i];
+    return OrnWgradJob{e->L[i].xpad, e->L[i].dypad, l.H, l.W, l.C, l.O, l.s, e->L[i].wslab, slab_cap(e, i)};
+}
+
+static OrnWgradReduce wgrad_reduce(const orn_engine *e, int i, OrnScaleState *sc)
+{
+    const orn_layer_desc &l = e->d.layer[i];
+    return OrnWgradReduce{e->L[i].wslab, l.H, l.W, l.C, l.O, l.s, 1.0f / e->gs, e->grads + l.w3x3, e->grads + l.b3x3, sc, slab_cap(e, i)};
 }
 
 // set: which layers this forward merges (0 all; 1: all but the last block, whose merged kernel the side branch of the previous
@@ -547,10 +595,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
     if (ff < nl && !d.erb) {      // 16-bit operand copies of every fast layer's kernel, one launch (ERB: written by the merge's S launch)
         OrnPrepLayer pl[ORN_MAX_LAYERS];
         const int np = (set == 1 ? nl - 1 : nl) - ff;       // (pipelined step: the side branch prepares the last block's)
-        for (int i = ff; i < ff + np; ++i) {
-            const orn_layer_desc &l = d.layer[i];
-            pl[i - ff] = OrnPrepLayer{e->L[i].wf, e->L[i].bf, l.O, l.C, l.s, e->L[i].wb, e->L[i].wd, e->L[i].biasp, ORN_FAST_C};
-        }
+        for (int i = ff; i < ff + np; ++i) pl[i - ff] = prep_layer(e, i);
         ORN_TRY(e->ops->prep_all(np, pl, st));
     }
     OrnHeadFuse hf = {};
@@ -564,10 +609,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
                 OrnPrepLayer pl[ORN_MAX_LAYERS];
                 int np = 0;
                 if (d.erb)
-                    for (int j = ff; j < (set == 1 ? nl - 1 : nl); ++j) {
-                        const orn_layer_desc &lj = d.layer[j];
-                        pl[np++] = OrnPrepLayer{e->L[j].wf, e->L[j].bf, lj.O, lj.C, lj.s, e->L[j].wb, e->L[j].wd, e->L[j].biasp, ORN_FAST_C};
-                    }
+                    for (int j = ff; j < (set == 1 ? nl - 1 : nl); ++j) pl[np++] = prep_layer(e, j);
                 ORN_TRY(orn_launch_stage0_fwd(x, b.wf, b.bf, l.C, l.O, l.H, l.W, l.s, keep_z ? b.z : nullptr, e->L[1].xpad, ORN_FAST_C,
                                               d.precision, st, np, pl, pack_t, pack_t_blocks));
             }
@@ -587,7 +629,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
             const bool last = (i + 1 == nl);
             // pipelined step: the side branch of the previous step still reads the last block's input buffer (its weight gradient)
             // until ev_wgrad, and writes that block's merged kernel (and the head's parameters) until ev_join
-            if (e->side_busy && i + 3 == nl && side_takes_below(e)) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));   // (this conv overwrites the input of the block below the last)
+            if (e->side_busy && i + 3 == nl && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));   // (this conv overwrites the input of the block below the last)
             if (e->side_busy && i + 2 == nl) ORN_HIP(hipStreamWaitEvent(st, e->ev_wgrad, 0));
             if (e->side_busy && last) { ORN_HIP(hipStreamWaitEvent(st, e->ev_join, 0)); e->side_busy = false; }
             if (last) hf = OrnHeadFuse{P + d.head_w, P + d.head_b, e->img, d.sigmoid, 0};
@@ -618,8 +660,6 @@ extern "C" int orn_engine_decode(orn_engine *e, const float *embed, float *img, 
     return 0;
 }
 
-// adv_count > 0: advance the device-side schedule by that many steps first (states e->cur[0 .. adv_count)); the step itself
-// runs on e->cur[cur_idx]
 static OrnMergeMisc merge_misc(const orn_engine *e, int i)
 {
     const orn_layer_desc &l = e->d.layer[i];
@@ -633,71 +673,27 @@ static OrnMergeMisc merge_misc(const orn_engine *e, int i)
     return m;
 }
 
-// Split-K slabs of the LAST block's weight gradient on an engine that can run the pipelined step: fewer, longer work-groups (one
-// per CU, or little more) leave room on every CU for the launches that run beside it.  Measured on the 720p step (tools/probes, round 4):
-// 40 / 32 / 24 slabs = 1.050 / 1.015..1.024 / 1.019..1.023 ms per pipelined step in the final form of the branch (DESIGN 4.7; 32 and 24
-// are equal within the noise of a box, 24 moves less data).  The serial forms of the step use the same count, so that all forms of
-// the step give bit-identical results.
-static int last_smax(const orn_engine *e)
-{
-    static const int smax = orn_probe_env_int("ORN_SIDE_SMAX", 24);
-    return e->pipe_ok ? smax : 0;
-}
-
-// Where the side branch forks off the backward: behind the dgrad launch of this layer (n_layers: behind the head's backward);
-// -1: behind the lower blocks' weight gradients and their reduction, in front of the merge backward.  Default: behind the dgrad of
-// the block below the last one.  Measured on the 720p step, one box (tools/probes/mode_ab.sh; serial 1.079 ms): fork behind layer
-// 5 (the head) 1.038, 4 1.058, 3 1.024, 2 1.032, 1 1.035, 0 1.067, -1 1.050 ms -- the last block's own dgrad and the launch behind
-// it are full-chip MFMA launches that the side branch's weight gradient only thrashes; behind them the caller's stream runs
-// under-filled launches, and the earlier the branch starts the earlier it is back for the next forward.
-// The side stream also takes the weight gradient of the block below the last one (ahead of the last block's), and then forks one
-// launch earlier, behind the last block's dgrad: that wgrad (216 work-groups at 720p) runs beside the block's own dgrad launch (230
-// work-groups on 512 slots), and the lower blocks' batched wgrad on the caller's stream shrinks to a third (95 -> 40 us at 720p).
-// Same box: 1.037 -> 1.021 ms per step.  ORN_SIDE_BELOW=0: tools/probes A/B.
-static bool side_takes_below(const orn_engine *e)
-{
-    static const bool on = orn_probe_env_int("ORN_SIDE_BELOW", 1) != 0;
-    return on && e->pipe_ok && e->d.n_layers - 2 > e->ff;
-}
-
-static int below_smax(const orn_engine *e)
-{
-    static const int smax = orn_probe_env_int("ORN_BELOW_SMAX", 0);      // probe: slab cap of the block below the last (0: the default rule)
-    return side_takes_below(e) ? smax : 0;
-}
-
-static int side_fork_at(const orn_engine *e)
-{
-    static const int at = orn_probe_env_int("ORN_SIDE_FORK", -2);
-    if (at == -2 && side_takes_below(e)) return e->d.n_layers - 1;
-    if (at == -2) return e->d.n_layers - 2 > e->ff ? e->d.n_layers - 2 : -1;      // default
-    if (side_takes_below(e) && at > e->d.n_layers - 1) return e->d.n_layers - 1;      // (that wgrad needs the last block's dgrad output)
-    return at > e->d.n_layers ? e->d.n_layers : at;
-}
-
-// The side branch of a pipelined step, first half (enqueued at the fork point, side_fork_at): the weight gradient of the block below the
-// last one (side_takes_below), then the last block's weight gradient (+ the head's dW / db finish), its slab reduction, its merge backward.
+// The side branch of a pipelined step, first half (enqueued at the fork point, fork_behind_dgrad): the weight gradient of the block below the
+// last one (side_below), then the last block's weight gradient (+ the head's dW / db finish), its slab reduction, its merge backward.
 static int side_branch_backward(orn_engine *e, hipStream_t st)
 {
     const orn_engine_desc &d = e->d;
     const int nl = d.n_layers;
-    const orn_layer_desc &l = d.layer[nl - 1];
     float *G = e->grads;
     hipStream_t sd = e->side;
     OrnScaleState *sc = e->sc_side;                     // this step's scale, copied by the loss's finalize stage; the branch's detections
     ORN_HIP(hipEventRecord(e->ev_fork, st));
     ORN_HIP(hipStreamWaitEvent(sd, e->ev_fork, 0));
-    if (side_takes_below(e)) {      // (its dy is the output of the dgrad launch this branch forks behind; its slabs are reduced on the caller's stream)
-        const orn_layer_desc &lb = d.layer[nl - 2];
-        const OrnWgradJob wb = {e->L[nl - 2].xpad, e->L[nl - 2].dypad, lb.H, lb.W, lb.C, lb.O, lb.s, e->L[nl - 2].wslab, below_smax(e)};
+    if (e->side_below) {      // (its dy is the output of the dgrad launch this branch forks behind; its slabs are reduced on the caller's stream)
+        const OrnWgradJob wb = wgrad_job(e, nl - 2);
         ORN_TRY(e->ops->wgrad_batch(1, &wb, sd, nullptr, nullptr, 1));
         ORN_HIP(hipEventRecord(e->ev_below, sd));
     }
-    const OrnWgradJob wj = {e->L[nl - 1].xpad, e->L[nl - 1].dypad, l.H, l.W, l.C, l.O, l.s, e->L[nl - 1].wslab, last_smax(e)};
+    const OrnWgradJob wj = wgrad_job(e, nl - 1);
     const OrnHeadFinish hf = {e->head_ws, e->ops->head_bwd_blocks(e->Hout, e->Wout), e->Cn_last, 1.0f / e->gs, G + d.head_w, G + d.head_b, sc};
     ORN_TRY(e->ops->wgrad_batch(1, &wj, sd, &hf, nullptr, 1));
     ORN_HIP(hipEventRecord(e->ev_wgrad, sd));           // the last block's input buffer is free again
-    const OrnWgradReduce wr = {e->L[nl - 1].wslab, l.H, l.W, l.C, l.O, l.s, 1.0f / e->gs, G + l.w3x3, G + l.b3x3, sc, last_smax(e)};
+    const OrnWgradReduce wr = wgrad_reduce(e, nl - 1, sc);
     ORN_TRY(e->ops->wgrad_reduce_all(1, &wr, sd, nullptr));
     if (d.erb) {
         const orn_engine::MergeSet &ms = e->mset[2];
@@ -722,51 +718,96 @@ static int side_branch_update(orn_engine *e, bool more)
     ORN_HIP(hipStreamWaitEvent(sd, e->ev_adam, 0));
     ORN_TRY(orn_launch_adam(e->params + lo, e->grads + lo, e->m + lo, e->v + lo, (size_t)d.n_params - lo, 0.0, 1, e->cur_side, d.beta1, d.beta2,
                             d.eps, 1.0f, sd, e->gmask ? e->gmask + lo : nullptr, e->sc_side, nullptr, nullptr, false, e->sc));
-    if (!more) {
-    } else if (d.erb) {
+    const void *packs = nullptr;        // (16-bit ERB) the branch's pack jobs, launched behind the join event
+    if (more && d.erb) {
         const orn_engine::MergeSet &ms = e->mset[2];
-        int pk_par = 0, pk_t = 0;
-        const void *pk = ms.mh_host ? orn_merge_h16_pack(ms.mh_host, &pk_par, &pk_t) : nullptr;
         const OrnLinearJob none = {};
-        // The pack jobs that ride on these launches in the serial step (half copies for the NEXT merge backward of this block: needed
-        // a whole step later) are launches of their own BEHIND the join event here: the branch's S launch runs while the 8-wave forward
-        // conv of the block below holds all but a few CUs, and 160 rider work-groups in front of its 84 tiles cost it those.
-        static const bool late_packs = orn_probe_env("ORN_SIDE_RIDERS") == nullptr;
-        ORN_TRY(orn_launch_w2_transpose(ms.n, ms.ml, sd, late_packs ? nullptr : pk, late_packs ? 0 : pk_par));
+        ORN_TRY(orn_launch_w2_transpose(ms.n, ms.ml, sd));
         ORN_TRY(orn_launch_merge_group_linear(ms.tables, 0, ms.tiles[0], none, sd));
-        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], none, sd, late_packs ? nullptr : pk, late_packs ? 0 : pk_t));   // the S epilogue writes the 16-bit operand copies
-        if (late_packs && pk) {
-            ORN_HIP(hipEventRecord(e->ev_join, sd));
-            ORN_TRY(orn_launch_merge_h16_pack_jobs(ms.mh_host, 1, sd));
-            ORN_TRY(orn_launch_merge_h16_pack_jobs(ms.mh_host, 2, sd));
-            e->side_busy = true;
-            return 0;
-        }
-    } else {
-        const orn_layer_desc &l = d.layer[nl - 1];
-        const OrnPrepLayer pl = {e->L[nl - 1].wf, e->L[nl - 1].bf, l.O, l.C, l.s, e->L[nl - 1].wb, e->L[nl - 1].wd, e->L[nl - 1].biasp, ORN_FAST_C};
+        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], none, sd));   // the S epilogue writes the 16-bit operand copies
+        packs = ms.mh_host;
+    } else if (more) {
+        const OrnPrepLayer pl = prep_layer(e, nl - 1);
         ORN_TRY(e->ops->prep_all(1, &pl, sd));
     }
     ORN_HIP(hipEventRecord(e->ev_join, sd));
+    if (packs) {
+        // The pack jobs that ride on these launches in the serial step (half copies for the NEXT merge backward of this block: needed
+        // a whole step later) are launches of their own BEHIND the join event here: the branch's S launch runs while the 8-wave forward
+        // conv of the block below holds all but a few CUs, and 160 rider work-groups in front of its 84 tiles cost it those (as riders:
+        // +3..10 us per step).
+        ORN_TRY(orn_launch_merge_h16_pack_jobs(packs, 1, sd));
+        ORN_TRY(orn_launch_merge_h16_pack_jobs(packs, 2, sd));
+    }
     e->side_busy = true;
     return 0;
 }
 
-// pipe: the pipelined form (struct orn_engine, `side`): the last block's weight-gradient chain leaves this step on the side stream
-static int train_step(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
-                      int32_t *cursor, float *stats_out, int32_t n_slots, hipStream_t st, int adv_count = 1, int cur_idx = 0,
-                      bool pipe = false, bool more = false)
+// Weight gradients of every fast layer the caller's stream keeps: nothing on the dgrad chain needs them, so they run behind it as ONE
+// launch (the small layers' 72 / 216 / 360 work-groups pack behind the last block's 504 instead of leaving CUs idle one launch
+// at a time: -37 us per 720p step), followed by ONE launch that reduces every layer's split-K slabs (-27 us).  The stem backward's
+// deferred kernels (needed by Adam only) ride on the two launches.
+static int fast_weight_grads(orn_engine *e, hipStream_t st, bool pipe, OrnScaleState *sc, const OrnStemL2Job *l2job, const OrnStemW0Job *w0job)
 {
     const orn_engine_desc &d = e->d;
+    const int nl = d.n_layers, ff = e->ff;
+    OrnWgradJob wj[ORN_MAX_LAYERS];
+    int nj = 0;
+    const int n_main = pipe ? nl - 1 : nl;      // (pipelined step: the last block's is the side branch's)
+    for (int i = n_main - 1; i >= ff; --i) {    // largest first
+        if (pipe && i == nl - 2 && e->side_below) continue;      // (the side stream's)
+        wj[nj++] = wgrad_job(e, i);
+    }
+    const OrnHeadFinish hf = {e->head_ws, e->ops->head_bwd_blocks(e->Hout, e->Wout), e->Cn_last, 1.0f / e->gs, e->grads + d.head_w, e->grads + d.head_b, sc};
+    if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS], st);
+    ORN_TRY(e->ops->wgrad_batch(nj, wj, st, pipe ? nullptr : &hf, l2job, 0));
+    if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 1], st);
+    OrnWgradReduce wr[ORN_MAX_LAYERS];
+    for (int i = ff; i < n_main; ++i) wr[i - ff] = wgrad_reduce(e, i, sc);
+    if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 2], st);
+    if (pipe && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));
+    ORN_TRY(e->ops->wgrad_reduce_all(n_main - ff, wr, st, w0job));
+    if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 3], st);
+    return 0;
+}
+
+// (ERB) merge backward of every layer of a set (closed forms): dW3 & dT, then dW2 & dW1, then the slices
+static int merge_backward(orn_engine *e, const orn_engine::MergeSet &ms, hipStream_t st, OrnScaleState *sc)
+{
+    if (e->d.precision != 0) {
+        ORN_TRY(orn_launch_merge_h16_bwd(ms.mh_tables, ms.mh_host, st, sc));
+    } else {
+        ORN_TRY(orn_launch_merge_group(ms.tables, 2, ms.tiles[2], st));
+        ORN_TRY(orn_launch_merge_group(ms.tables, 3, ms.tiles[3], st));
+    }
+    OrnMergeMisc mm[ORN_MAX_LAYERS];
+    for (int k = 0; k < ms.n; ++k) mm[k] = merge_misc(e, ms.layer[k]);
+    ORN_TRY(orn_launch_merge_bwd_tail_all(ms.n, mm, st));
+    return 0;
+}
+
+struct StepOpts {
+    int advance = 1;        // advance the device-side schedule by this many steps first (states e->cur[0 .. advance)); 0: not at all
+    int cur = 0;            // the step itself runs on e->cur[cur]
+    bool pipe = false;      // the pipelined form (struct orn_engine, `side`): the last block's weight-gradient chain leaves this step on the side stream
+    bool more = false;      // (pipelined form) another step follows in this call
+};
+
+// forward -> loss / head -> dgrad chain -> stem -> weight gradients -> merge backward -> Adam
+static int train_step(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                      int32_t *cursor, float *stats_out, int32_t n_slots, hipStream_t st, const StepOpts &o = StepOpts())
+{
+    const orn_engine_desc &d = e->d;
+    const bool pipe = o.pipe;
     float *P = e->params, *G = e->grads;
     const int Nout = d.fc_h * d.fc_w * d.fc_dim;
     const size_t HWo = (size_t)e->Hout * e->Wout;
-    OrnStepCur *cur = e->cur + cur_idx;
-    if (adv_count > 0) {
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, d.beta1, d.beta2, e->cur, adv_count, e->sc /* all entries */);
+    OrnStepCur *cur = e->cur + o.cur;
+    if (o.advance > 0) {
+        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, d.beta1, d.beta2, e->cur, o.advance, e->sc /* all entries */);
         ORN_LAUNCH_CHECK("advance");
     }
-    OrnScaleState *const sc = e->sc + cur_idx;          // this step's entry: its own flag, the shared scale
+    OrnScaleState *const sc = e->sc + o.cur;            // this step's entry: its own flag, the shared scale
     const int *fidx = &cur->frame;
     ORN_TRY(forward(e, embeds, fidx, true, st, (pipe && e->side_busy) ? 1 : 0));
     const int nl = d.n_layers, ff = e->ff;
@@ -789,7 +830,6 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
         for (int i = 0; i < nl; ++i) { wfs[i] = e->L[i].wf; wds[i] = e->L[i].wd32; Os[i] = d.layer[i].O; Cs[i] = d.layer[i].C; }
         ORN_TRY(orn_launch_flip_transpose_all(nl, wfs, wds, Os, Cs, st));
     }
-    if (pipe && side_fork_at(e) >= nl) ORN_TRY(side_branch_backward(e, st));
     for (int i = nl - 1; i >= 0; --i) {
         const orn_layer_desc &l = d.layer[i];
         LayerBuf &b = e->L[i];
@@ -818,7 +858,7 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
         ORN_TRY(orn_launch_conv_bwd_f32(x, b.wf, b.z, b.da, 1, l.C, l.O, l.H, l.W, l.s, dx, G + l.w3x3, G + l.b3x3, e->scratch, st,
                                         (i == nl - 1 && head_fused32) ? &hfuse : nullptr, ff >= nl ? b.wd32 : nullptr));
         if (e->prof) (void)hipEventRecord(e->prof_ev[2 * ORN_MAX_LAYERS + 2 * i + 1], st);
-        if (pipe && i == side_fork_at(e)) ORN_TRY(side_branch_backward(e, st));
+        if (pipe && e->fork_behind_dgrad && i == nl - 1) ORN_TRY(side_branch_backward(e, st));     // fork: behind the last block's dgrad
     }
     // stem backward; with a wgrad batch behind it, its last kernel (needed by Adam only) rides along that launch
     OrnStemW0Job w0job;
@@ -828,52 +868,15 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
                                 e->stage0 ? e->scratch + e->stem_ws : e->dh2, 1, d.embed_len, d.stem_dim, Nout, G + d.stem_w0,
                                 G + d.stem_b0, G + d.stem_w1, G + d.stem_b1, e->scratch, st,
                                 e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr));
-    if (ff < nl) {
-        // Weight gradients of every fast layer: nothing on the dgrad chain needs them, so they run here as ONE launch (the
-        // small layers' 72 / 216 / 360 work-groups pack behind the last block's 504 instead of leaving CUs idle one launch
-        // at a time: -37 us per 720p step), followed by ONE launch that reduces every layer's split-K slabs (-27 us).
-        OrnWgradJob wj[ORN_MAX_LAYERS];
-        int nj = 0;
-        const int n_main = pipe ? nl - 1 : nl;      // (pipelined step: the last block's is the side branch's)
-        for (int i = n_main - 1; i >= ff; --i) {    // largest first
-            if (pipe && i == nl - 2 && side_takes_below(e)) continue;      // (the side stream's)
-            const orn_layer_desc &l = d.layer[i];
-            wj[nj++] = OrnWgradJob{e->L[i].xpad, e->L[i].dypad, l.H, l.W, l.C, l.O, l.s, e->L[i].wslab, (i == nl - 1) ? last_smax(e) : (i == nl - 2 ? below_smax(e) : 0)};
-        }
-        const OrnHeadFinish hf = {e->head_ws, e->ops->head_bwd_blocks(e->Hout, e->Wout), e->Cn_last, 1.0f / e->gs, G + d.head_w, G + d.head_b, sc};
-        if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS], st);
-        ORN_TRY(e->ops->wgrad_batch(nj, wj, st, pipe ? nullptr : &hf, &l2job, 0));
-        if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 1], st);
-        OrnWgradReduce wr[ORN_MAX_LAYERS];
-        for (int i = ff; i < n_main; ++i) {
-            const orn_layer_desc &l = d.layer[i];
-            wr[i - ff] = OrnWgradReduce{e->L[i].wslab, l.H, l.W, l.C, l.O, l.s, 1.0f / e->gs, G + l.w3x3, G + l.b3x3, sc, (i == nl - 1) ? last_smax(e) : (i == nl - 2 ? below_smax(e) : 0)};
-        }
-        if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 2], st);
-        if (pipe && side_takes_below(e)) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));
-        ORN_TRY(e->ops->wgrad_reduce_all(n_main - ff, wr, st, &w0job));
-        if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 3], st);
-    }
-    if (pipe && side_fork_at(e) < 0) ORN_TRY(side_branch_backward(e, st));     // fork: the last block's wgrad .. merge backward, on the side stream
-    if (d.erb) {
-        // merge backward of every layer (closed forms): dW3 & dT, then dW2 & dW1, then the slices
-        const orn_engine::MergeSet &ms = e->mset[pipe ? 1 : 0];
-        if (d.precision != 0) {
-            ORN_TRY(orn_launch_merge_h16_bwd(ms.mh_tables, ms.mh_host, st, sc));
-        } else {
-            ORN_TRY(orn_launch_merge_group(ms.tables, 2, ms.tiles[2], st));
-            ORN_TRY(orn_launch_merge_group(ms.tables, 3, ms.tiles[3], st));
-        }
-        OrnMergeMisc mm[ORN_MAX_LAYERS];
-        for (int k = 0; k < ms.n; ++k) mm[k] = merge_misc(e, ms.layer[k]);
-        ORN_TRY(orn_launch_merge_bwd_tail_all(ms.n, mm, st));
-    }
+    if (ff < nl) ORN_TRY(fast_weight_grads(e, st, pipe, sc, &l2job, &w0job));
+    if (pipe && !e->fork_behind_dgrad) ORN_TRY(side_branch_backward(e, st));     // fork: behind the lower blocks' slab reduction
+    if (d.erb) ORN_TRY(merge_backward(e, e->mset[pipe ? 1 : 0], st, sc));
     if (pipe) {
         // this stream's Adam launch covers everything below the last block; its skip decision is mirrored for the side branch's launch
         // (into sc_side->mirrored: a word of its own, apart from the flag the side branch's detectors raise meanwhile)
         ORN_TRY(orn_launch_adam(P, G, e->m, e->v, e->side_lo, 0.0, 1, cur, d.beta1, d.beta2, d.eps, 1.0f, st, e->gmask, sc, e->sc, e->sc_side));
         ORN_HIP(hipEventRecord(e->ev_adam, st));
-        return side_branch_update(e, more);
+        return side_branch_update(e, o.more);
     }
     ORN_TRY(orn_launch_adam(P, G, e->m, e->v, (size_t)d.n_params, 0.0, 1, cur, d.beta1, d.beta2, d.eps, 1.0f, st, e->gmask, sc, e->sc));
     return 0;
@@ -898,7 +901,12 @@ extern "C" int orn_engine_train_steps(orn_engine *e, const float *frames, const 
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps: engine was created without grads / Adam arenas");
     hipStream_t st = (hipStream_t)stream;
     int rc = 0;
-    for (int k = 0; k < n_steps && rc == 0; ++k) rc = train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, st, 1, 0, e->pipe_ok, k + 1 < n_steps);
+    StepOpts o;
+    o.pipe = e->pipe_ok;
+    for (int k = 0; k < n_steps && rc == 0; ++k) {
+        o.more = k + 1 < n_steps;
+        rc = train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, st, o);
+    }
     if (e->side_busy) {
         const hipError_t hrc = hipStreamWaitEvent(st, e->ev_join, 0);
         e->side_busy = false;
@@ -957,10 +965,7 @@ extern "C" int orn_engine_train_steps_graph(orn_engine *e, const float *frames, 
     const bool same = e->graph_exec && e->g_frames == frames && e->g_embeds == embeds && e->g_sched == sched &&
                       e->g_cursor == cursor && e->g_stats == stats_out && e->g_slots == n_slots && e->g_stream == st;
     if (!same) {
-        if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
-        if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-        if (e->graph_exec_u) { (void)hipGraphExecDestroy(e->graph_exec_u); e->graph_exec_u = nullptr; }
-        if (e->graph_u) { (void)hipGraphDestroy(e->graph_u); e->graph_u = nullptr; }
+        drop_graphs(e);
         for (int pass = 0; pass < 2; ++pass) {
             const int reps = pass == 0 ? 1 : ORN_GRAPH_UNROLL;
             hipGraph_t *g = pass == 0 ? &e->graph : &e->graph_u;
@@ -968,7 +973,12 @@ extern "C" int orn_engine_train_steps_graph(orn_engine *e, const float *frames, 
             hipError_t rc = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
             if (rc != hipSuccess) { orn_set_error("graph: BeginCapture failed: %s", hipGetErrorString(rc)); return (int)rc; }
             int trc = 0;
-            for (int r = 0; r < reps && trc == 0; ++r) trc = train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, st, r == 0 ? reps : 0, r);
+            for (int r = 0; r < reps && trc == 0; ++r) {
+                StepOpts o;
+                o.advance = r == 0 ? reps : 0;      // the first step of the graph advances the schedule for all of them
+                o.cur = r;
+                trc = train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, st, o);
+            }
             rc = hipStreamEndCapture(st, g);
             if (trc != 0) { if (*g) { (void)hipGraphDestroy(*g); *g = nullptr; } return trc; }
             if (rc != hipSuccess) { orn_set_error("graph: EndCapture failed: %s", hipGetErrorString(rc)); return (int)rc; }
@@ -982,8 +992,7 @@ extern "C" int orn_engine_train_steps_graph(orn_engine *e, const float *frames, 
     // The host needs longer to launch the unrolled graph than the single-step one, and on an idle stream that launch is exposed (the
     // device waits for it): a call that will launch several graphs starts with ONE single step, and the unrolled launches queue up
     // behind it while it runs.  (20-step timed region after a synchronise: see DESIGN 6.)
-    static const bool first_single = orn_probe_env("ORN_GRAPH_NO_FIRST_SINGLE") == nullptr;
-    if (first_single && left > ORN_GRAPH_UNROLL) {
+    if (left > ORN_GRAPH_UNROLL) {
         hipError_t rc = hipGraphLaunch(e->graph_exec, st);
         if (rc != hipSuccess) { orn_set_error("graph: Launch failed: %s", hipGetErrorString(rc)); return (int)rc; }
         left -= 1;
