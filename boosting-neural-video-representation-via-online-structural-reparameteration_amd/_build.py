@@ -19,10 +19,17 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function', '-fvisibility=hidden', '-fno-slp-vectorize']
 # Per-file flags (none at present)
 FILE_FLAGS = {}
+# the 16-bit fast path is built for bf16 and, with -DORN_FP16, for IEEE half
+BUILT_TWICE = ('orn_conv_bf16.hip', 'orn_conv_fwd_bf16.hip', 'orn_conv2_bf16.hip', 'orn_wgrad_bf16.hip', 'orn_ops_bf16.hip')
 
 
 def _sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith('.hip'))
+
+
+def variants(src):
+    """(object-name suffix, extra flags) of every build of one source file"""
+    return [('', []), ('_f16', ['-DORN_FP16'])] if src in BUILT_TWICE else [('', [])]
 
 
 def _deps_mtime():
@@ -40,10 +47,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objs = []
     for src in _sources():
         s = os.path.join(CSRC, src)
-        variants = [('', [])]
-        if src in ('orn_conv_bf16.hip', 'orn_conv_fwd_bf16.hip', 'orn_conv2_bf16.hip'):   # the 16-bit fast path is built for bf16 and for IEEE half
-            variants.append(('_f16', ['-DORN_FP16']))
-        for suffix, extra in variants:
+        for suffix, extra in variants(src):
             o = os.path.join(OBJ, src[:-4] + suffix + '.o')
             objs.append(o)
             if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hm):

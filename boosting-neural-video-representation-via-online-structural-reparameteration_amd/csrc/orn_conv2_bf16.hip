@@ -23,36 +23,7 @@
 //   constants and a tap is one basic block (a runtime branch inside it cost 50 us per launch: the scheduler no longer
 //   interleaves the next reads with the MFMAs).
 // Compiled twice like its siblings: as is (bf16, namespace orn_bf16) and with -DORN_FP16 (IEEE half, namespace orn_f16).
-#include "orn_internal.h"
-#include <type_traits>
-#ifdef ORN_FP16
-#define HNS orn_f16
-typedef _Float16 h16;
-#define MFMA16_H16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-#define MFMA_H16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#else
-#define HNS orn_bf16
-typedef __bf16 h16;
-#define MFMA16_H16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-#define MFMA_H16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#endif
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define PDBG(p_) 0
-typedef __attribute__((ext_vector_type(8))) h16 h16x8;
-typedef __attribute__((ext_vector_type(2))) h16 h16x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-// compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N)
-template <int I, int N, class F>
-__device__ __forceinline__ void c2_sfor(F &&f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        c2_sfor<I + 1, N>(f);
-    }
-}
+#include "orn_h16.h"
 
 namespace HNS {
 
@@ -96,36 +67,6 @@ struct Conv2P {
     float *head_out;                // fp32 [3][H*s][W*s], or null: no head
     int head_sigmoid;
 };
-
-__device__ __forceinline__ int c2_div(int x, unsigned m) { return m ? (int)__umulhi((unsigned)x, m) : x; }
-// m with x / d == umulhi(x, m) for every 0 <= x < 2^16 and 2 <= d < 2^16; d == 1 is encoded as m = 0
-static unsigned c2_magic(int d)
-{
-    return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned long long)d - 1) / (unsigned long long)d);
-}
-// v_permlane16_swap: odd 16-lane rows of `a` <-> even rows of `b`.  Afterwards rows 0 / 2 hold (own a, the next row's a) and
-// rows 1 / 3 hold (the previous row's b, own b) -- checked on hardware with tools/probes (row = lane >> 4).
-// (keep the operands named lvalues: with bit_cast temporaries as arguments hipcc 7.2 returned a wrong second half)
-__device__ __forceinline__ void c2_swap_rows(unsigned &a, unsigned &b)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-__device__ __forceinline__ void c2_swap_rows_f(float &a, float &b)
-{
-    unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
-    c2_swap_rows(ua, ub);
-    a = __builtin_bit_cast(float, ua);
-    b = __builtin_bit_cast(float, ub);
-}
-__device__ __forceinline__ unsigned c2_pack(float lo, float hi)
-{
-    h16x2 v;
-    v[0] = (h16)lo;
-    v[1] = (h16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // Fragment reads of step (tap TAP) into set SET: 4 pixel sub-blocks (rows 2w + {0,1} + ti, two 16-pixel halves) and 6 channel
 // sub-blocks.  LDS rows are 64 B = 4 chunks of 16 B; logical chunk c of row R sits at position c ^ ((R >> 1) & 3) (conflict-free
@@ -276,7 +217,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
 
     // prologue: patch of chunk 0, weight tiles 0..R-2, rendezvous; tile R-1 stays in flight behind it
     const h16 *w_cur = p.w + (size_t)seg0 * 96 * p.wrow;
-    c2_sfor<0, 6>([&](auto k_c) __attribute__((always_inline)) { C2_DMA_PATCH_PIECE(0, 0, decltype(k_c)::value) });
+    orn_sfor<0, 6>([&](auto k_c) __attribute__((always_inline)) { C2_DMA_PATCH_PIECE(0, 0, decltype(k_c)::value) });
 #pragma unroll
     for (int u0 = 0; u0 < C2_NSLOT - 1; ++u0) C2_DMA_TILE_AT(w_cur, u0, u0)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -299,7 +240,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
 #pragma unroll
             for (int j = 0; j < 6; ++j) fb[0][j] = fb[1][j];
         }
-        c2_sfor<0, 9>([&](auto tap_c) __attribute__((always_inline)) {
+        orn_sfor<0, 9>([&](auto tap_c) __attribute__((always_inline)) {
             constexpr int tap = decltype(tap_c)::value;
             constexpr int cur = tap & 1, nxt = cur ^ 1;
             // fragment reads of step u + 1 (its tile is known to have landed since rendezvous u - 1); the reads issued by the
@@ -343,8 +284,8 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
             const int c8 = n0 + j * 32 + c8_lane;
             const float4 ba = *reinterpret_cast<const float4 *>(sbias + j * 32 + c8_lane);
             const float4 bb = *reinterpret_cast<const float4 *>(sbias + j * 32 + c8_lane + 4);
-            const int ij = c2_div(c8, p.mCn), n = c8 - ij * p.Cn;
-            const int si = c2_div(ij, p.mS), sj = ij - si * p.s;
+            const int ij = conv_div(c8, p.mCn), n = c8 - ij * p.Cn;
+            const int si = conv_div(ij, p.mS), sj = ij - si * p.s;
             float hw[3][8];
             if (EPI == C2_FWD_LAST && head) {
 #pragma unroll
@@ -364,18 +305,18 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float x0 = ta[e], x1 = tb[e];
-                    c2_swap_rows_f(x0, x1);
+                    swap_rows_f(x0, x1);
                     v[e] = x0; v[4 + e] = x1;
                 }
                 v[0] += ba.x; v[1] += ba.y; v[2] += ba.z; v[3] += ba.w;
                 v[4] += bb.x; v[5] += bb.y; v[6] += bb.z; v[7] += bb.w;
                 const int Ws = W * p.s, oh = gh * p.s + si, ow = gw * p.s + sj;
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{c2_pack(v[0], v[1]), c2_pack(v[2], v[3]), c2_pack(v[4], v[5]), c2_pack(v[6], v[7])}, z_rsrc,
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack_h16x2(v[0], v[1]), pack_h16x2(v[2], v[3]), pack_h16x2(v[4], v[5]), pack_h16x2(v[6], v[7])}, z_rsrc,
                                                        ok ? ((oh * Ws + ow) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);   // < 2^31 bytes: launcher
                 if (EPI == C2_FWD) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = orn_silu(v[e]);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{c2_pack(v[0], v[1]), c2_pack(v[2], v[3]), c2_pack(v[4], v[5]), c2_pack(v[6], v[7])}, a_rsrc,
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack_h16x2(v[0], v[1]), pack_h16x2(v[2], v[3]), pack_h16x2(v[4], v[5]), pack_h16x2(v[6], v[7])}, a_rsrc,
                                                            ok ? (((oh + 1) * (Ws + 2) + (ow + 1)) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);
                 }
                 if (EPI == C2_FWD_LAST && head) {
@@ -392,7 +333,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
         }
         if (EPI == C2_FWD_LAST && head) {
             // the four lanes l15 + 16 g of a pixel hold 24 channels each: sum them, lane g < 3 stores output channel g
-            const int ij = c2_div(n0, p.mCn), si = c2_div(ij, p.mS), sj = ij - si * p.s;
+            const int ij = conv_div(n0, p.mCn), si = conv_div(ij, p.mS), sj = ij - si * p.s;
             const size_t HWs = (size_t)(H * p.s) * (W * p.s);
 #pragma unroll
             for (int pi = 0; pi < 4; ++pi) {
@@ -419,7 +360,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
         for (int pi = 0; pi < 4; ++pi) {
             const int gh = h0 + 2 * uwave + (pi >> 1), gw = w0 + 16 * (pi & 1) + l15;
             const bool ok = (gh < H) && (gw < W);
-            const int sp = p.sp, ph = c2_div(gh, p.mSp), pw = c2_div(gw, p.mSp);
+            const int sp = p.sp, ph = conv_div(gh, p.mSp), pw = conv_div(gw, p.mSp);
             const int sub = (gh - ph * sp) * sp + (gw - pw * sp);
             h16x8 zz[3];
 #pragma unroll
@@ -433,7 +374,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float x0 = ta[e], x1 = tb[e];
-                    c2_swap_rows_f(x0, x1);
+                    swap_rows_f(x0, x1);
                     v[e] = x0; v[4 + e] = x1;
                 }
                 if (ok) {
@@ -484,7 +425,7 @@ int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, cons
     p.wrow = O; p.wtap = 96 * O * 2;                      // (wtap in BYTES)
     p.qseg = O / C2_CK;
     p.tiles_w = orn_cdiv(W, C2_TW); p.tiles_h = orn_cdiv(H, C2_TH); p.ptiles = p.tiles_w * p.tiles_h; p.nsplit = 1;
-    p.zprev = zprev; p.dyprev = dyprev; p.sp = sp; p.mSp = c2_magic(sp);
+    p.zprev = zprev; p.dyprev = dyprev; p.sp = sp; p.mSp = conv_magic(sp);
     return c2_launch<C2_DGRAD>(p, p.ptiles, C2_LDS, st, "dgrad2_nhwc");
 }
 
@@ -506,7 +447,7 @@ int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, 
     p.bias = bias_p; p.z = z; p.apad = apad; p.s = s; p.Cn = O / (s * s); p.Nout = O;
     p.z_bytes = (unsigned)((size_t)(H * s) * (W * s) * p.Cn * 2);
     p.apad_bytes = apad ? (unsigned)((size_t)(H * s + 2) * (W * s + 2) * p.Cn * 2) : 0;
-    p.mCn = c2_magic(p.Cn); p.mS = c2_magic(s);
+    p.mCn = conv_magic(p.Cn); p.mS = conv_magic(s);
     // The head in this epilogue is correct (tests run it with ORN_HEAD_FUSED=1) but does not pay: 96 SiLUs + 288 FMAs per lane on
     // the vector pipe cost the last block 145 -> 190 us, the 42 us HBM-bound head kernel it replaces included -- and the denser
     // launch drags the clock of its neighbours down (720p step 1.168 -> 1.188 ms on one box).  Off unless asked for.

@@ -5,103 +5,15 @@
 // v_mfma_f32_16x16x32 (higher clock under load), this kernel loses 12 % with it (measured both ways on the 720p shapes), so
 // the two directions keep separate kernels -- different lane maps, LDS swizzles and epilogues -- in separate files.
 // Compiled twice like its sibling: as is (bf16, namespace orn_bf16) and with -DORN_FP16 (IEEE half, namespace orn_f16).
-#include "orn_internal.h"
-#include <type_traits>
-#ifdef ORN_FP16
-#define HNS orn_f16
-typedef _Float16 h16;
-#define MFMA_H16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#else
-#define HNS orn_bf16
-typedef __bf16 h16;
-#define MFMA_H16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#endif
-typedef __attribute__((ext_vector_type(8))) h16 h16x8;
-typedef __attribute__((ext_vector_type(4))) h16 h16x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-// compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N)
-template <int I, int N, class F>
-__device__ __forceinline__ void orn_sfor_f(F &&f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        orn_sfor_f<I + 1, N>(f);
-    }
-}
+#include "orn_h16.h"
 
 namespace HNS {
 
-// The timing-ablation flags cost registers and branches in the hot loops: they are compiled in only with
-// -DORN_CONV_ABLATE (tools/probes builds); product builds see a constant 0.
-#ifdef ORN_CONV_ABLATE
-#define PDBG(p_) ((p_).dbg)
-#else
-#define PDBG(p_) 0
-#endif
 static int g_convf_dbg = 0;   // timing experiments only (tools/probes), see orn_debug_set
-// Phase stamps (diagnostic build -DORN_CONV_STAMP; the product build compiles none of it): wave 0 of every work-group writes
-// s_memtime at the N-tile phase boundaries into a buffer no other code reads.
 #ifdef ORN_CONV_STAMP
 static unsigned long long *g_convf_stamps = nullptr;
-// stamps collect in 512 B of LDS behind the kernel's own images (a global store per stamp would sit in every vmcnt wait)
-#define STAMP_LDS ((unsigned long long *)(smem + PATCH_LDS + NBUF * BS_BYTES + (EPI_IS_FWD(EPI) ? ((((p.Nout + BN - 1) / BN * BN) * 4 + 255) & ~255) : 0)))
-#define STAMP(i_) { if (p.stamps && t == 0) STAMP_LDS[i_] = __builtin_amdgcn_s_memtime(); }
-#define STAMP_RT(i_) { if (p.stamps && t == 0) STAMP_LDS[i_] = __builtin_amdgcn_s_memrealtime(); }
-#define STAMP_FLUSH() { if (p.stamps && t < 128) p.stamps[(size_t)(blockIdx.x + blockIdx.y * gridDim.x) * 128 + t] = STAMP_LDS[t]; }
-// per-tap stamps of wave 0 (slots 16..) and of the wave that shares its SIMD (slots 64..): up to 4 N tiles / chunks x 9 taps
-#define STAMP_TAP(seg_, tap_) { if (p.stamps && (seg_) < 4 && lane == 0 && (wave == 0 || wave == NWAVES / 2)) STAMP_LDS[(wave == 0 ? 16 : 64) + (seg_) * 9 + (tap_)] = __builtin_amdgcn_s_memtime(); }
-// rendezvous of taps 3..5 of segment 0: arrival (k 0), after the vmcnt wait (1), after the barrier (2); wave 0 -> slots 100.., partner -> 112..
-#define STAMP_BAR(seg_, tap_, k_) { if (p.stamps && (seg_) == 0 && (tap_) >= 3 && (tap_) <= 5 && lane == 0 && (wave == 0 || wave == NWAVES / 2)) STAMP_LDS[(wave == 0 ? 100 : 112) + ((tap_) - 3) * 3 + (k_)] = __builtin_amdgcn_s_memtime(); }
-#else
-#define STAMP(i_)
-#define STAMP_RT(i_)
-#define STAMP_FLUSH()
-#define STAMP_TAP(seg_, tap_)
-#define STAMP_BAR(seg_, tap_, k_)
+#define STAMP_LDS_OFF ((((p.Nout + BN - 1) / BN * BN) * 4 + 255) & ~255)   // behind the bias copy
 #endif
-
-#define CB_TH 8
-#define CB_TW 32
-#define CB_PH (CB_TH + 2)
-#define CB_PW (CB_TW + 2)
-#define CB_CK 96                 // channels per K chunk
-#define CB_PIXB 208              // LDS bytes per patch pixel (192 data + 16 pad: conflict-free b128 reads)
-#define CB_PATCH_BYTES (CB_PH * CB_PW * CB_PIXB)
-#define CB_ROWB 208              // LDS bytes per weight-tile row
-
-// EPI_B_FWD_LAST: the forward of the last block (no activation copy for a next layer): its own instantiation, so the
-// largest launch of the step carries neither the second set of deferred-store registers nor the SiLU code
-enum { EPI_B_FWD = 0, EPI_B_DGRAD = 1, EPI_B_DGRAD_F32 = 2, EPI_B_FWD_LAST = 3 };
-#define EPI_IS_FWD(e_) ((e_) == EPI_B_FWD || (e_) == EPI_B_FWD_LAST)
-
-typedef __attribute__((ext_vector_type(2))) h16 h16x2;
-__device__ __forceinline__ unsigned packf_h16x2(float lo, float hi)
-{
-    h16x2 v;
-    v[0] = (h16)lo;
-    v[1] = (h16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-// v_permlane32_swap: lanes 32-63 of `a` <-> lanes 0-31 of `b` (guide T21).  After the call lanes < 32
-// hold (own a, upper half's a) and lanes >= 32 hold (lower half's b, own b).
-__device__ __forceinline__ void swapf_halves(unsigned &a, unsigned &b)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-__device__ __forceinline__ void swapf_halves_f(float &a, float &b)
-{
-    unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
-    swapf_halves(ua, ub);
-    a = __builtin_bit_cast(float, ua);
-    b = __builtin_bit_cast(float, ub);
-}
-
-__device__ __forceinline__ int convf_div(int x, unsigned m) { return m ? (int)__umulhi((unsigned)x, m) : x; }
 
 struct ConvFP {
     const h16 *xpad;     // [H+2][W+2][Cin]
@@ -110,32 +22,15 @@ struct ConvFP {
     int H, W, Cin, Nout;
     int tiles_w, tiles_h, n_tiles_per_wg;
     int n_full;          // work-groups [0, n_full) own whole pixel tiles; the rest own one N tile each
-    int qsplit;          // EPI_B_DGRAD_F32 on small images: blockIdx.y = input chunk, one fp32 partial slab per chunk
-    // EPI_B_FWD
     h16 *z;              // [H*s][W*s][Cn]
     h16 *apad;           // [H*s+2][W*s+2][Cn] or null
     int s, Cn;
     unsigned z_bytes, apad_bytes;   // sizes of the two buffers (raw-buffer bounds)
-    // EPI_B_DGRAD: out = dx * silu'(zprev) scattered into the previous layer's dypad
-    const h16 *zprev;    // [H][W][Nout]
-    h16 *dyprev;         // [H/sp+2][W/sp+2][Nout*sp*sp]
-    int sp;
-    // EPI_B_DGRAD_F32
-    float *dx_f32;       // [H][W][Nout]
-    // exact division by multiply-high for the epilogues' index math (a runtime integer division costs ~30 instructions,
-    // and 16 of them per N tile per lane were a measurable part of the forward kernel): convf_div / convf_magic
-    unsigned mCn, mS, mSp;
+    unsigned mCn, mS;    // conv_magic of Cn and s for the epilogue's index math (conv_div)
     int dbg;             // timing-only ablation flags (tools/probes): 1 no weight restage, 2 no patch stage, 4 no stores
     unsigned long long *stamps;   // -DORN_CONV_STAMP diagnostic builds only: 64 time stamps per work-group (tools/probes/conv_stamps.py)
 };
 
-// Fragment register sets: reads run CONV_NSET - 1 k-steps ahead of the MFMAs that consume them
-#ifndef CONVF_NSET
-#define CONVF_NSET 2
-#endif
-#ifndef CONVF_NSET_UNUSED
-#define CONVF_NSET_UNUSED 2
-#endif
 // Fragment reads of k-step (TAP, KS_) into register set SET: MB patch rows (the MFMA's B operand: pixels) and NB weight
 // blocks (A operand: output channels).  a_lane = LDS byte address of this lane's patch pixel for (row wm*MB, tap 0),
 // pix_lane = that pixel's index (for the swizzle), b_par0 = this lane's weight-row address for k-step parity 0.
@@ -180,15 +75,14 @@ __device__ __forceinline__ void convf_wait_set(h16x8 (&fa)[NSET][MB], h16x8 (&fb
 // (the zero-padded narrow layer, forward only): its whole K = 9 x 32 fits LDS -- patch 22 KB + all nine [BN][32] weight
 // tiles 72 KB -- so an N tile is ONE rendezvous and 72 back-to-back MFMAs per wave instead of nine rounds of barrier +
 // counted wait + 24 MFMAs of which two thirds multiply zeros.  Rows are 64 B: 4 chunks, XOR swizzle (chunk ^ ((row >> 2) & 3)).
-// ALLTAPS: all nine weight tiles of the (single) K chunk resident, one rendezvous per N tile -- the narrow form, and the
-// chunk-split dgrad of a layer with <= 32 real OUTPUT channels (N tile 32: 9 x 6 KB next to the 64 KB patch).
+// ALLTAPS: all nine weight tiles of the (single) K chunk resident, one rendezvous per N tile -- the narrow form.
 template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK)>
 __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(ConvFP p)
 {
     ORN_PRIO_HIGH();
     static_assert(EPI_IS_FWD(EPI), "this file holds the forward kernel only (dgrad: orn_conv_bf16.hip)");
     constexpr bool NARROW = (CK != CB_CK);
-    static_assert(CK == CB_CK || (CK == 32 && EPI_IS_FWD(EPI)), "narrow form: 32 channels, forward only");
+    static_assert(CK == CB_CK || CK == 32, "narrow form: 32 channels");
     constexpr int NCH = CK / 8;                        // 16-byte chunks per LDS row
     static_assert(!NARROW || ALLTAPS, "the narrow form keeps all taps resident");
     constexpr int NBUF = ALLTAPS ? 9 : 3;              // weight tiles resident at once
@@ -196,8 +90,8 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
     constexpr int BN = WAVES_N * NB * 32;
     static_assert(WAVES_M * MB == CB_TH, "M tile must be 8 rows of 32 pixels");
     // LDS images: UNPADDED 192-byte rows (12 x 16-byte chunks) filled by LDS-DMA (global_load_lds_dwordx4: 1 KiB per
-    // wave-instruction, lane-linear destination, no VGPRs, no ds_write).  Conflict-free ds_read_b128 comes from a
-    // rotation swizzle -- logical chunk c of row R sits at position (c + ((R >> 2) & 3)) % 12 -- applied on the DMA's
+    // wave-instruction, lane-linear destination, no VGPRs, no ds_write).  Conflict-free ds_read_b128 comes from an
+    // XOR swizzle -- logical chunk c of row R sits at position c ^ ((R >> 2) & 3) -- applied on the DMA's
     // per-lane SOURCE address and on the fragment reads (both sides or neither: guide rule 21).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NWAVES = WAVES_M * WAVES_N;
@@ -210,11 +104,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
     // LDS-DMA instruction parks its wave for ~100 cycles, and when both waves of a SIMD issue theirs right after the
     // rendezvous the matrix pipe idles for all of them (~300 cycles per tap, measured with phase stamps); with one loader
     // per SIMD its partner's MFMAs run meanwhile, and the loader catches up while the partner waits at the next rendezvous.
-#ifdef ORN_DGRAD_ALL_LOAD
-    constexpr int NLOAD = (ALLTAPS || NWAVES < 8 || !EPI_IS_FWD(EPI)) ? NWAVES : NWAVES / 2;
-#else
     constexpr int NLOAD = (ALLTAPS || NWAVES < 8) ? NWAVES : NWAVES / 2;
-#endif
     constexpr int B_PER_WAVE = (B_INSTR + NLOAD - 1) / NLOAD;
     constexpr int P_PER_WAVE = (PATCH_INSTR + NWAVES - 1) / NWAVES;
     static_assert((NARROW || PATCH_INSTR % NWAVES == 0) && BS_BYTES % 1024 == 0, "tile geometry");
@@ -236,9 +126,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
     const int tw = tile % p.tiles_w, th = tile / p.tiles_w;
     const int h0 = th * CB_TH, w0 = tw * CB_TW;
     const int H = p.H, W = p.W, Cin = p.Cin;
-    const int q_base = (EPI == EPI_B_DGRAD_F32 && p.qsplit) ? (int)blockIdx.y : 0;   // chunk split: this WG's chunk
-    const int Q = (ALLTAPS || (EPI == EPI_B_DGRAD_F32 && p.qsplit)) ? 1 : Cin / CB_CK;   // ALLTAPS dgrad: launched chunk-split
-    if (EPI == EPI_B_DGRAD_F32 && p.qsplit) nt0 = 0;
+    const int Q = ALLTAPS ? 1 : Cin / CB_CK;           // chunks of the input channels
     const int n_tiles = Q * 9;                         // weight tiles per N tile
 
     const int uwave = __builtin_amdgcn_readfirstlane(wave);        // provably wave-uniform (LDS-DMA base -> M0)
@@ -269,7 +157,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
 #define DMA_B(buf_, nt_, q_, tap_)                                                                              \
     {                                                                                                           \
         if (NLOAD == NWAVES || uwave < NLOAD) {                                                                 \
-            const h16 *wbase = p.w + ((size_t)((tap_) * p.Nout + (nt_) * BN) * Cin + ((q_) + q_base) * CK);     \
+            const h16 *wbase = p.w + ((size_t)((tap_) * p.Nout + (nt_) * BN) * Cin + (q_) * CK);     \
             _Pragma("unroll") for (int k = 0; k < B_PER_WAVE; ++k)                                              \
                 DMA16(wbase + b_goff[k], PATCH_LDS + (buf_) * BS_BYTES + ((uwave + NLOAD * k) % B_INSTR) * 1024); \
         }                                                                                                       \
@@ -278,7 +166,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
     {                                                                                                           \
         _Pragma("unroll") for (int k = 0; k < P_PER_WAVE; ++k)                                                  \
             if (!NARROW || uwave + NWAVES * k < PATCH_INSTR)                                                    \
-                DMA16(p.xpad + p_goff[k] + (p_ok[k] ? ((q_) + q_base) * CK : 0), (uwave + NWAVES * k) * 1024);  \
+                DMA16(p.xpad + p_goff[k] + (p_ok[k] ? (q_) * CK : 0), (uwave + NWAVES * k) * 1024);  \
     }
 #define WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(" #n_ ")" ::: "memory")
 #define WAIT_VMC(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
@@ -292,25 +180,21 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
     const unsigned b_par0 = lds0 + PATCH_LDS + (wn * NB * 32 + l31) * ROWB + 16 * (hh ^ b_rot);   // weight rows, parity 0
     const unsigned a_lane = lds0 + (wm * MB * CB_PW + l31) * ROWB;                               // patch pixel of (row wm*MB, tap 0)
 
-    // EPI_B_FWD*: the packed outputs of an N tile are stored by its epilogue as RAW BUFFER stores that every lane issues
+    // The packed outputs of an N tile are stored by its epilogue as RAW BUFFER stores that every lane issues
     // (out-of-image lanes carry an out-of-range offset and are dropped by the bounds check): the number of vector-memory
     // operations behind the last DMA is then known, and the next rendezvous' wait steps over them (vmcnt(n) = all but the n
     // newest) instead of stalling on HBM write latency.
     constexpr bool APAD = (EPI == EPI_B_FWD);          // also writes a = SiLU(z) into the next layer's padded input
-    constexpr int NST = EPI_IS_FWD(EPI) ? MB * NB * 2 * (APAD ? 2 : 1) : 0;   // stores per wave and N tile
+    constexpr int NST = MB * NB * 2 * (APAD ? 2 : 1);  // stores per wave and N tile
     bool pending = false;                              // epilogue stores were issued after this wave's last DMA wait
     // z / apad as raw buffers: byte offsets; 0x80000000 (out of range for any buffer the launcher admits) drops the lane's store
-    const auto z_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.z, 0, EPI_IS_FWD(EPI) ? p.z_bytes : 0, 0x00020000);
+    const auto z_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.z, 0, p.z_bytes, 0x00020000);
     const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.apad, 0, APAD ? p.apad_bytes : 0, 0x00020000);
-    float *sbias = reinterpret_cast<float *>(smem + PATCH_LDS + NBUF * BS_BYTES);     // [Nout] after the weight ring (EPI_B_FWD)
-    if (EPI_IS_FWD(EPI))
-        for (int i = t; i < (p.Nout + BN - 1) / BN * BN; i += NT)                    // visible after the first N tile's barriers
-            sbias[i] = (p.bias && i < p.Nout) ? p.bias[i] : 0.f;                    // (zeros behind Nout: a ragged last N tile)
-#ifdef ORN_CONV_PRIO
-    if (NLOAD != NWAVES && uwave >= NLOAD) __builtin_amdgcn_s_setprio(1);   // experiment: static priority for the non-loader half
-#endif
+    float *sbias = reinterpret_cast<float *>(smem + PATCH_LDS + NBUF * BS_BYTES);     // [Nout] after the weight ring
+    for (int i = t; i < (p.Nout + BN - 1) / BN * BN; i += NT)                        // visible after the first N tile's barriers
+        sbias[i] = (p.bias && i < p.Nout) ? p.bias[i] : 0.f;                        // (zeros behind Nout: a ragged last N tile)
     STAMP_RT(0)
-    constexpr int NSET = EPI_IS_FWD(EPI) ? CONVF_NSET : CONVF_NSET_UNUSED, LEAD = NSET - 1;   // reads run LEAD k-steps ahead of their MFMAs
+    constexpr int NSET = 2, LEAD = NSET - 1;            // fragment register sets: reads run LEAD k-steps ahead of their MFMAs
     h16x8 fa[NSET][MB], fb[NSET][NB];                   // fragment register sets (carried across N tiles by the pipeline)
     for (int nti = 0; nti < nt_cnt; ++nti) {
         const int nt = nt0 + nti;
@@ -348,23 +232,23 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
         // issues the fragment reads of step s+LEAD into another register set, waits with a COUNTED lgkmcnt for its own
         // (issued LEAD steps earlier), then runs its MFMAs -- also across a tap boundary, so the rendezvous at the end of a tap
         // sits between MFMAs whose operands are already in registers or in flight.  (LEAD = 2 measured the same as 1 on the
-        // 720p shapes: CONV_NSET_* keep the knob.)  Reading tile t+1 before rendezvous t is legal because every wave waits for
+        // 720p shapes.)  Reading tile t+1 before rendezvous t is legal because every wave waits for
         // ALL its outstanding DMA pieces (tile t+2 included) before rendezvous t: tile t+1 was complete, and known to be, at
         // rendezvous t-1.  Ring: after rendezvous t the DMA of tile t+3 overwrites tile t.
         constexpr int KS = CK / 16, NR = MB + NB, NSTEP = 9 * KS;
-        static_assert(NSTEP % NSET == 0 && KS >= LEAD, "the register-set rotation must repeat per chunk");
+        static_assert(NSET == 2 && LEAD == 1 && NSTEP % NSET == 0, "two register sets, reads one k-step ahead; the rotation repeats per chunk");
 #define READ_STEP(set_, tap_, ks_) convf_read_step<NSET, MB, NB, ROWB, BS_BYTES, ALLTAPS, set_, tap_, ks_>(fa, fb, a_lane, wm * MB * CB_PW + l31, b_par0, hh)
         STAMP(3 + nti * 4)
-        if (ALLTAPS || nti == 0) { READ_STEP(0, 0, 0); if constexpr (LEAD > 1) READ_STEP(1 % NSET, 0, 1); }   // later N tiles: issued by the previous N tile's last steps
+        if (ALLTAPS || nti == 0) READ_STEP(0, 0, 0);                       // later N tiles: issued by the previous N tile's last step
         for (int q = 0; q < Q; ++q) {
             const bool last_chunk = (q + 1 >= Q);
             const bool more_segs = !last_chunk || has_next_nt;             // another (N tile, chunk) segment follows in the stream
             const int qn = last_chunk ? 0 : q + 1, ntn = last_chunk ? nt + 1 : nt;
             const bool carry = !ALLTAPS && (Q == 1) && has_next_nt;        // same patch next: the pipeline runs on into the next N tile
-            orn_sfor_f<0, 9>([&](auto tap_c) __attribute__((always_inline)) {
+            orn_sfor<0, 9>([&](auto tap_c) __attribute__((always_inline)) {
                 constexpr int tap = decltype(tap_c)::value;
                 constexpr int buf = ALLTAPS ? tap : tap % 3;
-                orn_sfor_f<0, KS>([&](auto ks_c) __attribute__((always_inline)) {
+                orn_sfor<0, KS>([&](auto ks_c) __attribute__((always_inline)) {
                     constexpr int ks = decltype(ks_c)::value;
                     constexpr int g = tap * KS + ks, cur = g % NSET, nxt = (g + LEAD) % NSET;
                     constexpr int g2 = g + LEAD;                           // the step whose reads are issued now
@@ -384,7 +268,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
                 STAMP_TAP(nti * Q + q, tap)
                 if (!ALLTAPS && ((tap < 8) || more_segs)) {
                     // stream per wave: .. DMA (tap 8) [epilogue: NST stores] | tap 0: wait for that DMA only, DMA | tap 1: wait all ..
-                    if constexpr (EPI_IS_FWD(EPI) && tap == 0) {
+                    if constexpr (tap == 0) {
                         if (pending) WAIT_VMC(NST); else WAIT_VM(0);
                         pending = false;
                     } else {
@@ -406,13 +290,13 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
                         else if (more_segs) DMA_B(buf, ntn, qn, tap - 6)
                     }
                     if constexpr (tap == 8) {
-                        if (Q > 1) { READ_STEP(0, 0, 0); if constexpr (LEAD > 1) READ_STEP(1 % NSET, 0, 1); }
+                        if (Q > 1) READ_STEP(0, 0, 0);
                     }
                 }
             });
         }
         // a carried-over prefetch lands before the epilogue's code runs (the compiler may move those registers there)
-        if (!ALLTAPS && (Q == 1) && has_next_nt) { convf_wait_set<NSET, MB, NB, 0, (LEAD - 1) * NR>(fa, fb); if constexpr (LEAD > 1) convf_wait_set<NSET, MB, NB, 1 % NSET, 0>(fa, fb); }
+        if (!ALLTAPS && (Q == 1) && has_next_nt) convf_wait_set<NSET, MB, NB, 0, 0>(fa, fb);
 #undef READ_STEP
         STAMP(4 + nti * 4)
 
@@ -431,39 +315,37 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
 #pragma unroll
                 for (int k = 0; k < 4; k += 2) {
                     const int c8 = cb + 8 * (k + hh);                   // the 8 channels this lane stores
-                    if (EPI_IS_FWD(EPI)) {
-                        float va[4], vb[4];
-                        // bias from its LDS copy (a global load here would expose its latency once per N tile)
-                        const float4 ba = *reinterpret_cast<const float4 *>(sbias + cb + 8 * k + 4 * hh);
-                        const float4 bb = *reinterpret_cast<const float4 *>(sbias + cb + 8 * (k + 1) + 4 * hh);
-                        va[0] = acc[i][j][4 * k + 0] + ba.x; va[1] = acc[i][j][4 * k + 1] + ba.y;
-                        va[2] = acc[i][j][4 * k + 2] + ba.z; va[3] = acc[i][j][4 * k + 3] + ba.w;
-                        vb[0] = acc[i][j][4 * k + 4] + bb.x; vb[1] = acc[i][j][4 * k + 5] + bb.y;
-                        vb[2] = acc[i][j][4 * k + 6] + bb.z; vb[3] = acc[i][j][4 * k + 7] + bb.w;
-                        unsigned za0 = packf_h16x2(va[0], va[1]), za1 = packf_h16x2(va[2], va[3]);
-                        unsigned zb0 = packf_h16x2(vb[0], vb[1]), zb1 = packf_h16x2(vb[2], vb[3]);
-                        swapf_halves(za0, zb0); swapf_halves(za1, zb1);
-                        const int ij = convf_div(c8, p.mCn), n = c8 - ij * p.Cn;
-                        const int si = convf_div(ij, p.mS), sj = ij - si * p.s;
-                        const int Ws = W * p.s, oh = gh * p.s + si, ow = gw * p.s + sj;
-                        // (a ragged last N tile -- Nout not a multiple of the N tile -- computes its missing 32-channel blocks
-                        // on whatever weight rows follow in memory and drops them here)
-                        const bool okc = ok && c8 < p.Nout;
-                        __builtin_amdgcn_raw_buffer_store_b128(u32x4{za0, za1, zb0, zb1}, z_rsrc,
-                                                               okc ? ((oh * Ws + ow) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);   // < 2^31 bytes: launcher
-                        if (APAD) {
-                            unsigned aa0 = packf_h16x2(orn_silu(va[0]), orn_silu(va[1])), aa1 = packf_h16x2(orn_silu(va[2]), orn_silu(va[3]));
-                            unsigned ab0 = packf_h16x2(orn_silu(vb[0]), orn_silu(vb[1])), ab1 = packf_h16x2(orn_silu(vb[2]), orn_silu(vb[3]));
-                            swapf_halves(aa0, ab0); swapf_halves(aa1, ab1);
-                            // the activation copy leaves right away (the next vmcnt wait is a whole tap of the next N tile away)
-                            __builtin_amdgcn_raw_buffer_store_b128(u32x4{aa0, aa1, ab0, ab1}, a_rsrc,
-                                                                   okc ? (((oh + 1) * (Ws + 2) + (ow + 1)) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);
-                        }
+                    float va[4], vb[4];
+                    // bias from its LDS copy (a global load here would expose its latency once per N tile)
+                    const float4 ba = *reinterpret_cast<const float4 *>(sbias + cb + 8 * k + 4 * hh);
+                    const float4 bb = *reinterpret_cast<const float4 *>(sbias + cb + 8 * (k + 1) + 4 * hh);
+                    va[0] = acc[i][j][4 * k + 0] + ba.x; va[1] = acc[i][j][4 * k + 1] + ba.y;
+                    va[2] = acc[i][j][4 * k + 2] + ba.z; va[3] = acc[i][j][4 * k + 3] + ba.w;
+                    vb[0] = acc[i][j][4 * k + 4] + bb.x; vb[1] = acc[i][j][4 * k + 5] + bb.y;
+                    vb[2] = acc[i][j][4 * k + 6] + bb.z; vb[3] = acc[i][j][4 * k + 7] + bb.w;
+                    unsigned za0 = pack_h16x2(va[0], va[1]), za1 = pack_h16x2(va[2], va[3]);
+                    unsigned zb0 = pack_h16x2(vb[0], vb[1]), zb1 = pack_h16x2(vb[2], vb[3]);
+                    swap_halves(za0, zb0); swap_halves(za1, zb1);
+                    const int ij = conv_div(c8, p.mCn), n = c8 - ij * p.Cn;
+                    const int si = conv_div(ij, p.mS), sj = ij - si * p.s;
+                    const int Ws = W * p.s, oh = gh * p.s + si, ow = gw * p.s + sj;
+                    // (a ragged last N tile -- Nout not a multiple of the N tile -- computes its missing 32-channel blocks
+                    // on whatever weight rows follow in memory and drops them here)
+                    const bool okc = ok && c8 < p.Nout;
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{za0, za1, zb0, zb1}, z_rsrc,
+                                                           okc ? ((oh * Ws + ow) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);   // < 2^31 bytes: launcher
+                    if (APAD) {
+                        unsigned aa0 = pack_h16x2(orn_silu(va[0]), orn_silu(va[1])), aa1 = pack_h16x2(orn_silu(va[2]), orn_silu(va[3]));
+                        unsigned ab0 = pack_h16x2(orn_silu(vb[0]), orn_silu(vb[1])), ab1 = pack_h16x2(orn_silu(vb[2]), orn_silu(vb[3]));
+                        swap_halves(aa0, ab0); swap_halves(aa1, ab1);
+                        // the activation copy leaves right away (the next vmcnt wait is a whole tap of the next N tile away)
+                        __builtin_amdgcn_raw_buffer_store_b128(u32x4{aa0, aa1, ab0, ab1}, a_rsrc,
+                                                               okc ? (((oh + 1) * (Ws + 2) + (ow + 1)) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);
                     }
                 }
             }
         }
-        if (EPI_IS_FWD(EPI)) pending = true;
+        pending = true;
         STAMP(5 + nti * 4)
     }
     STAMP(2 + nt_cnt * 4)
@@ -483,7 +365,7 @@ static int launch_convf_cfg(const ConvFP &p, int n_tiles_total, hipStream_t st)
     constexpr int BN = WAVES_N * NB * 32;
     constexpr int NT = WAVES_M * WAVES_N * 64;
     constexpr size_t LDS_IMG = (size_t)(CB_PH * CB_PW * CK * 2 + 1023) / 1024 * 1024 + (ALLTAPS ? 9 : 3) * (size_t)BN * CK * 2;
-    size_t smem = LDS_IMG + (EPI_IS_FWD(EPI) ? orn_align((size_t)orn_cdiv(p.Nout, BN) * BN * 4) : 0);   // + bias copy (whole N tiles)
+    size_t smem = LDS_IMG + orn_align((size_t)orn_cdiv(p.Nout, BN) * BN * 4);   // + bias copy (whole N tiles)
 #ifdef ORN_CONV_STAMP
     smem += 1024;
 #endif
@@ -499,7 +381,6 @@ static int launch_convf_cfg(const ConvFP &p, int n_tiles_total, hipStream_t st)
     const int ptiles = p.tiles_w * p.tiles_h;
     ConvFP q = p;
     dim3 grid(ptiles, n_tiles_total / p.n_tiles_per_wg);
-    if (p.qsplit) grid.y = p.Cin / CB_CK;
     q.n_full = ptiles;
     if (p.n_tiles_per_wg > 1 && p.n_tiles_per_wg == n_tiles_total && ptiles > 256) {
         // 256 CUs, one work-group each: whole rounds keep full tiles, the last partial round is cut up
@@ -513,16 +394,7 @@ static int launch_convf_cfg(const ConvFP &p, int n_tiles_total, hipStream_t st)
 
 void set_debug_fwd(int flags) { g_convf_dbg = flags; }
 
-// m with x / d == umulhi(x, m) for every 0 <= x < 2^16 and 2 <= d < 2^16 (m = ceil(2^32 / d): the error term
-// x * (m*d - 2^32) < 2^16 * 2^16); d == 1 is encoded as m = 0 (convf_div returns x)
-static unsigned convf_magic(int d)
-{
-    return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned long long)d - 1) / (unsigned long long)d);
-}
-
-int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st, OrnHeadFuse *head);   // orn_conv2_bf16.hip
-
-// fwd: N tile 128 (waves 4x2, wave tile 64 px x 64 ch); dgrad: N = 96 in one tile (waves 8x1, 32 px x 96 ch)
+// N tile 128 (waves 4x2, wave tile 64 px x 64 ch)
 // c_real: input channels that are not zero padding (<= Cin); <= 32 of them take the narrow form (forward of a non-last block)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
                              h16 *z, h16 *apad, hipStream_t st, int c_real, OrnHeadFuse *head)
@@ -544,7 +416,7 @@ int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p
     ORN_REQUIRE(O <= 2048 && s < 65536 && (long)(H * s + 2) * (W * s + 2) * p.Cn < 1073741824L, "conv_bf16_fwd: sizes exceed the 32-bit index math");
     p.z_bytes = (unsigned)((size_t)(H * s) * (W * s) * p.Cn * 2);
     p.apad_bytes = apad ? (unsigned)((size_t)(H * s + 2) * (W * s + 2) * p.Cn * 2) : 0;
-    p.mCn = convf_magic(p.Cn); p.mS = convf_magic(s);
+    p.mCn = conv_magic(p.Cn); p.mS = conv_magic(s);
     const int nt_total = orn_cdiv(O, 128);
     // One work-group per CU (LDS): keep a pixel tile's N tiles together (patch staged once) unless cutting them
     // apart fills the chip better.  Cost model in units of one N tile: rounds x (work + ~0.3 for the patch).

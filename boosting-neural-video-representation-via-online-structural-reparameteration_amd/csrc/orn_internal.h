@@ -113,8 +113,10 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
                     const float *tstats = nullptr,    // tstats: orn_loss_target_stats of the SAME frame table (Fusion6; indexed by *frame_idx)
                     OrnLossFinalJob *defer = nullptr);   // defer: the finalize stage is returned as a job instead of launched
 
-// orn_conv_bf16.hip: the 16-bit MFMA fast path (channels-last buffers, see the file header).  The file is built
-// twice (bf16 and, with -DORN_FP16, IEEE half); the engine reaches either build through this type-erased table.
+// The 16-bit MFMA fast path (channels-last buffers, see the header of orn_conv_bf16.hip): orn_conv_fwd_bf16.hip, orn_conv_bf16.hip
+// (dgrad), orn_conv2_bf16.hip (both, large images), orn_wgrad_bf16.hip and orn_ops_bf16.hip, with orn_h16.h between them.  These
+// files are built twice (bf16 and, with -DORN_FP16, IEEE half); the engine reaches either build through the type-erased table
+// that orn_ops_bf16.hip fills.
 struct OrnPrepLayer { const float *wf, *bf; int O, C, s; void *wb, *wd; float *biasp; int Cp; };   // Cp: channel stride (0: = C)
 // deferred split-K reduction of a layer's wgrad slabs (wgrad called with dwf == nullptr leaves them in `slabs`)
 struct OrnWgradReduce { const float *slabs; int H, W, C, O, s; float gscale; float *dwf, *dbf; OrnScaleState *sc; int smax; };   // sc (optional): 1/scale from the device state, non-finite results raise its flag

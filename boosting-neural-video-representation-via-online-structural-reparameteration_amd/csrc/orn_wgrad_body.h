@@ -1,6 +1,6 @@
-// wgrad work-group body of the 16-bit fast path (dW[tap][o'][c] = sum_p dy[p][o'] * x[p + off(tap)][c]), shared by
-// orn_conv_bf16.hip (its own launches) and orn_conv2_bf16.hip (wgrad work-groups riding behind a block's dgrad tiles).
-// Include INSIDE namespace HNS, after h16 / h16x8 / s16x4 / f32x16 / MFMA_H16 (v_mfma_f32_32x32x16) / PDBG are defined.
+// wgrad work-group body of the 16-bit fast path (dW[tap][o'][c] = sum_p dy[p][o'] * x[p + off(tap)][c]), the kernels around it
+// are in orn_wgrad_bf16.hip.
+// Include INSIDE namespace HNS, after orn_h16.h (h16 / h16x8 / s16x4 / f32x16 / MFMA_H16 (v_mfma_f32_32x32x16) / PDBG).
 #pragma once
 #define WB_TH 2                  // K tile = 2 rows x 32 pixels
 #define WB_TW 32

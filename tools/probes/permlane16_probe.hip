@@ -6,7 +6,7 @@
 #include <cstdio>
 __global__ void k(unsigned *out)
 {
-    unsigned a = 100 + threadIdx.x, b = 200 + threadIdx.x;   // named lvalues: see c2_swap_rows in csrc/orn_conv2_bf16.hip
+    unsigned a = 100 + threadIdx.x, b = 200 + threadIdx.x;   // named lvalues: see swap_rows in csrc/orn_h16.h
     const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
     out[threadIdx.x] = r[0];
     out[64 + threadIdx.x] = r[1];
