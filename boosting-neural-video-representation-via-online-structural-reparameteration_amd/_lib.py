@@ -72,6 +72,7 @@ _SIGS = {
     'orn_engine_create': (c_int, [POINTER(EngineDesc), P, P, P, P, P, c_size_t, POINTER(c_void_p)]),
     'orn_engine_destroy': (None, [P]),
     'orn_engine_decode': (c_int, [P, P, P, P]),
+    'orn_engine_decode_frames': (c_int, [P, P, P, c_int32, P, P, P, P, P]),
     'orn_engine_train_step': (c_int, [P, P, P, P, P, P, c_int32, P]),
     'orn_engine_train_steps_graph': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
     'orn_engine_train_steps': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
@@ -89,7 +90,9 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_conv_fwd_f16': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, P]),
                'orn_debug_conv_dgrad_bf16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
                'orn_debug_conv_dgrad_f16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
-               'orn_debug_merge_h16_bwd': (c_int, [c_int, P, P, P, P, P])}
+               'orn_debug_merge_h16_bwd': (c_int, [c_int, P, P, P, P, P]),
+               'orn_debug_decode_out_ws_bytes': (c_size_t, []),
+               'orn_debug_decode_out_f32': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P])}
 
 _lib = None
 

@@ -6,6 +6,7 @@
 #include "orn_internal.h"
 #include <new>
 #include <cstdlib>
+#include <cassert>
 
 struct LayerBuf {
     float *T, *wf, *bf;   // merge products (ERB) -- wf/bf alias the params for vanilla/deploy
@@ -35,6 +36,7 @@ struct orn_engine {
     float *pre1, *h1, *pre2, *h2, *dh2;
     float *img, *dimg, *stats;
     float *loss_ws;
+    float *dec_ws;                   // orn_engine_decode_frames: per-block partial sums of the PSNR + the ticket (OrnDecodeOut)
     float *scratch;                  // shared scratch for the backward kernels
     float *head_ws;                  // 16-bit head backward: per-block partials (live until the deferred finish)
     OrnStepCur *cur;                 // state of the step in flight (device)
@@ -247,6 +249,7 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
     }
     float *cur_side = take((sizeof(OrnStepCur) + 3) / 4 + 16);
     float *sc_side = take(sizeof(OrnScaleState) / 4 + 16);
+    float *dec_ws = take(ORN_DECODE_WS_FLOATS);
     if (e) {
         e->pre1 = pre1; e->h1 = h1; e->pre2 = pre2; e->h2 = h2; e->dh2 = dh2;
         e->img = img; e->dimg = dimg; e->stats = stats; e->loss_ws = loss_ws; e->scratch = scr; e->head_ws = head_ws;
@@ -261,6 +264,7 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
         for (int k = 0; k < 3; ++k) { e->mset[k].tables = mtab[k]; e->mset[k].mh_tables = mhtab[k]; }
         e->cur_side = (OrnStepCur *)cur_side;
         e->sc_side = (OrnScaleState *)sc_side;
+        e->dec_ws = dec_ws;
     }
     return off * 4;
 }
@@ -563,9 +567,14 @@ static OrnWgradReduce wgrad_reduce(const orn_engine *e, int i, OrnScaleState *sc
 }
 
 // set: which layers this forward merges (0 all; 1: all but the last block, whose merged kernel the side branch of the previous
-// pipelined step leaves behind -- the forward then waits for that branch where it touches the last block's buffers)
-static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set = 0)
+// pipelined step leaves behind -- the forward then waits for that branch where it touches the last block's buffers;
+// MERGE_NONE: nothing -- the parameters have not changed since the previous forward (frames 1.. of orn_engine_decode_frames), so
+// every wf / bf / wb / biasp is used as that forward left it: no W2 transpose, no merge launch, no operand copies, no riders)
+// head: false leaves the A5 head of a 16-bit engine to the caller (the decode output kernel reads the last block's z)
+enum { MERGE_NONE = -1 };
+static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set = 0, bool head = true)
 {
+    const bool merge = set != MERGE_NONE;
     const orn_engine_desc &d = e->d;
     const int Nout = d.fc_h * d.fc_w * d.fc_dim;
     float *P = e->params;
@@ -575,7 +584,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
     const int nl = d.n_layers, ff = e->ff;
     const void *pack_t = nullptr;
     int pack_t_blocks = 0;
-    if (d.erb) {
+    if (d.erb && merge) {
         // online re-parameterisation of every layer (model.py:534): weights only, so all layers up front -- two grouped
         // launches (T, then S with the bias merge b3x3 + (b1x3 + b3x1) in its first tile column), each carrying one of
         // the stem's two linear layers as extra work-groups
@@ -592,7 +601,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
         ORN_TRY(orn_launch_linear_silu(lin1.x, lin1.row_idx, lin1.row_stride, lin1.w, lin1.bias, 1, lin1.K, lin1.N, lin1.pre, lin1.y, st));
         ORN_TRY(orn_launch_linear_silu(lin2.x, nullptr, 0, lin2.w, lin2.bias, 1, lin2.K, lin2.N, lin2.pre, lin2.y, st));
     }
-    if (ff < nl && !d.erb) {      // 16-bit operand copies of every fast layer's kernel, one launch (ERB: written by the merge's S launch)
+    if (ff < nl && !d.erb && merge) {      // 16-bit operand copies of every fast layer's kernel, one launch (ERB: written by the merge's S launch)
         OrnPrepLayer pl[ORN_MAX_LAYERS];
         const int np = (set == 1 ? nl - 1 : nl) - ff;       // (pipelined step: the side branch prepares the last block's)
         for (int i = ff; i < ff + np; ++i) pl[i - ff] = prep_layer(e, i);
@@ -608,7 +617,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
                 // ERB: the 16-bit operand copies of the later blocks' merged kernels ride on this launch (orn_prep_rider.h)
                 OrnPrepLayer pl[ORN_MAX_LAYERS];
                 int np = 0;
-                if (d.erb)
+                if (d.erb && merge)
                     for (int j = ff; j < (set == 1 ? nl - 1 : nl); ++j) pl[np++] = prep_layer(e, j);
                 ORN_TRY(orn_launch_stage0_fwd(x, b.wf, b.bf, l.C, l.O, l.H, l.W, l.s, keep_z ? b.z : nullptr, e->L[1].xpad, ORN_FAST_C,
                                               d.precision, st, np, pl, pack_t, pack_t_blocks));
@@ -634,12 +643,12 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
             if (e->side_busy && last) { ORN_HIP(hipStreamWaitEvent(st, e->ev_join, 0)); e->side_busy = false; }
             if (last) hf = OrnHeadFuse{P + d.head_w, P + d.head_b, e->img, d.sigmoid, 0};
             ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C,
-                                     last ? &hf : nullptr));
+                                     last && head ? &hf : nullptr));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
         }
     }
     if (ff < nl) {
-        if (!hf.fused)
+        if (!hf.fused && head)
             ORN_TRY(e->ops->head_fwd(e->L[nl - 1].zb, P + d.head_w, P + d.head_b, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img, st));
     } else
     {
@@ -657,6 +666,34 @@ extern "C" int orn_engine_decode(orn_engine *e, const float *embed, float *img, 
     ORN_TRY(forward(e, embed, nullptr, false, st));
     hipError_t rc = hipMemcpyAsync(img, e->img, (size_t)3 * e->Hout * e->Wout * 4, hipMemcpyDeviceToDevice, st);
     if (rc != hipSuccess) { orn_set_error("engine_decode: copy failed: %s", hipGetErrorString(rc)); return (int)rc; }
+    return 0;
+}
+
+// n frames back to back: frame 0 runs the full forward (the parameters may have changed since the last call), the others reuse
+// its merged kernels and operand copies (MERGE_NONE); each ends in the decode output stage (orn_decode_out.hip) instead of
+// head + copy (+ the caller's torch ops for bytes and PSNR).  main_eval.py:795-815, main_train.py:377-438.
+extern "C" int orn_engine_decode_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const float *targets,
+                                        uint8_t *rgb8, float *img, float *stats, void *stream)
+{
+    ORN_REQUIRE(e && embeds, "engine_decode_frames: null engine / embeds");
+    ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_decode_frames: n=%d frames need a device array of n row indices", n);
+    ORN_REQUIRE(rgb8 || img || stats, "engine_decode_frames: no output asked for (rgb8, img and stats are all null)");
+    ORN_REQUIRE(!stats || targets, "engine_decode_frames: stats need targets");
+    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
+    hipStream_t st = (hipStream_t)stream;
+    const orn_engine_desc &d = e->d;
+    const size_t HW = (size_t)e->Hout * e->Wout;
+    const bool fast = e->ff < d.n_layers;
+    if (stats && n > 0) ORN_HIP(hipMemsetAsync(e->dec_ws + 2 * ORN_DECODE_MAX_BLOCKS, 0, 64 * 4, st));      // the ticket starts at zero
+    for (int32_t k = 0; k < n; ++k) {
+        ORN_TRY(forward(e, embeds, rows + k, false, st, k == 0 ? 0 : MERGE_NONE, false));
+        const OrnDecodeOut o = {targets, rows + k, rgb8 ? rgb8 + (size_t)k * HW * 3 : nullptr, img ? img + (size_t)k * HW * 3 : nullptr,
+                                stats ? stats + (size_t)k * 4 : nullptr, e->dec_ws};
+        if (fast)
+            ORN_TRY(e->ops->decode_out(e->L[d.n_layers - 1].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st));
+        else
+            ORN_TRY(orn_launch_decode_out_f32(e->img, HW, o, st));
+    }
     return 0;
 }
 

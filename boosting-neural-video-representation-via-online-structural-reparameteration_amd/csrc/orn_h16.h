@@ -134,6 +134,33 @@ static inline unsigned conv_magic(int d)
     return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned long long)d - 1) / (unsigned long long)d);
 }
 
+// A5 head on the channels-last pre-activation of the last block, the per-pixel arithmetic (k_head_fwd_nhwc_bf16 and the decode
+// output kernel of orn_decode_out.hip share it, so their fp32 results are bit-identical): 4 lanes per pixel, lane `sub` holds the
+// 8-channel groups q*4 + sub.  sw: LDS copy of W [3][C] followed by the three biases.
+#define HB_MAXC 256
+__device__ __forceinline__ void head_accum8(const h16x8 v, int c0, int C, const float *sw, float &a0, float &a1, float &a2)
+{
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float a = orn_silu((float)v[e]);
+        a0 = fmaf(sw[c0 + e], a, a0);
+        a1 = fmaf(sw[C + c0 + e], a, a1);
+        a2 = fmaf(sw[2 * C + c0 + e], a, a2);
+    }
+}
+// sums over the four lanes of a pixel (all four must be active)
+__device__ __forceinline__ void head_reduce4(float &a0, float &a1, float &a2)
+{
+    a0 += __shfl_xor(a0, 1, 64); a1 += __shfl_xor(a1, 1, 64); a2 += __shfl_xor(a2, 1, 64);
+    a0 += __shfl_xor(a0, 2, 64); a1 += __shfl_xor(a1, 2, 64); a2 += __shfl_xor(a2, 2, 64);
+}
+// output channel `sub` (< 3) of the pixel from its reduced sums
+__device__ __forceinline__ float head_act(float a0, float a1, float a2, int sub, int C, const float *sw, int sigmoid)
+{
+    const float u = (sub == 0 ? a0 : (sub == 1 ? a1 : a2)) + sw[3 * C + sub];
+    return sigmoid ? 1.0f / (1.0f + __expf(-u)) : (tanhf(u) + 1.0f) * 0.5f;
+}
+
 // ---- launchers and switches that one file of the path defines and another calls ------------------------------------------
 // orn_conv_fwd_bf16.hip.  c_real: input channels that are not zero padding (<= Cin)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
@@ -155,5 +182,7 @@ int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, con
 int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0);
 int orn_launch_head_finish_bf16(const float *partial, int blocks, int C, float gscale, float *dw, float *db, hipStream_t st);
 void set_debug_wgrad(int flags);
+// orn_decode_out.hip
+int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
 
 }  // namespace HNS

@@ -126,6 +126,15 @@ struct OrnWgradJob { const void *xpad, *dypad; int H, W, C, O, s; float *slabs; 
 // A5 head riding on the last block's forward (its epilogue holds all channels of an output pixel): out = act(W SiLU(z) + b).
 // The launcher sets `fused` when the kernel it chose did the head; otherwise the caller launches head_fwd on z.
 struct OrnHeadFuse { const float *w, *b; float *out; int sigmoid; int fused; };
+// Decode output stage (orn_decode_out.hip): what one decoded frame leaves behind.  Every output is optional (null: not wanted).
+//   rgb8 [H][W][3] bytes, q = (uint8) clamp(x*255 + 0.5, 0, 255); img [3][H][W] fp32; stats {mse, psnr} of x and of q/255 against
+//   targets[*row] ([3][H][W] fp32 each).  ws: ORN_DECODE_WS_FLOATS floats, the last of them a ticket counter that is zero
+//   between launches (per-block partial sums in front of it; the last block to arrive sums them in fixed order).
+#define ORN_DECODE_MAX_BLOCKS 8192
+#define ORN_DECODE_WS_FLOATS (2 * ORN_DECODE_MAX_BLOCKS + 64)
+struct OrnDecodeOut { const float *targets; const int32_t *row; uint8_t *rgb8; float *img, *stats; float *ws; };
+// fp32 engine: the same stage from the planar image the fp32 head wrote
+int orn_launch_decode_out_f32(const float *src, size_t HW, const OrnDecodeOut &o, hipStream_t st);
 struct OrnHalfOps {
     int (*conv_fwd)(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s, void *z, void *apad,
                     hipStream_t st, int c_real, OrnHeadFuse *head);   // c_real <= Cin: input channels that are not zero padding; head: optional
@@ -146,6 +155,8 @@ struct OrnHalfOps {
     int (*head_bwd)(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp,
                     float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc,
                     const OrnLossFinalJob *fin);   // sc: gs from the device state; fin (optional): the loss's finalize stage as one more work-group
+    // decode: head forward on z + the output stage above in one kernel (same per-pixel arithmetic as head_fwd)
+    int (*decode_out)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
 };
 const OrnHalfOps *orn_half_ops_bf16();
 const OrnHalfOps *orn_half_ops_f16();

@@ -214,8 +214,6 @@ int orn_launch_dbias_bf16(const h16 *dypad, int H, int W, int O, int s, float gs
 //   a = SiLU(z);  u = W a + b;  out = (tanh u + 1)/2 | sigmoid u           out: fp32 NCHW [3][H][W]
 // 4 lanes per pixel (C/4 channels each, 16-byte loads), 16 pixels per wave: fully coalesced.
 // ================================================================================================
-#define HB_MAXC 256
-
 __global__ void __launch_bounds__(256)
 k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ bias, int C, size_t HW,
                      int sigmoid, float *__restrict__ out)
@@ -249,15 +247,7 @@ k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
                     if (q < nq) vn[q] = *reinterpret_cast<const h16x8 *>(z + pnx * C + (q * 4 + sub) * 8);
             }
         }
-        auto proc = [&](const h16x8 v, int c0) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float a = orn_silu((float)v[e]);
-                a0 = fmaf(sw[c0 + e], a, a0);
-                a1 = fmaf(sw[C + c0 + e], a, a1);
-                a2 = fmaf(sw[2 * C + c0 + e], a, a2);
-            }
-        };
+        auto proc = [&](const h16x8 v, int c0) { head_accum8(v, c0, C, sw, a0, a1, a2); };
         if (piped) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -265,12 +255,8 @@ k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
         } else {
             for (int q = 0; q < nq; ++q) proc(*reinterpret_cast<const h16x8 *>(z + pix * C + (q * 4 + sub) * 8), (q * 4 + sub) * 8);
         }
-        a0 += __shfl_xor(a0, 1, 64); a1 += __shfl_xor(a1, 1, 64); a2 += __shfl_xor(a2, 1, 64);
-        a0 += __shfl_xor(a0, 2, 64); a1 += __shfl_xor(a1, 2, 64); a2 += __shfl_xor(a2, 2, 64);
-        if (sub < 3) {
-            const float u = (sub == 0 ? a0 : (sub == 1 ? a1 : a2)) + sw[3 * C + sub];
-            out[(size_t)sub * HW + pix] = sigmoid ? 1.0f / (1.0f + __expf(-u)) : (tanhf(u) + 1.0f) * 0.5f;
-        }
+        head_reduce4(a0, a1, a2);
+        if (sub < 3) out[(size_t)sub * HW + pix] = head_act(a0, a1, a2, sub, C, sw, sigmoid);
     }
 }
 
@@ -442,12 +428,14 @@ static int a_to_nchw_f32(const float *src, int C, int Cp, int H, int W, int nsla
 { return orn_launch_nhwc_to_nchw_f32(src, C, Cp, H, W, nslab, scale, dst, st, sc); }
 static int a_head_fwd(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st)
 { return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, HW, sigmoid, out, st); }
+static int a_decode_out(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st)
+{ return orn_launch_decode_out_h16((const h16 *)z, w, b, C, HW, sigmoid, o, st); }
 static int a_head_bwd(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp,
                       float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc, const OrnLossFinalJob *fin)
 { return orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs_up, (h16 *)dypad, dw, db, ws, st, sc, fin); }
 
 const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, a_wgrad, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
-                        a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd};
+                        a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out};
 
 // ================================================================================================
 // test / per-op hooks: the 16-bit block on PyTorch-layout fp32 tensors (conversions included).  Built in both element

@@ -84,7 +84,108 @@ def make_schedule(entries: Sequence[Tuple[int, int, float]]) -> np.ndarray:
     return arr
 
 
-class TrainEngine:
+def _out_hw(model):
+    Hs, Ws = model.fc_h, model.fc_w
+    for blk in model.layers:
+        Hs, Ws = Hs * blk.stride, Ws * blk.stride
+    return Hs, Ws
+
+
+class _Decoding:
+    """Forward-only entry points of an engine handle (`_h`, `device`, `out_hw`, `desc`; `frames` / `embeds` when a video is
+    resident): shared by TrainEngine and the decode-only Decoder."""
+    frames = None
+    embeds = None
+
+    def decode(self, embed: torch.Tensor) -> torch.Tensor:
+        """Forward only: embed [E] or [1,E] -> image [1,3,H,W]."""
+        embed = embed.to(self.device, torch.float32).contiguous().view(-1)
+        img = torch.empty(1, 3, *self.out_hw, device=self.device)
+        check(lib().orn_engine_decode(self._h, _lib.ptr(embed), _lib.ptr(img), _lib.stream()), 'orn_engine_decode')
+        return img
+
+    def decode_frames(self, rows=None, embeds=None, frames=None, rgb8=True, f32=False, stats=True) -> dict:
+        """Decode many frames in one call (orn_engine_decode_frames; main_eval.py:795-815, main_train.py:377-438): the weight-only
+        work of the forward runs once, and each frame ends on the device in what is asked for.
+        rows: indices (sequence or tensor) into `embeds` [*,E] and `frames` [*,3,H,W]; both default to the resident video
+        (set_video) and rows to all of it.  Returns device tensors, enqueued on the current stream without a host sync:
+          'rgb8'  uint8 [n,H,W,3], torchvision.utils.save_image's bytes;  'img' float [n,3,H,W] (f32=True);
+          'stats' float [n,4]: mse, PSNR of the float image, mse, PSNR of the bytes / 255, against frames[rows] (stats=True; needs frames)."""
+        embeds = self.embeds if embeds is None else embeds.to(self.device, torch.float32).contiguous()
+        frames = self.frames if frames is None else frames.to(self.device, torch.float32).contiguous()
+        if embeds is None:
+            raise OrnError('decode_frames: no embeds given and no video resident (set_video)')
+        if embeds.dim() != 2 or embeds.shape[1] != self.desc.embed_len:
+            raise OrnError(f'decode_frames: embeds {tuple(embeds.shape)} vs (*, {self.desc.embed_len})')
+        if stats and frames is None:
+            raise OrnError('decode_frames: stats need target frames (frames=, or set_video)')
+        if frames is not None and tuple(frames.shape[1:]) != (3,) + tuple(self.out_hw):
+            raise OrnError(f'decode_frames: frames {tuple(frames.shape)} do not match the decoder output {self.out_hw}')
+        if rows is None:
+            rows = torch.arange(embeds.shape[0], dtype=torch.int32)
+        rows = torch.as_tensor(rows).to(torch.int32).reshape(-1)
+        n = int(rows.numel())
+        limit = embeds.shape[0] if not stats else min(embeds.shape[0], frames.shape[0])
+        if n and (int(rows.min()) < 0 or int(rows.max()) >= limit):        # the device would read out of bounds
+            raise OrnError(f'decode_frames: row index out of range [0, {limit})')
+        rows = rows.to(self.device).contiguous()
+        H, W = self.out_hw
+        out = {}
+        if rgb8:
+            out['rgb8'] = torch.empty(n, H, W, 3, dtype=torch.uint8, device=self.device)
+        if f32:
+            out['img'] = torch.empty(n, 3, H, W, device=self.device)
+        if stats:
+            out['stats'] = torch.empty(n, 4, device=self.device)
+        check(lib().orn_engine_decode_frames(self._h, _lib.ptr(embeds), _lib.ptr(rows), c_int32(n), _lib.ptr(frames) if stats else None,
+                                             _lib.ptr(out.get('rgb8')), _lib.ptr(out.get('img')), _lib.ptr(out.get('stats')),
+                                             _lib.stream()), 'orn_engine_decode_frames')
+        self._decode_keep = (embeds, frames, rows)          # alive until the stream has drained
+        return out
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and h.value:
+            try:
+                lib().orn_engine_destroy(h)
+                self._h = c_void_p()
+            except Exception:          # interpreter shutdown: module globals may already be gone
+                pass
+
+
+class Decoder(_Decoding):
+    """Decode-only engine for a fitted model (loaded from a train-mode or a `_deploy` checkpoint, checkpoint.load_into): the
+    parameter arena and the workspace, no gradient or Adam arenas -- the training entry points refuse such an engine.
+    precision: 'fp16' | 'bf16' run the blocks on 16-bit MFMA as the training engine does (the arithmetic a fit at that
+    precision was evaluated with); 'fp32' is the reference's."""
+
+    def __init__(self, model, precision: str = 'fp16', device: Optional[torch.device] = None):
+        if not torch.cuda.is_available():
+            raise OrnError('Decoder needs a GPU: there is no CPU path')
+        self.device = torch.device(device or f'cuda:{torch.cuda.current_device()}')
+        self.model = model
+        named = [(k, tuple(p.shape)) for k, p in model.named_parameters()]
+        self.layout, self.n_params = arena_layout(named)
+        self.params = torch.zeros(self.n_params, device=self.device)
+        with torch.no_grad():
+            for k, p in model.named_parameters():
+                off, n = self.layout[k]
+                view = self.params[off:off + n].view(p.shape)
+                view.copy_(p.detach().to(self.device))
+                p.data = view                                   # the module and the engine share the arena
+        self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
+        self.desc = build_desc(model, self.layout, self.n_params, 'L2', 0.5, 0.999, 1e-8, self.precision)
+        nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
+        if nbytes == 0:
+            raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._h = c_void_p()
+        check(lib().orn_engine_create(byref(self.desc), _lib.ptr(self.params), None, None, None, _lib.ptr(self.ws), c_size_t(nbytes),
+                                      byref(self._h)), 'orn_engine_create')
+        self.out_hw = _out_hw(model)
+
+
+class TrainEngine(_Decoding):
     """Native training engine for one video (one process / one GPU per video)."""
 
     def __init__(self, model, loss_type: str = 'Fusion6', beta: float = 0.5, precision: str = 'fp32',
@@ -127,22 +228,10 @@ class TrainEngine:
         self.embeds = None
         self.global_step = 0
         self.skipped_carry = 0                             # steps skipped by engines this one replaced (main_train fall-back)
-        Hs, Ws = model.fc_h, model.fc_w
-        for blk in model.layers:
-            Hs, Ws = Hs * blk.stride, Ws * blk.stride
-        self.out_hw = (Hs, Ws)
+        self.out_hw = _out_hw(model)
         # HIP graphs cannot be captured on the legacy default stream: the engine runs on its own
         # stream, ordered against the caller's current stream on entry and exit.
         self.stream = torch.cuda.Stream(device=dev)
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h is not None and h.value:
-            try:
-                lib().orn_engine_destroy(h)
-                self._h = c_void_p()
-            except Exception:          # interpreter shutdown: module globals may already be gone
-                pass
 
     # ---- data ---------------------------------------------------------------------------------
     def set_video(self, frames: torch.Tensor, embeds: torch.Tensor):
@@ -266,13 +355,6 @@ class TrainEngine:
     def stats(self, n: int) -> torch.Tensor:
         """[n,8] host tensor of the last run's first n steps: loss, L1, MSE, SSIM, PSNR, lr, frame, step."""
         return self.stats_ring[:n].cpu()
-
-    def decode(self, embed: torch.Tensor) -> torch.Tensor:
-        """Forward only: embed [E] or [1,E] -> image [1,3,H,W]."""
-        embed = embed.to(self.device, torch.float32).contiguous().view(-1)
-        img = torch.empty(1, 3, *self.out_hw, device=self.device)
-        check(lib().orn_engine_decode(self._h, _lib.ptr(embed), _lib.ptr(img), _lib.stream()), 'orn_engine_decode')
-        return img
 
     def engine_fused_kernel(self, layer: int):
         """(Wf, bf) of block `layer` exactly as the ENGINE's last merge left them in its workspace (copies; ERB only)."""

@@ -2,6 +2,10 @@
 load `model_latest(.pth|_deploy.pth)` -> global L1 prune (--prune_ratio) -> switch to deploy -> per-axis 8-bit
 quantisation + Huffman size estimate (--quant_bit) -> decode every frame (PSNR, decoder FPS, bits per pixel).
 
+`--decoder engine` decodes with the native engine at `--precision` (engine.Decoder: all frames in one
+orn_engine_decode_frames call, PSNR of the float image and of the 8-bit pixels and the `--dump_images` bytes computed on the
+device); the default `eager` is the per-op fp32 module forward, frame by frame.
+
 `--finetune` (main_eval.py:213-545): load the TRAIN-mode checkpoint, prune the stem Linear weights and every conv
 branch weight together (global L1), fine-tune `--finetune_epochs` on the native engine, then deploy/quantise/evaluate.
 The reference's behaviour is kept, quirks included: Q1 -- with ERB the online merge reads `.weight`
@@ -82,14 +86,52 @@ def _prune_finetune(model, args, PE, ckpt_path, vid_index=0):
     return keep, {k: v for k, v in originals.items() if k in keep}
 
 
-def main(argv=None):
+def eval_parser():
     p = build_parser()
     p.add_argument('--finetune', action='store_true')
     p.add_argument('--finetune_epochs', type=int, default=100)
     p.add_argument('--cycles', type=int, default=1)
     p.add_argument('--video', default=None, help='which video of a multi-video training job (--dataset a,b,c or a multi-rank '
                                                   '--synthetic job: synthetic<k>) to evaluate; default: the first')
-    args = p.parse_args(argv)
+    p.add_argument('--decoder', default='eager', choices=['eager', 'engine'],
+                   help='eager: the fp32 module forward per frame; engine: the native engine at --precision, all frames in one '
+                        'call, PSNR (float and 8-bit) and the --dump_images pixels computed on the device')
+    return p
+
+
+def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
+    """--decoder engine: every frame through engine.Decoder in one call (main_eval.py:795-815)."""
+    from . import engine as oeng
+    n = frames.shape[0]
+    dec = oeng.Decoder(model, precision=args.precision)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = dec.decode_frames(embeds=embeds, frames=frames, rgb8=True, f32=False, stats=True)
+    torch.cuda.synchronize()
+    fps = n / (time.time() - t0)
+    st = out['stats'].double().mean(0)
+    psnr, psnr8 = float(st[1]), float(st[3])
+    if args.dump_images:
+        from PIL import Image
+        visual_dir = os.path.join(outf, 'visualize')
+        os.makedirs(visual_dir, exist_ok=True)
+        print(f'Saving predictions to {visual_dir}')
+        for k, arr in enumerate(out['rgb8'].cpu().numpy()):
+            Image.fromarray(arr).save(os.path.join(visual_dir, f'pred_{k}.png'))
+    ms = []
+    for k in range(n):                                               # untimed, as the FPS above is the decoder's
+        img = dec.decode_frames(rows=[k], embeds=embeds, rgb8=False, f32=True, stats=False)['img']
+        ms.append(utils.msssim_fn([img], [frames[k:k + 1]])[0, 0])
+    msg = (f'Eval: PSNR {psnr:.2f} dB, 8-bit PSNR {psnr8:.2f} dB, MS-SSIM {float(torch.stack(ms).mean()):.4f}, '
+           f'decode {fps:.1f} FPS (engine, {args.precision}), params {n_param / 1e6:.3f} M')
+    if bits is not None:
+        msg += f', bpp {bits / (n * hw[0] * hw[1]):.4f}'
+    print(msg)
+    return psnr
+
+
+def main(argv=None):
+    args = eval_parser().parse_args(argv)
     args.warmup = int(args.warmup * args.epochs)          # main_eval.py:106 (as main_train.parse_args): warm-up in epochs
     outf = os.path.join('result', args.outf, f'{args.suffix}')
     # a job that fitted several videos wrote one sub-directory per video (main_train.video_outf)
@@ -153,6 +195,8 @@ def main(argv=None):
     frames, pos = load_frames(args, hw, 'cuda', args.dataset, vid_index, args.test_gap)       # val_dataset: CustomDataSet(frame_gap=test_gap)
     n = frames.shape[0]
     embeds = PE(pos)
+    if args.decoder == 'engine':
+        return _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw)
     psnrs = []
     torch.cuda.synchronize()
     t0 = time.time()

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3) */
+#define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -219,6 +219,20 @@ ORN_API int orn_engine_create(const orn_engine_desc *d, float *params, float *gr
 ORN_API void orn_engine_destroy(orn_engine *e);
 /* Forward only (decode): embed [E] device -> img [3,H,W] device. */
 ORN_API int orn_engine_decode(orn_engine *e, const float *embed, float *img, void *stream);
+/* ---- N2  decode a fitted video: pixels and PSNR                     main_eval.py:795-815, main_train.py:377-438 ----
+ * Decode n frames back to back on `stream` (no sync, capturable).  The weight-only work of the forward (ERB merge, 16-bit
+ * operand copies) runs once, for frame 0; a 16-bit engine ends each frame in one kernel that reads the last block's output and
+ * writes what is asked for (no fp32 image in between, no copy).
+ * rows: DEVICE int32[n], indices into `embeds` [*,E] and, when given, `targets` [*,3,H,W] (fp32 planar).
+ * Outputs, each optional (NULL = not wanted), at least one of the three non-NULL:
+ *   rgb8  uint8 [n][H][W][3]   interleaved; q = (uint8) clamp(x*255 + 0.5, 0, 255)  (torchvision save_image; three fp32 ops)
+ *   img   float [n][3][H][W]   what orn_engine_decode writes, bit for bit
+ *   stats float [n][4]         {mse, psnr} of the float image and {mse, psnr} of q/255, against targets[rows[k]]
+ *                              (psnr = -10 log10(mse), utils.py:191); requires targets
+ * The engine may have been created without grads / Adam arenas (a decode-only engine).  Not to be enqueued on two streams at once
+ * (one workspace). */
+ORN_API int orn_engine_decode_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n,
+                                     const float *targets, uint8_t *rgb8, float *img, float *stats, void *stream);
 /* One optimiser step.  frames [n_frames,3,H,W], embeds [n_frames,E] (device); sched: device array,
  * `cursor` a device int32 the step reads and post-increments, so `n` back-to-back steps consume
  * sched[cursor..cursor+n).  stats_out: device [n_slots][8] ring written at slot (cursor % n_slots). */

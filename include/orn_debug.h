@@ -36,6 +36,13 @@ ORN_API int orn_debug_conv_dgrad_f16(const void *dypad, const void *wd, int H, i
  * *flag: the flag word of the scale state after the call (1: a half copy of G or of dT was not finite).  Returns 0 or an
  * error code. */
 ORN_API int orn_debug_merge_h16_bwd(int n, const int *co, const float *const *in, float *const *out, int *flag, void *stream);
+/* The output stage of orn_engine_decode_frames in its fp32-engine form, on a caller's planar image img [3][H][W] (device): bytes
+ * rgb8 [H][W][3], a copy img_out, stats[4] = {mse, psnr, mse of bytes / 255, its psnr} against target [3][H][W]; each output
+ * optional.  ws (device, 4-byte aligned, the size the _ws_bytes call returns) is needed for stats only.  tests/test_gpu_decode.py pins the
+ * quantisation at the half-way points k + 0.5 through it. */
+ORN_API size_t orn_debug_decode_out_ws_bytes(void);
+ORN_API int orn_debug_decode_out_f32(const float *img, int H, int W, const float *target, uint8_t *rgb8, float *img_out,
+                                     float *stats, void *ws, size_t ws_bytes, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
