@@ -52,7 +52,7 @@ struct orn_engine {
         OrnMergeLayer ml[ORN_MAX_LAYERS];   // the layers as the merge launchers see them
         int layer[ORN_MAX_LAYERS];      // their indices in the engine
         void *tables;                   // device-resident grouped-GEMM problem tables
-        int tiles[4];
+        int tiles[4];                   // work-groups of each table's launch, as orn_merge_groups_build counted them
         void *mh_tables, *mh_host;      // 16-bit modes: tables of the packed-operand merge backward (device / host)
     } mset[3];
     int ff;                          // first layer on the bf16 fast path (== n_layers: none)
@@ -399,13 +399,12 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
                 bufs[ms.n] = e->L[i].mh16;
                 ms.layer[ms.n++] = i;
             }
-            int rc = orn_merge_groups_build(ms.tables, ms.n, ms.ml, d->precision != 0);
+            int rc = orn_merge_groups_build(ms.tables, ms.n, ms.ml, d->precision == 0, ms.tiles);
             if (rc == 0 && d->precision != 0) {
                 ms.mh_host = malloc(orn_merge_h16_host_bytes());
                 rc = ms.mh_host ? orn_merge_h16_build(ms.mh_tables, ms.mh_host, ms.n, ms.ml, bufs, k == 2 ? e->sc_side : e->sc) : ORN_E_ARG;
             }
             if (rc != 0) { orn_engine_destroy(e); return rc; }
-            for (int q = 0; q < 4; ++q) ms.tiles[q] = orn_merge_group_tiles(q, ms.n, ms.ml);
         }
     }
     *out = e;

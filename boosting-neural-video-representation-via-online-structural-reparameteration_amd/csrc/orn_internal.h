@@ -62,14 +62,12 @@ size_t orn_merge_group_bytes();
 // W2 [O][2C][3][3] -> w2t [9][O][2C] for every layer with a w2t buffer, one launch (first launch of the forward merge)
 // (pack / par_blocks: the parameter-side half copies of the merge backward's operands ride behind the transposes)
 int orn_launch_w2_transpose(int n_layers, const OrnMergeLayer *L, hipStream_t st, const void *pack = nullptr, int par_blocks = 0);
-int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *L, int bwd_h16);
-int orn_merge_group_tiles(int which, int n_layers, const OrnMergeLayer *L);
-int orn_launch_merge_group(const void *dev_tables, int which, int tiles, hipStream_t st);
+// problem tables of the grouped launches: 0 = T, 1 = S (forward); fp32_bwd: also 2 = {dW3, dT}, 3 = {dW2, dW1 partials}.
+// tiles[q]: work-groups of table q's launch, to be handed to the launchers below (0: table not built)
+int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *L, bool fp32_bwd, int tiles[4]);
+int orn_launch_merge_group(const void *dev_tables, int which, int tiles, hipStream_t st);   // which = 2 / 3 (fp32 engine)
 int orn_launch_merge_group_linear(const void *dev_tables, int which, int tiles, const OrnLinearJob &job, hipStream_t st,
                                   const void *pack = nullptr, int pack_blocks = 0);   // pack: trailing T -> Th pack jobs (orn_merge_h16_pack)
-int orn_launch_merge_bias(const float *b3x3, const float *b1x3, const float *b3x1, int O, float *bf, hipStream_t st);
-int orn_launch_merge_bwd_tail(const float *g, const float *dbf, int C, int O, float *d3x3, float *db3x3, float *d3x1,
-                              float *db3x1, float *d1x3, float *db1x3, const float *dw1p, float *dw1, hipStream_t st);
 
 // orn_merge_h16.hip: merge backward GEMMs of the 16-bit engine modes (packed half operands, fragments from global)
 size_t orn_merge_h16_layer_halfs(int C, int O);
@@ -81,15 +79,13 @@ const void *orn_merge_h16_pack(const void *host, int *par_blocks, int *t_blocks)
 // the parameter-side (which = 1) or T -> Th (which = 2) pack jobs of the set as a launch of their own (instead of riders)
 int orn_launch_merge_h16_pack_jobs(const void *host, int which, hipStream_t st);
 
-// per-layer elementwise tails of the merge, all layers per launch
+// per-layer elementwise tail of the merge backward, all layers per launch (both precisions)
 struct OrnMergeMisc {
     int C, O;
-    const float *b3x3, *b1x3, *b3x1; float *bf;                       // forward bias
     const float *g, *dbf, *dw1p;                                      // backward inputs (dWf, dbf live in the grad arena)
     float *d3x1, *db3x1, *d1x3, *db1x3, *dw1;                         // backward outputs
     const float *dw2t; float *dw2;                                    // optional: dW2 [9][O][2C] -> [O][2C][3][3]
 };
-int orn_launch_merge_bias_all(int n, const OrnMergeMisc *L, hipStream_t st);
 int orn_launch_merge_bwd_tail_all(int n, const OrnMergeMisc *L, hipStream_t st);
 
 // orn_conv_f32.hip

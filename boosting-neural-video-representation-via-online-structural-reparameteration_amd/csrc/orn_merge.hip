@@ -18,17 +18,14 @@ struct GemmP {
     long scm, scn;   // C(m,n) = C[m*scm + n*scn]
     long ba, bb, bc; // per-batch element offsets (blockIdx.z)
     int a_kfast, b_nfast;
-    int a_vec, b_vec;    // gemm_body2: 16-byte global loads of A along k / of B along n are possible (strides, sizes and bases aligned)
-    // epilogue 1 (merge combine): C = (w3x3 + (P(w1x3) + P(w3x1))) + acc, n = c*9 + ij
+    int a_vec;           // gemm_body2: A is contiguous in k, 16-byte global loads along k (B is always contiguous in n there)
+    // epilogue 1 (merge combine, gemm_body2v only): C = (w3x3 + (P(w1x3) + P(w3x1))) + acc, n = c*9 + ij
     int epi;
     const float *w3x3, *w1x3, *w3x1;
     int Cch;
     // epilogue 1, optional (engine): the first column of tiles also merges the bias, bf = b3x3 + (b1x3 + b3x1)
     const float *b3x3, *b1x3, *b3x1;
     float *bf;
-    // 16-bit MFMA variant (merge backward in the 16-bit engine modes): operands are multiplied by sa / sb when they
-    // are rounded to IEEE half (gradient operands ~1e-6 would be subnormal), the result by so = 1/(sa*sb)
-    float sa, sb, so;
     // epilogue 1, optional (16-bit engine modes): the merged kernel also leaves in the two 16-bit operand layouts of the conv
     // kernels (what k_prep_weights_bf16_all would otherwise re-read Wf for): wb [9][O'][Cp], wd [9][Cp][O'] with flipped
     // taps, o' = (o % s2) * Cn + o / s2; the bias column writes biasp [O'].  half_kind: 1 = bf16, 2 = IEEE half.
@@ -38,7 +35,14 @@ struct GemmP {
 };
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+// output row of accumulator register `reg` of v_mfma_f32_32x32x2_f32 in lane half hh (lane >> 5), row0 = first row of the wave's
+// 32x32 block (the column is lane & 31)
+__device__ __forceinline__ int acc_row(int row0, int reg, int hh) { return row0 + (reg & 3) + 8 * (reg >> 2) + 4 * hh; }
 
+// Body of the fp32 BACKWARD products, those whose B is not contiguous in n: dW3, dW2 and the dW1 partials (per op and in the
+// fp32 engine's grouped launches; there dT as well).  Any strides, plain store of the accumulator, no epilogue.  The forward
+// products and the per-op dT (B contiguous in n) run on gemm_body2v below; the 16-bit engine modes have their own merge
+// backward (orn_merge_h16.hip).
 // 64x64 output tile per work-group, 4 waves (2x2), each wave one 32x32 v_mfma_f32_32x32x2_f32 block.
 // K is consumed in ascending order, 2 per instruction (lane half 0 = even k first, then odd k), the
 // 64-deep chunks in ascending order, always into the same accumulator: one k-ordered fmaf chain per
@@ -108,44 +112,11 @@ __device__ __forceinline__ void gemm_body(const GemmP &p, int bx, int by, int bz
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[kk], bp[kk * GLDB], acc, 0, 0, 0);
     }
     const int gn = n0 + wn * 32 + l31;
-    if (p.epi == 1 && p.bf && bx == 0 && wn == 0 && l31 == 0) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-            if (gm < p.M) {
-                const float b = p.b3x3[gm] + (p.b1x3[gm] + p.b3x1[gm]);     // model.py:476,496
-                p.bf[gm] = b;
-                if (p.half_kind) p.biasp[(gm % p.s2) * p.Cn + gm / p.s2] = b;
-            }
-        }
-    }
     if (gn >= p.N) return;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        if (gm >= p.M) continue;
-        float r = acc[reg];
-        if (p.epi == 1) {
-            const int c = gn / 9, ij = gn % 9, ii = ij / 3, jj = ij % 3;
-            const long oc = (long)gm * p.Cch + c;
-            const float p13 = (ii == 1) ? p.w1x3[oc * 3 + jj] : 0.f;
-            const float p31 = (jj == 1) ? p.w3x1[oc * 3 + ii] : 0.f;
-            r = (p.w3x3[(long)gm * p.N + gn] + (p13 + p31)) + r;   // association of model.py:475,495
-            if (p.half_kind) {
-                const int op = (gm % p.s2) * p.Cn + gm / p.s2;
-                const size_t ib = ((size_t)ij * p.M + op) * p.Cp + c, id = ((size_t)(8 - ij) * p.Cp + c) * p.M + op;
-                if (p.half_kind == 1) {
-                    const __bf16 h = (__bf16)r;
-                    reinterpret_cast<__bf16 *>(p.wb)[ib] = h;
-                    reinterpret_cast<__bf16 *>(p.wd)[id] = h;
-                } else {
-                    const _Float16 h = (_Float16)r;
-                    reinterpret_cast<_Float16 *>(p.wb)[ib] = h;
-                    reinterpret_cast<_Float16 *>(p.wd)[id] = h;
-                }
-            }
-        }
-        C[(long)gm * p.scm + (long)gn * p.scn] = r;
+        const int gm = acc_row(m0 + wm * 32, reg, hh);
+        if (gm < p.M) C[(long)gm * p.scm + (long)gn * p.scn] = acc[reg];
     }
 }
 
@@ -191,7 +162,7 @@ __device__ __forceinline__ void g2_sfor(F &&f)
     }
 }
 
-template <int WM, int WN, bool AVEC, bool BVEC>
+template <int WM, int WN, bool AVEC>
 __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int bz, float *lds)
 {
     constexpr int BM = 32 * WM, BN = 32 * WN;
@@ -210,7 +181,6 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
     const int M = p.M, N = p.N, K = p.K;
     const int sam = (int)p.sam, sak = (int)p.sak, sbk = (int)p.sbk;
     constexpr bool avec = AVEC;                    // A is contiguous in k (compile-time: the load forms differ)
-    static_assert(BVEC, "B is always loaded 16 bytes at a time");
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -318,7 +288,7 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
     if (p.epi == 1) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int gm = min(m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh, p.M - 1);
+            const int gm = min(acc_row(m0 + wm * 32, reg, hh), p.M - 1);
             const long oc = (long)gm * p.Cch + ec;
             const float p13 = (eii == 1) ? p.w1x3[oc * 3 + ejj] : 0.f;
             const float p31 = (ejj == 1) ? p.w3x1[oc * 3 + eii] : 0.f;
@@ -379,7 +349,7 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
     if (p.epi == 1 && p.bf && bx == 0 && wn == 0 && l31 == 0) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+            const int gm = acc_row(m0 + wm * 32, reg, hh);
             if (gm < p.M) {
                 const float b = p.b3x3[gm] + (p.b1x3[gm] + p.b3x1[gm]);     // model.py:476,496
                 p.bf[gm] = b;
@@ -392,7 +362,7 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
         const int c = ec, ij = eij;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+            const int gm = acc_row(m0 + wm * 32, reg, hh);
             if (gm >= p.M) continue;
             const float r = base[reg] + acc[reg];
             if (p.half_kind) {
@@ -413,7 +383,7 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
     } else {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+            const int gm = acc_row(m0 + wm * 32, reg, hh);
             if (gm < p.M) C[(long)gm * p.scm + (long)gn * p.scn] = acc[reg];
         }
     }
@@ -437,77 +407,8 @@ __device__ __forceinline__ void gemm_body2v(const GemmP &p, int bx, int by, int 
 template <int WM, int WN>
 __device__ __forceinline__ void gemm_body2(const GemmP &p, int bx, int by, int bz, float *lds)
 {
-    if (p.a_vec) gemm_body2v<WM, WN, true, true>(p, bx, by, bz, lds);
-    else gemm_body2v<WM, WN, false, true>(p, bx, by, bz, lds);
-}
-
-// Same tiling on v_mfma_f32_32x32x16_f16 (fp32 accumulate): operands are rounded to IEEE half while they are
-// staged into LDS ([row][k], k contiguous, 144-byte rows: conflict-free ds_read_b128).  Used for the merge BACKWARD
-// in the 16-bit engine modes only -- the forward merge stays exact fp32.
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-#define HK 64
-#define HROW (HK * 2 + 16)
-
-__device__ __forceinline__ void gemm_body_h16(const GemmP &p, int bx, int by, int bz)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char Ah[GT * HROW];
-    __shared__ __attribute__((aligned(16))) unsigned char Bh[GT * HROW];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int l31 = lane & 31, hh = lane >> 5;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = by * GT, n0 = bx * GT;
-    const float *A = p.A + (long)bz * p.ba;
-    const float *B = p.B + (long)bz * p.bb;
-    float *C = p.C + (long)bz * p.bc;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int NE = GT * HK / 256;
-    float ra[NE], rb[NE];
-    const int tf = t & 63, tv = t >> 6;
-    const int M = p.M, N = p.N, K = p.K;
-    const int sam = (int)p.sam, sak = (int)p.sak, sbk = (int)p.sbk, sbn = (int)p.sbn;
-    const bool akf = p.a_kfast, bnf = p.b_nfast;
-    auto gload = [&](int k0) {                  // unconditional clamped loads, see gemm_body
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int v = tv + 4 * i;
-            const int am = akf ? v : tf, ak = k0 + (akf ? tf : v);
-            const int bn = bnf ? tf : v, bk = k0 + (bnf ? v : tf);
-            const float va = A[__mul24(min(m0 + am, M - 1), sam) + __mul24(min(ak, K - 1), sak)];
-            const float vb = B[__mul24(min(bk, K - 1), sbk) + __mul24(min(n0 + bn, N - 1), sbn)];
-            ra[i] = va;                         // the K-tail zeroing happens at the LDS store: consuming the value here
-            rb[i] = vb;                         // would put the load wait in front of this chunk's MFMAs
-        }
-    };
-    gload(0);
-    for (int k0 = 0; k0 < p.K; k0 += HK) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const int v = tv + 4 * i;
-            const float xa = (k0 + (akf ? tf : v) < K) ? ra[i] : 0.f, xb = (k0 + (bnf ? v : tf) < K) ? rb[i] : 0.f;
-            *reinterpret_cast<_Float16 *>(Ah + (akf ? v : tf) * HROW + (akf ? tf : v) * 2) = (_Float16)(xa * p.sa);
-            *reinterpret_cast<_Float16 *>(Bh + (bnf ? tf : v) * HROW + (bnf ? v : tf) * 2) = (_Float16)(xb * p.sb);
-        }
-        __syncthreads();
-        if (k0 + HK < p.K) gload(k0 + HK);
-        const unsigned char *ap = Ah + (wm * 32 + l31) * HROW + hh * 16;
-        const unsigned char *bp = Bh + (wn * 32 + l31) * HROW + hh * 16;
-#pragma unroll
-        for (int ks = 0; ks < HK / 16; ++ks) {
-            const f16x8 a = *reinterpret_cast<const f16x8 *>(ap + ks * 32);
-            const f16x8 b = *reinterpret_cast<const f16x8 *>(bp + ks * 32);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-        }
-    }
-    const int gn = n0 + wn * 32 + l31;
-    if (gn >= p.N) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int gm = m0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        if (gm < p.M) C[(long)gm * p.scm + (long)gn * p.scn] = acc[reg] * p.so;
-    }
+    if (p.a_vec) gemm_body2v<WM, WN, true>(p, bx, by, bz, lds);
+    else gemm_body2v<WM, WN, false>(p, bx, by, bz, lds);
 }
 
 __global__ void __launch_bounds__(256) k_gemm_f32(GemmP p) { gemm_body(p, blockIdx.x, blockIdx.y, blockIdx.z); }
@@ -523,29 +424,33 @@ __global__ void __launch_bounds__(256) k_gemm2_f32(GemmP p)
 #define GEMM_MAXP 16
 struct GemmGroup {
     int n;
-    int h16;                    // 1: problems run on the 16-bit MFMA variant
     int shape;                  // k_gemm_f32_grouped_linear: 0 = 64x64 tiles (2x2 waves), 1 = 128x32 tiles (4x1 waves)
     int tile_start[GEMM_MAXP + 1];
     GemmP prob[GEMM_MAXP];
 };
-
-__global__ void __launch_bounds__(256) k_gemm_f32_grouped(const GemmGroup *__restrict__ g)
+// the problem that work-group `bid` of a grouped launch belongs to; local: its index among that problem's tiles
+__device__ __forceinline__ GemmP group_problem(const GemmGroup *g, int bid, int &local)
 {
-    const int bid = blockIdx.x;
     int pi = 0;
     while (pi + 1 < g->n && bid >= g->tile_start[pi + 1]) ++pi;
     const GemmP p = g->prob[pi];
-    const int local = bid - g->tile_start[pi];
+    local = bid - g->tile_start[pi];
+    return p;
+}
+
+__global__ void __launch_bounds__(256) k_gemm_f32_grouped(const GemmGroup *__restrict__ g)
+{
+    int local;
+    const GemmP p = group_problem(g, blockIdx.x, local);
     const int tn = (p.N + GT - 1) / GT, tm = (p.M + GT - 1) / GT;
     const int bz = local / (tn * tm), rem = local - bz * tn * tm;
-    if (g->h16) gemm_body_h16(p, rem % tn, rem / tn, bz);
-    else gemm_body(p, rem % tn, rem / tn, bz);
+    gemm_body(p, rem % tn, rem / tn, bz);
 }
 
 // The same launch with one of the stem's linear layers riding along as trailing work-groups (4 output neurons each): the
 // stem and the merge are independent latency-bound chains at the head of the step, and a graph node costs ~5 us by itself.
 __global__ void __launch_bounds__(256) k_gemm_f32_grouped_linear(const GemmGroup *__restrict__ g, OrnLinearJob job, int gemm_tiles, int lin_blocks,
-                                                                 MhPackAll pack, int tile_off)
+                                                                 MhPackAll pack)
 {
     ORN_PRIO_HIGH();
     // one dynamic array for every role of the launch, sized for the launch's tile shape: the static 60 KB of the larger
@@ -567,11 +472,8 @@ __global__ void __launch_bounds__(256) k_gemm_f32_grouped_linear(const GemmGroup
             orn_linear_silu_wave(job, ((blockIdx.x - gemm_tiles) * G2_LIN_ROUNDS + r) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
         return;
     }
-    const int bid = blockIdx.x + tile_off;            // (tile_off != 0: probe only, a launch of part of the tiles)
-    int pi = 0;
-    while (pi + 1 < g->n && bid >= g->tile_start[pi + 1]) ++pi;
-    const GemmP p = g->prob[pi];
-    const int local = bid - g->tile_start[pi];
+    int local;
+    const GemmP p = group_problem(g, blockIdx.x, local);
     if (g->shape == 1) {
         const int tn = (p.N + 31) / 32, tm = (p.M + 127) / 128;
         const int bz = local / (tn * tm), rem = local - bz * tn * tm;
@@ -588,16 +490,14 @@ static void finish_gemm(GemmP &p)
     p.a_kfast = (labs(p.sak) <= labs(p.sam)) ? 1 : 0;
     p.b_nfast = (labs(p.sbn) <= labs(p.sbk)) ? 1 : 0;
     p.a_vec = p.sak == 1 ? 1 : 0;          // gemm_body2: A rows contiguous in k -> 16-byte buffer loads (4-byte alignment is enough)
-    p.b_vec = p.sbn == 1 ? 1 : 0;
 }
 
 static int launch_gemm(GemmP p, int batch, hipStream_t st, const char *name)
 {
     finish_gemm(p);
-    static const bool old_body = orn_probe_env("ORN_MERGE_OLD_BODY") != nullptr;      // probe switch (tools/probes/merge_probe.py)
-    if (p.sbn == 1 && !old_body) hipLaunchKernelGGL(k_gemm2_f32, dim3(orn_cdiv(p.N, GT), orn_cdiv(p.M, GT), batch), dim3(256), 0, st, p);
-    else
-    hipLaunchKernelGGL(k_gemm_f32, dim3(orn_cdiv(p.N, GT), orn_cdiv(p.M, GT), batch), dim3(256), 0, st, p);
+    const dim3 grid(orn_cdiv(p.N, GT), orn_cdiv(p.M, GT), batch);
+    if (p.sbn == 1) hipLaunchKernelGGL(k_gemm2_f32, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_gemm_f32, grid, dim3(256), 0, st, p);
     ORN_LAUNCH_CHECK(name);
     return 0;
 }
@@ -868,10 +768,14 @@ static void group_add(GemmGroup &g, GemmP p, int batch)
 
 size_t orn_merge_group_bytes() { return orn_align(4 * sizeof(GemmGroup)); }
 
-// Builds the four device-resident problem tables (host side, at engine creation; synchronous copy).
-int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *L, int bwd_h16)
+// Builds the device-resident problem tables (host side, at engine creation; synchronous copy): 0 = T and 1 = S, the forward
+// merge; with fp32_bwd also 2 = {dW3, dT} and 3 = {dW2, dW1 partials}, the fp32 engine's merge backward (the 16-bit modes run
+// orn_launch_merge_h16_bwd instead).  tiles[q]: work-groups of table q's launch (0 for a table that was not built) -- counted
+// by group_add, the one place that knows the tile shapes, from which the kernels decode them.
+int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *L, bool fp32_bwd, int tiles[4])
 {
     ORN_REQUIRE(2 * n_layers <= GEMM_MAXP, "merge groups: too many layers");
+    const int n_tab = fp32_bwd ? 4 : 2;
     GemmGroup *h = new GemmGroup[4]();
     h[0].shape = 1;             // T products: N = C columns -> 128x32 tiles
     // Dispatch order of the S products.  The launch has a few more work-groups than the chip has CUs (720p: 320), all resident
@@ -906,34 +810,17 @@ int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *
     for (int i = 0; i < n_layers; ++i) {
         const OrnMergeLayer &l = L[i];
         group_add(h[0], l.w2t ? prob_T_tapmajor(l.w1, l.w2t, l.C, l.O, l.T) : prob_T(l.w1, l.w2, l.C, l.O, l.T), 9);
-        // gradient operands (dWf, dT ~ 1e-6) are scaled by 2^14 when rounded to half; weights are not
-        const float GS = 16384.0f;
-        GemmP q;
-        q = prob_dW3(l.g, l.T, l.C, l.O, l.dw3);   q.sa = GS;   q.sb = 1.0f; q.so = 1.0f / GS; group_add(h[2], q, 1);
-        q = prob_dT(l.g, l.w3, l.C, l.O, l.dT);    q.sa = 1.0f; q.sb = GS;   q.so = 1.0f / GS; group_add(h[2], q, 1);
-        q = prob_dW2(l.dT, l.w1, l.C, l.O, l.dw2); q.sa = GS;   q.sb = 1.0f; q.so = 1.0f / GS; group_add(h[3], q, 9);
-        q = prob_dW1p(l.w2, l.dT, l.C, l.O, l.dw1p); q.sa = 1.0f; q.sb = GS; q.so = 1.0f / GS; group_add(h[3], q, 9);
+        if (!fp32_bwd) continue;
+        group_add(h[2], prob_dW3(l.g, l.T, l.C, l.O, l.dw3), 1);
+        group_add(h[2], prob_dT(l.g, l.w3, l.C, l.O, l.dT), 1);
+        group_add(h[3], prob_dW2(l.dT, l.w1, l.C, l.O, l.dw2), 9);
+        group_add(h[3], prob_dW1p(l.w2, l.dT, l.C, l.O, l.dw1p), 9);
     }
-    h[2].h16 = h[3].h16 = bwd_h16 ? 1 : 0;
-    hipError_t e = hipMemcpy(dev_tables, h, 4 * sizeof(GemmGroup), hipMemcpyHostToDevice);
+    for (int q = 0; q < 4; ++q) tiles[q] = h[q].tile_start[h[q].n];
+    hipError_t e = hipMemcpy(dev_tables, h, n_tab * sizeof(GemmGroup), hipMemcpyHostToDevice);
     delete[] h;
     if (e != hipSuccess) { orn_set_error("merge groups: hipMemcpy failed: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
-}
-
-int orn_merge_group_tiles(int which, int n_layers, const OrnMergeLayer *L)
-{
-    int t = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const int C = L[i].C, O = L[i].O, n = C * 9, K2 = 2 * C;
-        switch (which) {
-        case 0: t += orn_cdiv(C, 32) * orn_cdiv(O, 128) * 9; break;
-        case 1: t += orn_cdiv(n, GT) * orn_cdiv(O, GT); break;
-        case 2: t += orn_cdiv(O, GT) * orn_cdiv(O, GT) + orn_cdiv(n, GT) * orn_cdiv(O, GT); break;
-        default: t += orn_cdiv(K2, GT) * orn_cdiv(O, GT) * 9 + orn_cdiv(C, GT) * orn_cdiv(K2, GT) * 9; break;
-        }
-    }
-    return t;
 }
 
 int orn_launch_merge_group(const void *dev_tables, int which, int tiles, hipStream_t st)
@@ -949,62 +836,22 @@ int orn_launch_merge_group_linear(const void *dev_tables, int which, int tiles, 
                                   int pack_blocks)
 {
     const GemmGroup *g = (const GemmGroup *)dev_tables + which;
-    int lin_blocks = orn_cdiv(job.N, 4 * G2_LIN_ROUNDS);
+    const int lin_blocks = orn_cdiv(job.N, 4 * G2_LIN_ROUNDS);
     const size_t smem = G2_LDS_BYTES(which == 0 ? 1 : 0) > 64 * 65 * 4 ? G2_LDS_BYTES(which == 0 ? 1 : 0) : 64 * 65 * 4;
     MhPackAll pk = {};
     if (pack && pack_blocks > 0) pk = *(const MhPackAll *)pack; else pack_blocks = 0;
-#ifdef ORN_PROBE_BUILD      // diagnostic builds only (ORN_BUILD_TAG + ORN_EXTRA_DEFS=-DORN_PROBE_BUILD): timing switch, results WRONG
-    static const int dbg = orn_probe_env_int("ORN_MERGE_DBG", 0);
-#else
-    constexpr int dbg = 0;
-#endif
-    if (dbg & 1) pack_blocks = 0;
-    if (dbg & 2) lin_blocks = 0;
-    if (dbg & 4) {                                    // one launch per problem: their durations inside a real step (rocprofv3 timeline)
-        GemmGroup hg;
-        if (hipMemcpy(&hg, g, sizeof(hg), hipMemcpyDeviceToHost) != hipSuccess) return ORN_E_ARG;
-        for (int i = 0; i < hg.n; ++i) {
-            const int nt = hg.tile_start[i + 1] - hg.tile_start[i];
-            hipLaunchKernelGGL(k_gemm_f32_grouped_linear, dim3(nt), dim3(256), smem, st, g, job, nt, 0, pk, hg.tile_start[i]);
-        }
-        ORN_LAUNCH_CHECK("merge_group_linear(dbg)");
-        return 0;
-    }
-    hipLaunchKernelGGL(k_gemm_f32_grouped_linear, dim3(tiles + lin_blocks + pack_blocks), dim3(256), smem, st, g, job, tiles, lin_blocks, pk, 0);
+    hipLaunchKernelGGL(k_gemm_f32_grouped_linear, dim3(tiles + lin_blocks + pack_blocks), dim3(256), smem, st, g, job, tiles, lin_blocks, pk);
     ORN_LAUNCH_CHECK("merge_group_linear");
     return 0;
 }
 
-int orn_launch_merge_bias(const float *b3x3, const float *b1x3, const float *b3x1, int O, float *bf, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_bias3, dim3(orn_cdiv(O, 256)), dim3(256), 0, st, b3x3, b1x3, b3x1, O, bf);
-    ORN_LAUNCH_CHECK("merge_bias");
-    return 0;
-}
-
-int orn_launch_merge_bwd_tail(const float *g, const float *dbf, int C, int O, float *d3x3, float *db3x3, float *d3x1,
-                              float *db3x1, float *d1x3, float *db1x3, const float *dw1p, float *dw1, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_merge_bwd_slices, dim3(orn_cdiv((long)O * C, 256)), dim3(256), 0, st, g, dbf, (long)O * C, O, d3x3,
-                       db3x3, d3x1, db3x1, d1x3, db1x3);
-    ORN_LAUNCH_CHECK("merge_bwd_slices");
-    return orn_launch_reduce_rows(dw1p, 9, (size_t)2 * C * C, (size_t)2 * C * C, dw1, st);
-}
-
 // ------------------------------------------------------------------------------------------------
-// Per-layer elementwise tails of the merge, all layers in one launch each (blockIdx.y = layer).
+// Per-layer elementwise tail of the merge backward, all layers in one launch (blockIdx.y = layer).
 // ------------------------------------------------------------------------------------------------
 struct MiscLayers {
     int n;
     OrnMergeMisc l[ORN_MAX_LAYERS];
 };
-
-__global__ void k_merge_bias_all(MiscLayers m)
-{
-    const OrnMergeMisc &l = m.l[blockIdx.y];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < l.O) l.bf[i] = l.b3x3[i] + (l.b1x3[i] + l.b3x1[i]);     // model.py:476,496
-}
 
 // slices of dWf into the 1x3 / 3x1 branches, bias fan-out, and dW1 = fixed-order sum of its 9 partials
 __global__ void k_merge_bwd_tail_all(MiscLayers m)
@@ -1043,17 +890,6 @@ __global__ void k_merge_bwd_tail_all(MiscLayers m)
             for (int k = 0; k < 9; ++k) l.dw2[j * 9 + k] = v[k];
         }
     }
-}
-
-int orn_launch_merge_bias_all(int n, const OrnMergeMisc *L, hipStream_t st)
-{
-    MiscLayers m;
-    m.n = n;
-    int maxO = 0;
-    for (int i = 0; i < n; ++i) { m.l[i] = L[i]; if (L[i].O > maxO) maxO = L[i].O; }
-    hipLaunchKernelGGL(k_merge_bias_all, dim3(orn_cdiv(maxO, 256), n), dim3(256), 0, st, m);
-    ORN_LAUNCH_CHECK("merge_bias_all");
-    return 0;
 }
 
 int orn_launch_merge_bwd_tail_all(int n, const OrnMergeMisc *L, hipStream_t st)

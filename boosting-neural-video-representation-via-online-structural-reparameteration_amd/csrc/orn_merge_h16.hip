@@ -262,7 +262,7 @@ int orn_merge_h16_build(void *dev_tables, void *host, int n_layers, const OrnMer
     return 0;
 }
 
-// the forward riders: the pack table and the block counts of its parameter-side jobs (k_merge_prep) and of T -> Th
+// the forward riders: the pack table and the block counts of its parameter-side jobs (riders of k_w2_transpose) and of T -> Th
 const void *orn_merge_h16_pack(const void *host, int *par_blocks, int *t_blocks)
 {
     const OrnMergeH16 *H = (const OrnMergeH16 *)host;

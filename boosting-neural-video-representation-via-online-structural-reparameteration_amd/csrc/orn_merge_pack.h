@@ -1,6 +1,6 @@
 // Half (IEEE fp16), K-contiguous operand copies for the merge backward of the 16-bit engine modes (orn_merge_h16.hip).
 // Where the jobs run (round 3): the ones that read only parameters -- W1 -> W1h, W3 -> W3T, W2 -> W2p -- trail the first
-// launch of the forward merge (k_merge_prep, orn_merge.hip: a lean kernel, five work-groups per CU); T -> Th trails the first
+// launch of the forward merge (k_w2_transpose, orn_merge.hip: a lean kernel, five work-groups per CU); T -> Th trails the first
 // block's forward launch (orn_stage0.hip) or, without that launch, the merge's S launch; the two that read the gradient G
 // stay a launch of their own in the backward.  (Rounds 1-2 put all four forward jobs behind the S launch: its GEMM tiles
 // hold 229 VGPRs, every work-group of a launch is charged the same, so ~1,500 short riders queued two per CU: +19 us.)

@@ -555,6 +555,50 @@ def test_engine_merge_is_bit_exact(orn):
         assert torch.equal(bf_e, bf_o), li
 
 
+def test_engine_fp32_merge_bwd_elementwise(orn):
+    """The fp32 engine's grouped merge backward (k_gemm_f32_grouped: dW3 & dT in one launch, dW2 & the dW1 partials in the next,
+    then the tail kernel), element by element.  One step at lr 0 of the small `narrow_first` engine, whose ERB blocks have the 720p
+    shapes (C, O) = (26, 650), (26, 384), (96, 384), (96, 384): K = 650 (ten 64-deep chunks and a tail of 10), K = 234, ragged
+    tiles in N (26, 52) and in M (650).  Per block, dWf and dbf are read from the engine's gradient arena; the gradients of the
+    other seven ERB tensors must equal cpu_ref.erb_merge_backward_closed_form of those (float64) within rtol 1e-4 and
+    atol 1e-5 max|ref| per tensor -- the tolerances of test_merge_bwd_real_shapes_vs_oracle, with atol relative to the tensor's
+    own maximum because the gradients of a real step are ~1e-6.
+    Worst |diff| / (atol + rtol |ref|) measured on an MI355X: 5.04e-2 (dW1 of block 0; dW2 and dW3 1.9e-2 .. 3.4e-2) before
+    gemm_body lost its unreachable epilogue and its 16-bit twin, and the same 5.04e-2 after, every per-tensor figure equal; the
+    slices and bias copies are exact (0).  With the last K chunk of gemm_body skipped (a planted fault) the test fails at the
+    first GEMM output it checks: dW1 of block 0 (K = 650), ratio 1.3e4, 1350 of 1352 elements out of tolerance."""
+    from helpers import small_engine
+    from oracle import cpu_ref
+    eng = small_engine(orn, 'fp32', 'ERB', 'narrow_first')
+    eng.set_schedule([(1, 1, 0.0)])
+    eng.run(1)
+    torch.cuda.synchronize()
+    s = eng.scale_state()
+    assert s['skipped'] == 0 and s['late_skipped'] == 0, s
+    P, G = eng.params.cpu(), eng.grads.cpu()
+    shapes = {k: p.shape for k, p in eng.model.named_parameters()}
+
+    def slot(arena, i, key):
+        name = f'layers.{i}.{key}'
+        off, n = eng.layout[name]
+        return arena[off:off + n].view(shapes[name])
+    worst = 0.0
+    for i in range(len(eng.model.layers)):
+        ref = cpu_ref.erb_merge_backward_closed_form(slot(G, i, ERB_KEYS[0]).double(), slot(G, i, ERB_KEYS[1]).double(),
+                                                     slot(P, i, ERB_KEYS[6]).double(), slot(P, i, ERB_KEYS[7]).double(),
+                                                     slot(P, i, ERB_KEYS[8]).double())
+        for k in ERB_KEYS[2:]:
+            r = ref[k].float().numpy()
+            got = slot(G, i, k).numpy()
+            assert np.abs(r).max() > 0, (i, k)
+            atol = 1e-5 * np.abs(r).max()
+            ratio = float((np.abs(got - r) / (atol + 1e-4 * np.abs(r))).max())
+            worst = max(worst, ratio)
+            print(f'RATIO layer {i} {k} {ratio:.3e}')
+            np.testing.assert_allclose(got, r, rtol=1e-4, atol=atol, err_msg=f'layer {i} {k}')
+    print(f'RATIO worst {worst:.3e}')
+
+
 def test_deploy_checkpoint_round_trip(orn, golden, tmp_path):
     """N1: a reference *_deploy.pth decodes frame-for-frame; our deploy export of a trained ERB model
     equals the reference's switch_to_deploy result and decodes identically through the engine's decode path."""
