@@ -11,12 +11,6 @@
 
 // ---- error plumbing --------------------------------------------------------------------------
 void orn_set_error(const char *fmt, ...);
-// Kernel-form switches of tools/probes (A/B runs) and of the tests that pin the non-default forms.  Every one that is SET is
-// reported on stderr the first time it is read ("liborn: probe switch ORN_X=.. is active"), so a stray environment variable can
-// not silently change what a fit runs.  None of them makes results wrong; the timing ablations that do are compile-time
-// definitions of diagnostic builds (ORN_CONV_ABLATE, G2_ABL), never environment switches.
-const char *orn_probe_env(const char *name);
-int orn_probe_env_int(const char *name, int dflt);
 
 #define ORN_REQUIRE(cond, ...)                         \
     do {                                               \

@@ -12,9 +12,7 @@
 //   tiles); K stream = chunks x 9 taps, one k-step (24 MFMAs per wave) per (chunk, tap), epilogue at the end.
 //     dgrad:   Cin / 32 chunks (Cin = the layer's conv output channels);
 //     forward: one 96-channel N tile = 3 chunks (K = 9 x 96) per work-group; the O / 96 work-groups of a pixel tile follow each
-//              other on one XCD.  With 96 channels per output pixel (Cn == 96) an N tile is ALL channels of one output
-//              sub-position, so the last block's epilogue CAN also run the A5 head (1x1 conv 96 -> 3 + activation) on them
-//              (ORN_HEAD_FUSED=1; measured slower than the separate HBM-bound head kernel, see orn_launch_fwd2).
+//              other on one XCD.
 //   Pipeline per step u: fragment reads of u+1 (other register set) | counted lgkmcnt wait for u | counted vmcnt wait + rendezvous
 //   | 24 MFMAs | DMA of weight tile u+4 into the slot of tile u | (taps 0..5) one DMA piece of the NEXT chunk's patch.
 //   What is known to have landed after rendezvous v: weight tiles <= v+2 and the patch pieces issued up to step v-2, because the
@@ -62,10 +60,6 @@ struct Conv2P {
     int s, Cn, Nout;
     unsigned z_bytes, apad_bytes;   // sizes of the two buffers (raw-buffer bounds)
     unsigned mCn, mS;
-    // A5 head in the last block's epilogue (C2_FWD_LAST, Cn == 96: an N tile is all channels of one output sub-position)
-    const float *head_w, *head_b;   // [3][96], [3]
-    float *head_out;                // fp32 [3][H*s][W*s], or null: no head
-    int head_sigmoid;
 };
 
 // Fragment reads of step (tap TAP) into set SET: 4 pixel sub-blocks (rows 2w + {0,1} + ti, two 16-pixel halves) and 6 channel
@@ -198,10 +192,6 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
     float *sbias = reinterpret_cast<float *>(smem + C2_LDS);
     if (EPI != C2_DGRAD)
         for (int i = t; i < 96; i += 256) sbias[i] = p.bias ? p.bias[seg0 * 96 + i] : 0.f;
-    float *shead = sbias + 96;                    // [3][96] head weights + [3] biases (+ pad)
-    const bool head = (EPI == C2_FWD_LAST) && p.head_out != nullptr;
-    if (EPI == C2_FWD_LAST && head)
-        for (int i = t; i < 3 * 96 + 3; i += 256) shead[i] = i < 3 * 96 ? p.head_w[i] : p.head_b[i - 3 * 96];
     // z / apad as raw buffers: a byte offset of 0x80000000 (out of range for any buffer the launcher admits) drops the lane's
     // store, so every lane issues every store and the number of vector-memory operations of an epilogue is a constant
     const auto z_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.z, 0, EPI != C2_DGRAD ? p.z_bytes : 0, 0x00020000);
@@ -276,9 +266,6 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
         // ---- forward epilogue: + bias, PixelShuffle scatter of z (and of a = SiLU(z) into the next block's
         // padded input), 8 channels = 16 B per lane and store -------------------------------------------------------------
         const int n0 = seg0 * 96;
-        float hu[4][3];                               // head: this lane's partial W . SiLU(z) of its 4 pixels
-#pragma unroll
-        for (int pi = 0; pi < 4; ++pi) hu[pi][0] = hu[pi][1] = hu[pi][2] = 0.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int c8 = n0 + j * 32 + c8_lane;
@@ -286,16 +273,6 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
             const float4 bb = *reinterpret_cast<const float4 *>(sbias + j * 32 + c8_lane + 4);
             const int ij = conv_div(c8, p.mCn), n = c8 - ij * p.Cn;
             const int si = conv_div(ij, p.mS), sj = ij - si * p.s;
-            float hw[3][8];
-            if (EPI == C2_FWD_LAST && head) {
-#pragma unroll
-                for (int o = 0; o < 3; ++o) {
-                    const float4 w0 = *reinterpret_cast<const float4 *>(shead + o * 96 + j * 32 + c8_lane);
-                    const float4 w1 = *reinterpret_cast<const float4 *>(shead + o * 96 + j * 32 + c8_lane + 4);
-                    hw[o][0] = w0.x; hw[o][1] = w0.y; hw[o][2] = w0.z; hw[o][3] = w0.w;
-                    hw[o][4] = w1.x; hw[o][5] = w1.y; hw[o][6] = w1.z; hw[o][7] = w1.w;
-                }
-            }
 #pragma unroll
             for (int pi = 0; pi < 4; ++pi) {
                 const int gh = h0 + 2 * uwave + (pi >> 1), gw = w0 + 16 * (pi & 1) + l15;
@@ -318,38 +295,6 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
                     for (int e = 0; e < 8; ++e) v[e] = orn_silu(v[e]);
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack_h16x2(v[0], v[1]), pack_h16x2(v[2], v[3]), pack_h16x2(v[4], v[5]), pack_h16x2(v[6], v[7])}, a_rsrc,
                                                            ok ? (((oh + 1) * (Ws + 2) + (ow + 1)) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);
-                }
-                if (EPI == C2_FWD_LAST && head) {
-                    // on the 16-bit z that was just stored: what the separate head kernel reads back, and what the backward uses
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float a = orn_silu((float)(h16)v[e]);
-                        hu[pi][0] = fmaf(hw[0][e], a, hu[pi][0]);
-                        hu[pi][1] = fmaf(hw[1][e], a, hu[pi][1]);
-                        hu[pi][2] = fmaf(hw[2][e], a, hu[pi][2]);
-                    }
-                }
-            }
-        }
-        if (EPI == C2_FWD_LAST && head) {
-            // the four lanes l15 + 16 g of a pixel hold 24 channels each: sum them, lane g < 3 stores output channel g
-            const int ij = conv_div(n0, p.mCn), si = conv_div(ij, p.mS), sj = ij - si * p.s;
-            const size_t HWs = (size_t)(H * p.s) * (W * p.s);
-#pragma unroll
-            for (int pi = 0; pi < 4; ++pi) {
-                const int gh = h0 + 2 * uwave + (pi >> 1), gw = w0 + 16 * (pi & 1) + l15;
-                float u = 0.f;
-#pragma unroll
-                for (int o = 0; o < 3; ++o) {
-                    float x = hu[pi][o];
-                    x += __shfl_xor(x, 16, 64);
-                    x += __shfl_xor(x, 32, 64);
-                    if (g4 == o) u = x;
-                }
-                if (g4 < 3 && gh < H && gw < W) {
-                    u += shead[3 * 96 + g4];
-                    const int oh = gh * p.s + si, ow = gw * p.s + sj;
-                    p.head_out[(size_t)g4 * HWs + (size_t)oh * (W * p.s) + ow] = p.head_sigmoid ? 1.0f / (1.0f + __expf(-u)) : (tanhf(u) + 1.0f) * 0.5f;
                 }
             }
         }
@@ -431,7 +376,7 @@ int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, cons
 
 // forward of a block with 96 input channels and O % 96 == 0 output channels.  Returns -1 without launching when the shape is
 // not this form's (the caller falls back to the first form).
-int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st, OrnHeadFuse *head)
+int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st)
 {
     if (O % 96 != 0 || O > 2048) return -1;
     Conv2P p = {};
@@ -448,16 +393,8 @@ int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, 
     p.z_bytes = (unsigned)((size_t)(H * s) * (W * s) * p.Cn * 2);
     p.apad_bytes = apad ? (unsigned)((size_t)(H * s + 2) * (W * s + 2) * p.Cn * 2) : 0;
     p.mCn = conv_magic(p.Cn); p.mS = conv_magic(s);
-    // The head in this epilogue is correct (tests run it with ORN_HEAD_FUSED=1) but does not pay: 96 SiLUs + 288 FMAs per lane on
-    // the vector pipe cost the last block 145 -> 190 us, the 42 us HBM-bound head kernel it replaces included -- and the denser
-    // launch drags the clock of its neighbours down (720p step 1.168 -> 1.188 ms on one box).  Off unless asked for.
-    static const bool fuse_head = orn_probe_env("ORN_HEAD_FUSED") != nullptr;
-    if (head && !apad && p.Cn == 96 && fuse_head) {
-        p.head_w = head->w; p.head_b = head->b; p.head_out = head->out; p.head_sigmoid = head->sigmoid;
-        head->fused = 1;
-    }
     const int blocks = orn_cdiv(p.ptiles, 8) * 8 * p.nsplit;
-    const size_t lds = C2_LDS + 96 * 4 + (p.head_out ? (3 * 96 + 4) * 4 : 0);
+    const size_t lds = C2_LDS + 96 * 4;
     return apad ? c2_launch<C2_FWD>(p, blocks, lds, st, "fwd2_nhwc") : c2_launch<C2_FWD_LAST>(p, blocks, lds, st, "fwd2_nhwc_last");
 }
 

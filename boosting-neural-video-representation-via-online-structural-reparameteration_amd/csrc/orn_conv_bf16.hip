@@ -1,7 +1,7 @@
 // A4 fast path, DGRAD of the NeRVBlock conv (model.py:539,567), first form: one work-group per CU on v_mfma_f32_16x16x32
 // (fp32 accumulate), for the layers that carry 99 % of the step's FLOPs (96 input channels of the forward conv).  Large images
 // with a fused epilogue take the two-work-groups-per-CU family instead (orn_conv2_bf16.hip); this kernel serves the small
-// images (chunk-split into fp32 slabs + k_dgrad_finish), the hand-off to an fp32 layer below and the ORN_DGRAD_FORM1 probe.
+// images (chunk-split into fp32 slabs + k_dgrad_finish) and the hand-off to an fp32 layer below.
 // Activations live in HBM as channels-last 16-bit with a one-pixel zero border:
 //
 //   xpad [H+2][W+2][C]      conv input  (= previous block's a = SiLU(z), border = conv zero padding)
@@ -31,14 +31,8 @@ struct ConvBP {
     const h16 *w;        // [9][Nout][Cin]: Wd
     int H, W, Cin, Nout;
     int tiles_w, tiles_h;
-    int qsplit;          // EPI_B_DGRAD_F32 on small images: blockIdx.y = input chunk, one fp32 partial slab per chunk
-    // EPI_B_DGRAD: out = dx * silu'(zprev) scattered into the previous layer's dypad
-    const h16 *zprev;    // [H][W][Nout]
-    h16 *dyprev;         // [H/sp+2][W/sp+2][Nout*sp*sp]
-    int sp;
-    unsigned mSp;        // conv_magic(sp) for the epilogue's index math (conv_div)
-    // EPI_B_DGRAD_F32
-    float *dx_f32;       // [H][W][Nout]
+    int qsplit;          // small images: blockIdx.y = input chunk, one fp32 partial slab per chunk
+    float *dx_f32;       // [H][W][Nout] (x one slab per chunk when chunk-split)
     int dbg;             // timing-only ablation flags (tools/probes): 1 no weight restage, 2 no patch stage, 4 no stores
     unsigned long long *stamps;   // -DORN_CONV_STAMP diagnostic builds only: 64 time stamps per work-group (tools/probes/conv_stamps.py)
 };
@@ -108,14 +102,15 @@ __device__ __forceinline__ void conv_mfma_step(h16x8 (&fa)[NSET][2 * MB], h16x8 
 }
 
 // One work-group: 8 x 32 pixels of dx, all BN = WAVES_N * NB * 32 channels of it (the whole N in ONE tile: 96, or 32 for the
-// all-taps form), walking the conv output's channels in chunks of CK = 96 (always: the parameter keeps the kernel's name).
+// all-taps form), walking the conv output's channels in chunks of CK = 96 and writing fp32 slabs (EPI_B_DGRAD_F32) -- always:
+// the two parameters keep the kernel's name, which the benchmark's roofline table prints.
 // ALLTAPS: all nine weight tiles of the (single) K chunk resident, one rendezvous -- the chunk-split dgrad of a layer with
 // <= 32 real OUTPUT channels (N tile 32: 9 x 6 KB next to the 64 KB patch).
 template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK)>
 __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_nhwc_bf16(ConvBP p)
 {
     ORN_PRIO_HIGH();
-    static_assert(!EPI_IS_FWD(EPI) && CK == CB_CK, "this file holds the dgrad kernels (forward: orn_conv_fwd_bf16.hip)");
+    static_assert(EPI == EPI_B_DGRAD_F32 && CK == CB_CK, "this file holds the dgrad kernels (forward: orn_conv_fwd_bf16.hip)");
     constexpr int NCH = CK / 8;                        // 16-byte chunks per LDS row
     constexpr int NBUF = ALLTAPS ? 9 : 3;              // weight tiles resident at once
     constexpr int NT = WAVES_M * WAVES_N * 64;
@@ -150,10 +145,10 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_nhwc_bf16(ConvBP
     const int tw = tile % p.tiles_w, th = tile / p.tiles_w;
     const int h0 = th * CB_TH, w0 = tw * CB_TW;
     const int H = p.H, W = p.W, Cin = p.Cin;
-    const int q_base = (EPI == EPI_B_DGRAD_F32 && p.qsplit) ? (int)blockIdx.y : 0;   // chunk split: this WG's chunk
+    const int q_base = p.qsplit ? (int)blockIdx.y : 0;   // chunk split: this WG's chunk
     // chunks of the input channels walked by one work-group (the all-taps-resident form is launched chunk-split: one)
     constexpr bool MULTI_CHUNK = !ALLTAPS;
-    const int Q = (!MULTI_CHUNK || (EPI == EPI_B_DGRAD_F32 && p.qsplit)) ? 1 : Cin / CB_CK;
+    const int Q = (!MULTI_CHUNK || p.qsplit) ? 1 : Cin / CB_CK;
     const int n_tiles = Q * 9;                         // weight tiles per N tile
 
     const int uwave = __builtin_amdgcn_readfirstlane(wave);        // provably wave-uniform (LDS-DMA base -> M0)
@@ -323,18 +318,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_nhwc_bf16(ConvBP
                     swap_rows_f(x0, x1);
                     v[e] = x0; v[4 + e] = x1;
                 }
-                if (EPI == EPI_B_DGRAD) {
-                    if (ok) {
-                        const h16x8 zz = *reinterpret_cast<const h16x8 *>(p.zprev + ((size_t)gh * W + gw) * p.Nout + c8);
-                        h16x8 o8;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) o8[e] = (h16)(v[e] * orn_silu_grad((float)zz[e]));
-                        const int sp = p.sp, ph = conv_div(gh, p.mSp), pw = conv_div(gw, p.mSp);
-                        const int sub = (gh - ph * sp) * sp + (gw - pw * sp);
-                        *reinterpret_cast<h16x8 *>(p.dyprev + ((size_t)(ph + 1) * (W / sp + 2) + (pw + 1)) * (p.Nout * sp * sp) +
-                                                   sub * p.Nout + c8) = o8;
-                    }
-                } else if (ok) {
+                if (ok) {
                     float *dst = p.dx_f32 + (size_t)q_base * H * W * p.Nout + ((size_t)gh * W + gw) * p.Nout + c8;
                     *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
                     *reinterpret_cast<float4 *>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
@@ -390,7 +374,7 @@ int orn_dgrad_f32_slabs(int H, int W, int O)
 
 // Small images (too few pixel tiles to fill the chip): the dgrad runs split over the input chunks into fp32 partial
 // slabs [Q][H][W][96]; this pass sums them (fixed order), applies SiLU'(z_prev) and scatters into the previous layer's
-// dypad -- what the EPI_B_DGRAD epilogue does in one go on large images.
+// dypad -- what the dgrad epilogue of orn_conv2_bf16.hip does in one go on large images.
 __global__ void __launch_bounds__(256) k_dgrad_finish(const float *__restrict__ slabs, int Q, const h16 *__restrict__ zprev, int H, int W,
                                                      int sp, h16 *__restrict__ dyprev)
 {
@@ -429,23 +413,19 @@ int orn_launch_conv_bf16_dgrad(const h16 *dypad, const h16 *wd, int H, int W, in
 #endif
     p.xpad = dypad; p.w = wd; p.H = H; p.W = W; p.Cin = O; p.Nout = C;
     p.tiles_w = orn_cdiv(W, CB_TW); p.tiles_h = orn_cdiv(H, CB_TH);
-    p.zprev = zprev; p.dyprev = dyprev; p.sp = sp; p.dx_f32 = dx_f32;
+    p.dx_f32 = dx_f32;
     ORN_REQUIRE(H < 65536 && W < 65536 && sp >= 1 && sp < 65536, "conv_bf16_dgrad: sizes exceed the epilogue's index math");
-    p.mSp = conv_magic(sp);
     if (dx_f32) {
         p.qsplit = (p.tiles_w * p.tiles_h < 128 && O / CB_CK > 1) ? 1 : 0;   // few pixel tiles: one work-group per input chunk
         if (!zprev && p.qsplit && c_real > 0 && c_real <= 32) return launch_conv_cfg<8, 1, 1, 1, EPI_B_DGRAD_F32, CB_CK, true>(p, st);
         if (!zprev) return launch_conv_cfg<8, 1, 1, 3, EPI_B_DGRAD_F32>(p, st);
         ORN_REQUIRE(dyprev && sp >= 1 && H % sp == 0 && W % sp == 0 && p.qsplit, "conv_bf16_dgrad: bad split-epilogue arguments");
-        p.zprev = nullptr; p.dyprev = nullptr;
         ORN_TRY((launch_conv_cfg<8, 1, 1, 3, EPI_B_DGRAD_F32>(p, st)));
         hipLaunchKernelGGL(k_dgrad_finish, dim3(orn_cdiv((long)H * W * 12, 256)), dim3(256), 0, st, dx_f32, O / CB_CK, zprev, H, W, sp, dyprev);
         ORN_LAUNCH_CHECK("dgrad_finish");
         return 0;
     }
     ORN_REQUIRE(zprev && dyprev && sp >= 1 && H % sp == 0 && W % sp == 0, "conv_bf16_dgrad: bad epilogue arguments");
-    static const bool form1 = orn_probe_env("ORN_DGRAD_FORM1") != nullptr;       // tools/probes: A/B against the one-work-group-per-CU form
-    if (form1) return launch_conv_cfg<8, 1, 1, 3, EPI_B_DGRAD>(p, st);
     // (Round 3 also built the block's own wgrad riding behind these dgrad tiles in one launch: the two combined launches took 17 us
     // less than the launches they replaced, the STEP 13 us more -- DESIGN 4.5; removed in round 4.)
     return orn_launch_dgrad2(dypad, wd, H, W, O, zprev, dyprev, sp, st);       // two work-groups per CU: orn_conv2_bf16.hip

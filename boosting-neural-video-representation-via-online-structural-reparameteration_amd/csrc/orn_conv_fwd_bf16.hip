@@ -397,7 +397,7 @@ void set_debug_fwd(int flags) { g_convf_dbg = flags; }
 // N tile 128 (waves 4x2, wave tile 64 px x 64 ch)
 // c_real: input channels that are not zero padding (<= Cin); <= 32 of them take the narrow form (forward of a non-last block)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
-                             h16 *z, h16 *apad, hipStream_t st, int c_real, OrnHeadFuse *head)
+                             h16 *z, h16 *apad, hipStream_t st, int c_real)
 {
     // O % 32: whole MFMA blocks; an O that is not a multiple of the 128-channel N tile gets a ragged last tile whose weight
     // DMA reads up to 96 rows past row O of each tap: `wb` must be readable for 96 * Cin elements behind its last row
@@ -428,12 +428,9 @@ int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p
     // large images with whole 96-channel N tiles: the two-work-groups-per-CU form (orn_conv2_bf16.hip).  Measured in the step:
     // the last block (z only) 150 -> 140 us at 720p; blocks that also write the activation copy are neutral at 230 pixel tiles
     // (720p, 180 x 320: 74.2 vs 73.9 us for the two such launches) and gain from ~500 tiles on (1080p: 181 -> 168 us for its
-    // three), so those take it from 400 tiles (ORN_FWD2_APAD: always).
-    static const bool form1 = orn_probe_env("ORN_FWD_FORM1") != nullptr;         // tools/probes: A/B against this file's kernel
-    static const bool form2_apad = orn_probe_env("ORN_FWD2_APAD") != nullptr;
-    static const int min_tiles = orn_probe_env_int("ORN_FWD2_MINTILES", 128);
-    if (!form1 && Cin == 96 && O % 96 == 0 && ptiles >= min_tiles && (!apad || ptiles >= 400 || form2_apad)) {
-        const int rc = orn_launch_fwd2(xpad, wb, bias_p, H, W, O, s, z, apad, st, head);
+    // three), so those take it from 400 tiles.
+    if (Cin == 96 && O % 96 == 0 && ptiles >= 128 && (!apad || ptiles >= 400)) {
+        const int rc = orn_launch_fwd2(xpad, wb, bias_p, H, W, O, s, z, apad, st);
         if (rc != -1) return rc;
     }
     return apad ? launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD>(p, nt_total, st) : launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD_LAST>(p, nt_total, st);

@@ -18,19 +18,6 @@ void orn_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-const char *orn_probe_env(const char *name)
-{
-    const char *v = getenv(name);
-    if (v) fprintf(stderr, "liborn: probe switch %s=%s is active (non-default kernel form)\n", name, v);
-    return v;
-}
-
-int orn_probe_env_int(const char *name, int dflt)
-{
-    const char *v = orn_probe_env(name);
-    return v ? atoi(v) : dflt;
-}
-
 extern "C" int orn_version(void) { return ORN_VERSION; }
 
 extern "C" int orn_last_error(char *buf, size_t n)

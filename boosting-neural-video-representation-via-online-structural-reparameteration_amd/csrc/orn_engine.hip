@@ -606,7 +606,6 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
         for (int i = ff; i < ff + np; ++i) pl[i - ff] = prep_layer(e, i);
         ORN_TRY(e->ops->prep_all(np, pl, st));
     }
-    OrnHeadFuse hf = {};
     for (int i = 0; i < nl; ++i) {
         const orn_layer_desc &l = d.layer[i];
         LayerBuf &b = e->L[i];
@@ -633,21 +632,18 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
         } else {
             if (i == ff && !e->stage0) ORN_TRY(e->ops->to_nhwc(x, l.C, ORN_FAST_C, l.H, l.W, b.xpad, st));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i], st);
-            // the last block's kernel may run the head in its epilogue (it then holds every channel of an output pixel)
             const bool last = (i + 1 == nl);
             // pipelined step: the side branch of the previous step still reads the last block's input buffer (its weight gradient)
             // until ev_wgrad, and writes that block's merged kernel (and the head's parameters) until ev_join
             if (e->side_busy && i + 3 == nl && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));   // (this conv overwrites the input of the block below the last)
             if (e->side_busy && i + 2 == nl) ORN_HIP(hipStreamWaitEvent(st, e->ev_wgrad, 0));
             if (e->side_busy && last) { ORN_HIP(hipStreamWaitEvent(st, e->ev_join, 0)); e->side_busy = false; }
-            if (last) hf = OrnHeadFuse{P + d.head_w, P + d.head_b, e->img, d.sigmoid, 0};
-            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C,
-                                     last && head ? &hf : nullptr));
+            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
         }
     }
     if (ff < nl) {
-        if (!hf.fused && head)
+        if (head)
             ORN_TRY(e->ops->head_fwd(e->L[nl - 1].zb, P + d.head_w, P + d.head_b, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img, st));
     } else
     {

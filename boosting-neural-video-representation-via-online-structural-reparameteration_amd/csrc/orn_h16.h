@@ -79,7 +79,8 @@ __device__ __forceinline__ void orn_sfor(F &&f)
 
 // EPI_B_FWD_LAST: the forward of the last block (no activation copy for a next layer): its own instantiation, so the
 // largest launch of the step carries neither the second set of deferred-store registers nor the SiLU code
-enum { EPI_B_FWD = 0, EPI_B_DGRAD = 1, EPI_B_DGRAD_F32 = 2, EPI_B_FWD_LAST = 3 };
+// EPI_B_DGRAD_F32: the one epilogue of the first-form dgrad (fp32 slabs).  The values are part of the kernels' names.
+enum { EPI_B_FWD = 0, EPI_B_DGRAD_F32 = 2, EPI_B_FWD_LAST = 3 };
 #define EPI_IS_FWD(e_) ((e_) == EPI_B_FWD || (e_) == EPI_B_FWD_LAST)
 
 namespace HNS {
@@ -164,7 +165,7 @@ __device__ __forceinline__ float head_act(float a0, float a1, float a2, int sub,
 // ---- launchers and switches that one file of the path defines and another calls ------------------------------------------
 // orn_conv_fwd_bf16.hip.  c_real: input channels that are not zero padding (<= Cin)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
-                             h16 *z, h16 *apad, hipStream_t st, int c_real, OrnHeadFuse *head = nullptr);
+                             h16 *z, h16 *apad, hipStream_t st, int c_real);
 void set_debug_fwd(int flags);
 void set_stamps_fwd(void *buf);       // (-DORN_CONV_STAMP builds)
 // orn_conv_bf16.hip
@@ -172,7 +173,7 @@ int orn_dgrad_f32_slabs(int H, int W, int O);
 int orn_launch_conv_bf16_dgrad(const h16 *dypad, const h16 *wd, int H, int W, int O, int C, const h16 *zprev,
                                h16 *dyprev, int sp, float *dx_f32, hipStream_t st, int c_real);
 // orn_conv2_bf16.hip
-int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st, OrnHeadFuse *head);
+int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st);
 int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st);
 // orn_wgrad_bf16.hip
 size_t orn_wgrad_bf16_ws_floats(int H, int W, int O);

@@ -119,9 +119,6 @@ struct OrnWgradReduce { const float *slabs; int H, W, C, O, s; float gscale; flo
 // deferred reduction of the 16-bit head backward's per-block partials (head_bwd called with dw == nullptr leaves them in ws)
 struct OrnHeadFinish { const float *partial; int blocks, C; float gscale; float *dw, *db; OrnScaleState *sc; };
 struct OrnWgradJob { const void *xpad, *dypad; int H, W, C, O, s; float *slabs; int smax; };   // wgrad into slabs, reduction deferred; smax > 0: at most that many split-K slabs (the reduction must be told the same)
-// A5 head riding on the last block's forward (its epilogue holds all channels of an output pixel): out = act(W SiLU(z) + b).
-// The launcher sets `fused` when the kernel it chose did the head; otherwise the caller launches head_fwd on z.
-struct OrnHeadFuse { const float *w, *b; float *out; int sigmoid; int fused; };
 // Decode output stage (orn_decode_out.hip): what one decoded frame leaves behind.  Every output is optional (null: not wanted).
 //   rgb8 [H][W][3] bytes, q = (uint8) clamp(x*255 + 0.5, 0, 255); img [3][H][W] fp32; stats {mse, psnr} of x and of q/255 against
 //   targets[*row] ([3][H][W] fp32 each).  ws: ORN_DECODE_WS_FLOATS floats, the last of them a ticket counter that is zero
@@ -133,7 +130,7 @@ struct OrnDecodeOut { const float *targets; const int32_t *row; uint8_t *rgb8; f
 int orn_launch_decode_out_f32(const float *src, size_t HW, const OrnDecodeOut &o, hipStream_t st);
 struct OrnHalfOps {
     int (*conv_fwd)(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s, void *z, void *apad,
-                    hipStream_t st, int c_real, OrnHeadFuse *head);   // c_real <= Cin: input channels that are not zero padding; head: optional
+                    hipStream_t st, int c_real);   // c_real <= Cin: input channels that are not zero padding
     int (*conv_dgrad)(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev, void *dyprev, int sp,
                       float *dx_f32, hipStream_t st, int c_real);   // c_real: output channels that are not zero padding
     size_t (*wgrad_ws_floats)(int H, int W, int O);

@@ -152,16 +152,13 @@ int orn_wgrad_bf16_split(int H, int W, int O, int smax = 0)
     const int n_ktiles = orn_cdiv(H, WB_TH) * orn_cdiv(W, WB_TW);
     const int per = 3 * orn_cdiv(O, WB_BO);
     int S = (512 / per) / 8 * 8;
-    static const int s_env = orn_probe_env_int("ORN_WGRAD_SMAX", 0);      // tools/probes: split-K sweep
-    if (s_env > 0 && S > s_env) S = s_env;
     // measured in the 720p step: a full wave of work-groups (56 slabs) makes the slab write + re-read cost more than the idle
     // slots do -- L3 (900 K tiles): 40 slabs beat 56 by 17 us; L4 (3600 K tiles), since the DMA prefetch of the K loop works:
     // 32 / 40 / 48 / 56 slabs = 1.148 / 1.128 / 1.133 / 1.143 ms per step (reduction 30 / 35 / 38 / 45 us, wgrad 224 / 199 / 199 / 201)
     if (S > 40) S = 40;
     // layers under 2000 K tiles (720p L3: 900): 24 slabs -- the wgrad launch does not notice (all layers share it), the reduction
     // reads less: 40 / 32 / 24 = 35 / 32 / 30 us
-    static const int s_small = orn_probe_env_int("ORN_WGRAD_SMAX_SMALL", 24);   // tools/probes override
-    if (n_ktiles < 2000 && S > s_small && smax < 8) S = s_small;     // (a caller's count replaces this rule)
+    if (n_ktiles < 2000 && S > 24 && smax < 8) S = 24;     // (a caller's count replaces this rule)
     const int by_work = (n_ktiles / 8) / 8 * 8;
     if (S > by_work) S = by_work;
     if (smax >= 8 && S > smax) S = smax / 8 * 8;   // caller's cap (the engine's side branch runs the last block on fewer, longer work-groups)

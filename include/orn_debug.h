@@ -14,7 +14,7 @@ ORN_API void orn_debug_set(int flags);
 /* The 16-bit conv launchers exactly as the engine calls them, bf16 and IEEE-half builds; buffers and conventions as
  * orn_conv_nhwc_bf16_fwd / orn_dgrad_nhwc_bf16 in orn.h (same slack rules), plus the arguments the raw entry points fix:
  *   fwd:   xpad holds Cin (= 96) channels per pixel, zero above the c_real real ones; c_real <= 32 with apad != NULL takes the
- *          narrow form.  No head fusion.
+ *          narrow form.
  *   dgrad: dx_f32 alone (zprev = dyprev = NULL): fp32 output slabs [Q][H][W][C], Q = O/96 when the image has fewer than 128
  *          pixel tiles of 8 x 32 and O > 96, else 1 (their sum is dx); c_real <= 32 on a split launch writes channels [0, 32)
  *          only.  zprev, dyprev and dx_f32 together (only where Q > 1): dx_f32 is the scratch of that split, which is

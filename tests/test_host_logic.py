@@ -40,6 +40,14 @@ def test_library_exports_every_declared_symbol(orn):
     assert L.orn_engine_ws_bytes(None) == 0
 
 
+def test_library_does_not_read_the_environment(orn):
+    """The kernel forms the library launches depend on shapes alone: it imports no environment reader."""
+    import subprocess
+    out = subprocess.run(['nm', '-D', '--undefined-only', orn._lib.lib_path()], capture_output=True, text=True, check=True).stdout
+    imported = {ln.split()[-1].split('@')[0] for ln in out.splitlines() if ln.strip()}
+    assert imported and not imported & {'getenv', 'secure_getenv'}, imported & {'getenv', 'secure_getenv'}
+
+
 def test_missing_library_fails_loudly(orn, monkeypatch):
     monkeypatch.setattr(orn._lib, '_lib', None)
     monkeypatch.setattr(orn._lib, 'lib_path', lambda: '/nonexistent/liborn.so')

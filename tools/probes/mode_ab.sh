@@ -1,4 +1,4 @@
-# whole-step A/B of the launch modes (and of probe switches) on one box.  usage: mode_ab.sh ["ENV=.. --mode m" ...]; default: the three modes
+# whole-step A/B of the launch modes on one box.  usage: mode_ab.sh ["[ENV=..] --mode m" ...]; default: the three modes
 if [ $# -eq 0 ]; then set -- "--mode graph" "--mode eager" "--mode stream"; fi
 for r in 1 2; do for a in "$@"; do
   envs=""; flags=""; for w in $a; do case $w in *=*) envs="$envs $w";; *) flags="$flags $w";; esac; done
