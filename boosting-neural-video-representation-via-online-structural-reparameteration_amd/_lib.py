@@ -67,12 +67,16 @@ _SIGS = {
     'orn_loss_target_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
     'orn_msssim_ws_bytes': (c_size_t, [c_int] * 4),
     'orn_msssim': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'orn_msssim_frames_ws_bytes': (c_size_t, [c_int] * 4),
+    'orn_msssim_frames': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     'orn_adam_step': (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, P]),
     'orn_engine_ws_bytes': (c_size_t, [POINTER(EngineDesc)]),
     'orn_engine_create': (c_int, [POINTER(EngineDesc), P, P, P, P, P, c_size_t, POINTER(c_void_p)]),
     'orn_engine_destroy': (None, [P]),
     'orn_engine_decode': (c_int, [P, P, P, P]),
     'orn_engine_decode_frames': (c_int, [P, P, P, c_int32, P, P, P, P, P]),
+    'orn_engine_eval_frames_ws_bytes': (c_size_t, [POINTER(EngineDesc), c_int]),
+    'orn_engine_eval_frames': (c_int, [P, P, P, c_int32, P, P, P, P, P, P, c_size_t, P]),
     'orn_engine_train_step': (c_int, [P, P, P, P, P, P, c_int32, P]),
     'orn_engine_train_steps_graph': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
     'orn_engine_train_steps': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),

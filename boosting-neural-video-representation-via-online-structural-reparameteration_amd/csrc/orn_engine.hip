@@ -667,6 +667,35 @@ extern "C" int orn_engine_decode(orn_engine *e, const float *embed, float *img, 
 // n frames back to back: frame 0 runs the full forward (the parameters may have changed since the last call), the others reuse
 // its merged kernels and operand copies (MERGE_NONE); each ends in the decode output stage (orn_decode_out.hip) instead of
 // head + copy (+ the caller's torch ops for bytes and PSNR).  main_eval.py:795-815, main_train.py:377-438.
+// msssim (orn_engine_eval_frames): after every `chunk` decoded frames, the batched MS-SSIM launches (orn_loss.hip) on the chunk's
+// fp32 planes -- the caller's img, or slots at the head of `ws` that the output kernel fills through its img output.
+static int decode_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const float *targets, uint8_t *rgb8,
+                         float *img, float *stats, float *msssim, float *ws, int chunk, hipStream_t st)
+{
+    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
+    const orn_engine_desc &d = e->d;
+    const size_t HW = (size_t)e->Hout * e->Wout;
+    const bool fast = e->ff < d.n_layers;
+    float *ms_ws = msssim ? ws + orn_align((size_t)chunk * 3 * HW * 4) / 4 : nullptr;
+    if (stats && n > 0) ORN_HIP(hipMemsetAsync(e->dec_ws + 2 * ORN_DECODE_MAX_BLOCKS, 0, 64 * 4, st));      // the ticket starts at zero
+    for (int32_t k = 0; k < n; ++k) {
+        ORN_TRY(forward(e, embeds, rows + k, false, st, k == 0 ? 0 : MERGE_NONE, false));
+        float *planes = img ? img + (size_t)k * HW * 3 : (msssim ? ws + (size_t)(k % chunk) * HW * 3 : nullptr);
+        const OrnDecodeOut o = {targets, rows + k, rgb8 ? rgb8 + (size_t)k * HW * 3 : nullptr, planes,
+                                stats ? stats + (size_t)k * 4 : nullptr, e->dec_ws};
+        if (fast)
+            ORN_TRY(e->ops->decode_out(e->L[d.n_layers - 1].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st));
+        else
+            ORN_TRY(orn_launch_decode_out_f32(e->img, HW, o, st));
+        if (msssim && ((k + 1) % chunk == 0 || k + 1 == n)) {
+            const int32_t k0 = k / chunk * chunk;
+            ORN_TRY(orn_launch_msssim_frames(img ? img + (size_t)k0 * HW * 3 : ws, targets, rows + k0, k + 1 - k0, 3, e->Hout, e->Wout,
+                                             msssim + k0, ms_ws, st));
+        }
+    }
+    return 0;
+}
+
 extern "C" int orn_engine_decode_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const float *targets,
                                         uint8_t *rgb8, float *img, float *stats, void *stream)
 {
@@ -674,22 +703,40 @@ extern "C" int orn_engine_decode_frames(orn_engine *e, const float *embeds, cons
     ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_decode_frames: n=%d frames need a device array of n row indices", n);
     ORN_REQUIRE(rgb8 || img || stats, "engine_decode_frames: no output asked for (rgb8, img and stats are all null)");
     ORN_REQUIRE(!stats || targets, "engine_decode_frames: stats need targets");
-    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
-    hipStream_t st = (hipStream_t)stream;
-    const orn_engine_desc &d = e->d;
-    const size_t HW = (size_t)e->Hout * e->Wout;
-    const bool fast = e->ff < d.n_layers;
-    if (stats && n > 0) ORN_HIP(hipMemsetAsync(e->dec_ws + 2 * ORN_DECODE_MAX_BLOCKS, 0, 64 * 4, st));      // the ticket starts at zero
-    for (int32_t k = 0; k < n; ++k) {
-        ORN_TRY(forward(e, embeds, rows + k, false, st, k == 0 ? 0 : MERGE_NONE, false));
-        const OrnDecodeOut o = {targets, rows + k, rgb8 ? rgb8 + (size_t)k * HW * 3 : nullptr, img ? img + (size_t)k * HW * 3 : nullptr,
-                                stats ? stats + (size_t)k * 4 : nullptr, e->dec_ws};
-        if (fast)
-            ORN_TRY(e->ops->decode_out(e->L[d.n_layers - 1].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st));
-        else
-            ORN_TRY(orn_launch_decode_out_f32(e->img, HW, o, st));
-    }
-    return 0;
+    return decode_frames(e, embeds, rows, n, targets, rgb8, img, stats, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+// image size of a checked description
+static void desc_out_hw(const orn_engine_desc *d, int *H, int *W)
+{
+    const orn_layer_desc &l = d->layer[d->n_layers - 1];
+    *H = l.H * l.s; *W = l.W * l.s;
+}
+
+// `chunk` fp32 image slots [3][H][W], then the MS-SSIM workspace of a chunk of that many frames
+extern "C" size_t orn_engine_eval_frames_ws_bytes(const orn_engine_desc *d, int chunk)
+{
+    if (chunk <= 0 || check_desc(d) != 0) return 0;
+    int H, W;
+    desc_out_hw(d, &H, &W);
+    const size_t ms = orn_msssim_frames_ws_bytes(chunk, 3, H, W);
+    return ms ? orn_align((size_t)chunk * 3 * H * W * 4) + ms : 0;
+}
+
+extern "C" int orn_engine_eval_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const float *targets,
+                                      uint8_t *rgb8, float *img, float *stats, float *msssim, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!msssim) return orn_engine_decode_frames(e, embeds, rows, n, targets, rgb8, img, stats, stream);
+    ORN_REQUIRE(e && embeds, "engine_eval_frames: null engine / embeds");
+    ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_eval_frames: n=%d frames need a device array of n row indices", n);
+    ORN_REQUIRE(targets, "engine_eval_frames: msssim needs targets");
+    ORN_REQUIRE((e->Hout < e->Wout ? e->Hout : e->Wout) > 160, "engine_eval_frames: msssim: image side must exceed 160 (got %dx%d)", e->Hout, e->Wout);
+    if (n == 0) return 0;
+    ORN_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "engine_eval_frames: msssim needs a 16-byte aligned workspace");
+    int chunk = n < 65535 / 3 ? n : 65535 / 3;
+    while (chunk > 0 && orn_engine_eval_frames_ws_bytes(&e->d, chunk) > ws_bytes) --chunk;
+    if (chunk < 1) { orn_set_error("engine_eval_frames: workspace %zu < %zu", ws_bytes, orn_engine_eval_frames_ws_bytes(&e->d, 1)); return ORN_E_WS; }
+    return decode_frames(e, embeds, rows, n, targets, rgb8, img, stats, msssim, (float *)ws, chunk, (hipStream_t)stream);
 }
 
 static OrnMergeMisc merge_misc(const orn_engine *e, int i)

@@ -108,6 +108,12 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
                     hipStream_t st, const OrnStepCur *cur = nullptr, float *ring = nullptr, OrnScaleState *sc = nullptr,
                     const float *tstats = nullptr,    // tstats: orn_loss_target_stats of the SAME frame table (Fusion6; indexed by *frame_idx)
                     OrnLossFinalJob *defer = nullptr);   // defer: the finalize stage is returned as a job instead of launched
+// Batched MS-SSIM (orn_msssim_frames): one chunk of F frames, pred [F][Ch][H][W] against targets[rows[k]] (rows null: targets[k]),
+// out [F]; ws: orn_msssim_frames_ws_bytes(F, ...) bytes.  Six launches, no copy, no sync.  orn_msssim_frames_chunk: the most frames
+// (<= n) whose workspace fits in ws_bytes, 0 if not even one.
+int orn_msssim_frames_chunk(int n, int Ch, int H, int W, size_t ws_bytes);
+int orn_launch_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *out,
+                             float *ws, hipStream_t st);
 
 // The 16-bit MFMA fast path (channels-last buffers, see the header of orn_conv_bf16.hip): orn_conv_fwd_bf16.hip, orn_conv_bf16.hip
 // (dgrad), orn_conv2_bf16.hip (both, large images), orn_wgrad_bf16.hip and orn_ops_bf16.hip, with orn_h16.h between them.  These

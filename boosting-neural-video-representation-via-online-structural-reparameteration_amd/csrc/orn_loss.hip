@@ -668,3 +668,222 @@ extern "C" int orn_msssim(const float *pred, const float *target, int B, int Ch,
     ORN_LAUNCH_CHECK("msssim_finalize");
     return 0;
 }
+
+// ================================================================================================
+// N3, batched: one MS-SSIM value per frame for n frame pairs (orn_msssim_frames, include/orn.h; the `msssim` column of
+// orn_engine_eval_frames).  Per chunk of F frames: ONE launch per pyramid level over F x Ch planes, then ONE finalize launch.
+// Nothing is uploaded and nothing synchronises: the five levels' geometry is a kernel argument.
+//   k_msssim_level does for its 16x64 tile what k_ssim_cs_partial does (same patch load, same separable fmaf chains, same
+//   orn_block_sum order) and, from the patch it already holds in LDS, writes the 2x2 average-pooled pred and target of the region
+//   it OWNS into the next level's buffers with k_avgpool2's arithmetic (in-bounds taps added in (dy, dx) order, then * 0.25f).
+//   Ownership: pooled pixel (yo, xo) belongs to the tile that holds its first in-bounds input row max(2*yo - ph, 0) and column
+//   max(2*xo - pw, 0); the second row / column then lies at most one past the tile's 16 x 64 pixels, inside its 10-pixel apron.
+//   The last tile row / column own everything up to the image edge: the tiles cover the VALID map (H-10 x W-10), so what is left
+//   of the image behind them is at most the apron.
+// Every sum keeps orn_msssim's order, so a frame's value is bit-identical to orn_msssim on that frame alone (B = 1).
+// ================================================================================================
+struct OrnMsLevel {
+    const float *x, *y;          // pred planes [F][Ch][H][W]; target planes likewise, or (level 0) the frame table rows index
+    const int32_t *rows;         // level 0: frame k's target is y[rows[k]]; nullptr: y[k]
+    int Ch, H, W, tiles_w, tiles_h;
+    float *part;                 // [F*Ch][tiles][2]
+    float *nx, *ny;              // next level's planes [F*Ch][Ho][Wo]; nullptr at the last level
+    int Ho, Wo, ph, pw;          // avg_pool2d(2, padding = size % 2)
+};
+struct OrnMsGeom { int nblk[5]; float nmap[5]; };
+
+__global__ void __launch_bounds__(256) k_msssim_level(OrnMsLevel q)
+{
+    __shared__ __attribute__((aligned(16))) float Ps[SS_PH][SS_PWP];
+    __shared__ __attribute__((aligned(16))) float Ts[SS_PH][SS_PWP];
+    __shared__ float Hs[5][SS_PH][SS_TW];
+    __shared__ float sred[16];
+    const int t = threadIdx.x, plane = blockIdx.y;
+    const int H = q.H, W = q.W;
+    const int tw = blockIdx.x % q.tiles_w, th = blockIdx.x / q.tiles_w;
+    const int y0 = th * SS_TH, x0 = tw * SS_TW;
+    const int Hv = H - 10, Wv = W - 10;
+    const int frame = plane / q.Ch;
+    const size_t tplane = q.rows ? (size_t)q.rows[frame] * q.Ch + (plane - frame * q.Ch) : (size_t)plane;
+    const float *pp = q.x + (size_t)plane * H * W, *tp = q.y + tplane * H * W;
+    for (int idx = t; idx < SS_PH * SS_PWP; idx += 256) {
+        const int r = idx / SS_PWP, c = idx - r * SS_PWP;
+        const int gy = y0 + r, gx = x0 + c;
+        const bool ok = c < SS_PW && gy < H && gx < W;
+        Ps[r][c] = ok ? pp[(size_t)gy * W + gx] : 0.f;
+        Ts[r][c] = ok ? tp[(size_t)gy * W + gx] : 0.f;
+    }
+    __syncthreads();
+    if (q.nx) {
+        // pooled rows [yo0, yo1) x columns [xo0, xo1): the ones whose first in-bounds input row / column this tile holds
+        const int yo0 = th == 0 ? 0 : y0 / 2 + q.ph, yo1 = th == q.tiles_h - 1 ? q.Ho : (y0 + SS_TH) / 2 + q.ph;
+        const int xo0 = tw == 0 ? 0 : x0 / 2 + q.pw, xo1 = tw == q.tiles_w - 1 ? q.Wo : (x0 + SS_TW) / 2 + q.pw;
+        const int nxo = xo1 - xo0, cnt = (yo1 - yo0) * nxo;
+        float *ox = q.nx + (size_t)plane * q.Ho * q.Wo, *oy = q.ny + (size_t)plane * q.Ho * q.Wo;
+        for (int idx = t; idx < cnt; idx += 256) {
+            const int yo = yo0 + idx / nxo, xo = xo0 + idx % nxo;
+            float sx = 0.f, sy = 0.f;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int yy = yo * 2 + dy - q.ph, xx = xo * 2 + dx - q.pw;
+                    if (yy >= 0 && yy < H && xx >= 0 && xx < W) { sx += Ps[yy - y0][xx - x0]; sy += Ts[yy - y0][xx - x0]; }
+                }
+            ox[(size_t)yo * q.Wo + xo] = sx * 0.25f;
+            oy[(size_t)yo * q.Wo + xo] = sy * 0.25f;
+        }
+    }
+    for (int idx = t; idx < SS_PH * SS_TW; idx += 256) {
+        const int r = idx / SS_TW, c = idx - r * SS_TW;
+        float sp = 0.f, st = 0.f, spp = 0.f, stt = 0.f, spt = 0.f;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const float g = c_gauss[k], a = Ps[r][c + k], b = Ts[r][c + k];
+            sp = fmaf(g, a, sp); st = fmaf(g, b, st);
+            spp = fmaf(g, a * a, spp); stt = fmaf(g, b * b, stt); spt = fmaf(g, a * b, spt);
+        }
+        Hs[0][r][c] = sp; Hs[1][r][c] = st; Hs[2][r][c] = spp; Hs[3][r][c] = stt; Hs[4][r][c] = spt;
+    }
+    __syncthreads();
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    float ss = 0.f, cs = 0.f;
+    for (int idx = t; idx < SS_TH * SS_TW; idx += 256) {
+        const int r = idx / SS_TW, c = idx - r * SS_TW;
+        if (y0 + r >= Hv || x0 + c >= Wv) continue;
+        float m = 0.f, mu = 0.f, qq = 0.f, tt = 0.f, rr = 0.f;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const float g = c_gauss[k];
+            m = fmaf(g, Hs[0][r + k][c], m); mu = fmaf(g, Hs[1][r + k][c], mu);
+            qq = fmaf(g, Hs[2][r + k][c], qq); tt = fmaf(g, Hs[3][r + k][c], tt); rr = fmaf(g, Hs[4][r + k][c], rr);
+        }
+        const float csm = (2.f * (rr - m * mu) + C2) / ((qq - m * m) + (tt - mu * mu) + C2);
+        cs += csm;
+        ss += ((2.f * m * mu + C1) / (m * m + mu * mu + C1)) * csm;
+    }
+    const float a = orn_block_sum(ss, sred);
+    const float b = orn_block_sum(cs, sred);
+    if (t == 0) {
+        const size_t bi = (size_t)plane * gridDim.x + blockIdx.x;
+        q.part[2 * bi] = a;
+        q.part[2 * bi + 1] = b;
+    }
+}
+
+// One thread per (frame, plane): k_msssim_finalize's level means -> relu -> weighted product, then per frame the mean over its planes
+// in plane order.  256 / Ch frames per work-group.
+__global__ void __launch_bounds__(256) k_msssim_frames_finalize(const float *__restrict__ part, OrnMsGeom g, int F, int Ch, float *__restrict__ out)
+{
+    __shared__ double acc[256];
+    const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+    const int fpb = 256 / Ch, fl = threadIdx.x / Ch, pc = threadIdx.x - fl * Ch;
+    const int frame = blockIdx.x * fpb + fl, planes = F * Ch;
+    const bool live = fl < fpb && frame < F;
+    double val = 0.0;
+    if (live) {
+        const size_t pl = (size_t)frame * Ch + pc;
+        size_t off = 0;
+        double prod = 1.0;
+        for (int lv = 0; lv < 5; ++lv) {
+            double ss = 0.0, cs = 0.0;
+            for (int b = 0; b < g.nblk[lv]; ++b) {
+                ss += (double)part[off + 2 * (pl * g.nblk[lv] + b)];
+                cs += (double)part[off + 2 * (pl * g.nblk[lv] + b) + 1];
+            }
+            off += (size_t)2 * planes * g.nblk[lv];
+            const double v = (lv < 4 ? cs : ss) / (double)g.nmap[lv];
+            prod *= pow(v > 0.0 ? v : 0.0, (double)wts[lv]);
+        }
+        val = prod;
+    }
+    acc[threadIdx.x] = val;
+    __syncthreads();
+    if (live && pc == 0) {
+        double s = 0.0;
+        for (int i = 0; i < Ch; ++i) s += acc[fl * Ch + i];
+        out[frame] = (float)(s / Ch);
+    }
+}
+
+// floats of one chunk's workspace: pooled pred / target planes of levels 1..4, then every level's per-tile partials
+static size_t msssim_frames_floats(size_t planes, const int Hs[5], const int Ws[5], float *pooled[5][2], float **part, float *base)
+{
+    size_t f = 0, nb = 0;
+    for (int l = 1; l < 5; ++l)
+        for (int k = 0; k < 2; ++k) {
+            if (pooled) pooled[l][k] = base + f;
+            f += orn_align(planes * Hs[l] * Ws[l] * 4) / 4;
+        }
+    for (int l = 0; l < 5; ++l) nb += (size_t)orn_cdiv(Ws[l] - 10, SS_TW) * orn_cdiv(Hs[l] - 10, SS_TH);
+    if (part) *part = base + f;
+    return f + orn_align(2 * planes * nb * 4) / 4;
+}
+
+extern "C" size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W)
+{
+    if (n <= 0 || Ch <= 0 || Ch > 64 || (H < W ? H : W) <= 160) return 0;
+    int Hs[5], Ws[5];
+    msssim_geom(H, W, Hs, Ws);
+    return msssim_frames_floats((size_t)n * Ch, Hs, Ws, nullptr, nullptr, nullptr) * 4;
+}
+
+// The most frames one chunk may hold in ws_bytes (0: not even one); F * Ch is a grid dimension.
+int orn_msssim_frames_chunk(int n, int Ch, int H, int W, size_t ws_bytes)
+{
+    int F = n < 65535 / Ch ? n : 65535 / Ch;
+    while (F > 0 && orn_msssim_frames_ws_bytes(F, Ch, H, W) > ws_bytes) --F;
+    return F;
+}
+
+// One chunk: F frames whose workspace fits (the callers check).  Six launches.
+int orn_launch_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *out,
+                             float *ws, hipStream_t st)
+{
+    int Hs[5], Ws[5];
+    msssim_geom(H, W, Hs, Ws);
+    const size_t planes = (size_t)F * Ch;
+    float *pooled[5][2] = {}, *part = nullptr;
+    msssim_frames_floats(planes, Hs, Ws, pooled, &part, ws);
+    OrnMsGeom g;
+    OrnMsLevel q = {};
+    q.x = pred; q.y = targets; q.rows = rows; q.Ch = Ch;
+    size_t poff = 0;
+    for (int l = 0; l < 5; ++l) {
+        q.H = Hs[l]; q.W = Ws[l];
+        q.tiles_w = orn_cdiv(Ws[l] - 10, SS_TW); q.tiles_h = orn_cdiv(Hs[l] - 10, SS_TH);
+        g.nblk[l] = q.tiles_w * q.tiles_h;
+        g.nmap[l] = (float)(Hs[l] - 10) * (float)(Ws[l] - 10);
+        q.part = part + poff;
+        poff += 2 * planes * g.nblk[l];
+        if (l < 4) { q.nx = pooled[l + 1][0]; q.ny = pooled[l + 1][1]; q.Ho = Hs[l + 1]; q.Wo = Ws[l + 1]; q.ph = Hs[l] % 2; q.pw = Ws[l] % 2; }
+        else { q.nx = q.ny = nullptr; q.Ho = q.Wo = q.ph = q.pw = 0; }
+        hipLaunchKernelGGL(k_msssim_level, dim3(g.nblk[l], (unsigned)planes), dim3(256), 0, st, q);
+        ORN_LAUNCH_CHECK("msssim_level");
+        q.x = q.nx; q.y = q.ny; q.rows = nullptr;
+    }
+    const int fpb = 256 / Ch;
+    hipLaunchKernelGGL(k_msssim_frames_finalize, dim3(orn_cdiv(F, fpb)), dim3(256), 0, st, part, g, F, Ch, out);
+    ORN_LAUNCH_CHECK("msssim_frames_finalize");
+    return 0;
+}
+
+// out[k] = ms_ssim(pred[k:k+1], targets[rows[k]] (rows NULL: targets[k]), data_range=1), k < n, in chunks of as many frames as ws holds.
+extern "C" int orn_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int n, int Ch, int H, int W, float *out,
+                                 void *ws, size_t ws_bytes, void *stream)
+{
+    ORN_REQUIRE(n >= 0 && Ch > 0 && Ch <= 64, "msssim_frames: bad frame / plane count");
+    ORN_REQUIRE((H < W ? H : W) > 160, "msssim_frames: image side must exceed 160 (got %dx%d)", H, W);
+    if (n == 0) return 0;
+    ORN_REQUIRE(pred && targets && out && ws, "msssim_frames: null pointer");
+    const int chunk = orn_msssim_frames_chunk(n, Ch, H, W, ws_bytes);
+    if (chunk < 1) { orn_set_error("msssim_frames: workspace too small"); return ORN_E_WS; }
+    ORN_TRY(ensure_gauss());
+    for (int k = 0; k < n; k += chunk) {
+        const int F = n - k < chunk ? n - k : chunk;
+        const size_t at = (size_t)k * Ch * H * W;
+        ORN_TRY(orn_launch_msssim_frames(pred + at, rows ? targets : targets + at, rows ? rows + k : nullptr, F, Ch, H, W, out + k,
+                                         (float *)ws, (hipStream_t)stream));
+    }
+    return 0;
+}

@@ -104,28 +104,32 @@ class _Decoding:
         check(lib().orn_engine_decode(self._h, _lib.ptr(embed), _lib.ptr(img), _lib.stream()), 'orn_engine_decode')
         return img
 
-    def decode_frames(self, rows=None, embeds=None, frames=None, rgb8=True, f32=False, stats=True) -> dict:
+    def decode_frames(self, rows=None, embeds=None, frames=None, rgb8=True, f32=False, stats=True, msssim=False, chunk=None) -> dict:
         """Decode many frames in one call (orn_engine_decode_frames; main_eval.py:795-815, main_train.py:377-438): the weight-only
         work of the forward runs once, and each frame ends on the device in what is asked for.
         rows: indices (sequence or tensor) into `embeds` [*,E] and `frames` [*,3,H,W]; both default to the resident video
         (set_video) and rows to all of it.  Returns device tensors, enqueued on the current stream without a host sync:
           'rgb8'  uint8 [n,H,W,3], torchvision.utils.save_image's bytes;  'img' float [n,3,H,W] (f32=True);
-          'stats' float [n,4]: mse, PSNR of the float image, mse, PSNR of the bytes / 255, against frames[rows] (stats=True; needs frames)."""
+          'stats' float [n,4]: mse, PSNR of the float image, mse, PSNR of the bytes / 255, against frames[rows] (stats=True; needs frames);
+          'msssim' float [n] (msssim=True; needs frames): MS-SSIM of each frame against frames[rows] as utils.py:201-211 computes it per
+            frame, in the same call (orn_engine_eval_frames), bit-identical to ops.ms_ssim on the decoded frame; zeros when the image
+            is less than 160 high (utils.msssim_fn's rule).  chunk: frames per group of MS-SSIM launches, which sizes the workspace
+            (default min(n, 8); the values do not depend on it)."""
         embeds = self.embeds if embeds is None else embeds.to(self.device, torch.float32).contiguous()
         frames = self.frames if frames is None else frames.to(self.device, torch.float32).contiguous()
         if embeds is None:
             raise OrnError('decode_frames: no embeds given and no video resident (set_video)')
         if embeds.dim() != 2 or embeds.shape[1] != self.desc.embed_len:
             raise OrnError(f'decode_frames: embeds {tuple(embeds.shape)} vs (*, {self.desc.embed_len})')
-        if stats and frames is None:
-            raise OrnError('decode_frames: stats need target frames (frames=, or set_video)')
+        if (stats or msssim) and frames is None:
+            raise OrnError('decode_frames: stats and msssim need target frames (frames=, or set_video)')
         if frames is not None and tuple(frames.shape[1:]) != (3,) + tuple(self.out_hw):
             raise OrnError(f'decode_frames: frames {tuple(frames.shape)} do not match the decoder output {self.out_hw}')
         if rows is None:
             rows = torch.arange(embeds.shape[0], dtype=torch.int32)
         rows = torch.as_tensor(rows).to(torch.int32).reshape(-1)
         n = int(rows.numel())
-        limit = embeds.shape[0] if not stats else min(embeds.shape[0], frames.shape[0])
+        limit = embeds.shape[0] if not (stats or msssim) else min(embeds.shape[0], frames.shape[0])
         if n and (int(rows.min()) < 0 or int(rows.max()) >= limit):        # the device would read out of bounds
             raise OrnError(f'decode_frames: row index out of range [0, {limit})')
         rows = rows.to(self.device).contiguous()
@@ -137,11 +141,34 @@ class _Decoding:
             out['img'] = torch.empty(n, 3, H, W, device=self.device)
         if stats:
             out['stats'] = torch.empty(n, 4, device=self.device)
-        check(lib().orn_engine_decode_frames(self._h, _lib.ptr(embeds), _lib.ptr(rows), c_int32(n), _lib.ptr(frames) if stats else None,
-                                             _lib.ptr(out.get('rgb8')), _lib.ptr(out.get('img')), _lib.ptr(out.get('stats')),
-                                             _lib.stream()), 'orn_engine_decode_frames')
+        if msssim and H < 160:                              # utils.msssim_fn (utils.py:201-211): no MS-SSIM below 160 rows
+            out['msssim'] = torch.zeros(n, device=self.device)
+            msssim = False
+        if msssim and n:
+            out['msssim'] = torch.empty(n, device=self.device)
+            ws = self._eval_ws(max(1, min(n, chunk or 8)))
+            check(lib().orn_engine_eval_frames(self._h, _lib.ptr(embeds), _lib.ptr(rows), c_int32(n), _lib.ptr(frames),
+                                               _lib.ptr(out.get('rgb8')), _lib.ptr(out.get('img')), _lib.ptr(out.get('stats')),
+                                               _lib.ptr(out['msssim']), _lib.ptr(ws), c_size_t(ws.numel()), _lib.stream()),
+                  'orn_engine_eval_frames')
+        elif msssim:
+            out['msssim'] = torch.empty(0, device=self.device)
+        elif rgb8 or f32 or stats or 'msssim' not in out:     # (a zero column alone needs no decode; no output at all is the library's error)
+            check(lib().orn_engine_decode_frames(self._h, _lib.ptr(embeds), _lib.ptr(rows), c_int32(n), _lib.ptr(frames) if stats else None,
+                                                 _lib.ptr(out.get('rgb8')), _lib.ptr(out.get('img')), _lib.ptr(out.get('stats')),
+                                                 _lib.stream()), 'orn_engine_decode_frames')
         self._decode_keep = (embeds, frames, rows)          # alive until the stream has drained
         return out
+
+    def _eval_ws(self, chunk: int) -> torch.Tensor:
+        """The workspace of orn_engine_eval_frames for `chunk` frames, cached on the object (kept alive; it only grows)."""
+        nbytes = lib().orn_engine_eval_frames_ws_bytes(byref(self.desc), chunk)
+        if nbytes == 0:
+            raise OrnError(f'decode_frames: MS-SSIM needs an image larger than 160 x 160 (decoder output {tuple(self.out_hw)})')
+        ws = getattr(self, '_eval_ws_buf', None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._eval_ws_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
 
     def __del__(self):
         h = getattr(self, '_h', None)

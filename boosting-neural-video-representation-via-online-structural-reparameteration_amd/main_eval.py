@@ -3,8 +3,8 @@ load `model_latest(.pth|_deploy.pth)` -> global L1 prune (--prune_ratio) -> swit
 quantisation + Huffman size estimate (--quant_bit) -> decode every frame (PSNR, decoder FPS, bits per pixel).
 
 `--decoder engine` decodes with the native engine at `--precision` (engine.Decoder: all frames in one
-orn_engine_decode_frames call, PSNR of the float image and of the 8-bit pixels and the `--dump_images` bytes computed on the
-device); the default `eager` is the per-op fp32 module forward, frame by frame.
+orn_engine_eval_frames call, PSNR of the float image and of the 8-bit pixels, the per-frame MS-SSIM and the `--dump_images`
+bytes computed on the device); the default `eager` is the per-op fp32 module forward, frame by frame.
 
 `--finetune` (main_eval.py:213-545): load the TRAIN-mode checkpoint, prune the stem Linear weights and every conv
 branch weight together (global L1), fine-tune `--finetune_epochs` on the native engine, then deploy/quantise/evaluate.
@@ -93,9 +93,6 @@ def eval_parser():
     p.add_argument('--cycles', type=int, default=1)
     p.add_argument('--video', default=None, help='which video of a multi-video training job (--dataset a,b,c or a multi-rank '
                                                   '--synthetic job: synthetic<k>) to evaluate; default: the first')
-    p.add_argument('--decoder', default='eager', choices=['eager', 'engine'],
-                   help='eager: the fp32 module forward per frame; engine: the native engine at --precision, all frames in one '
-                        'call, PSNR (float and 8-bit) and the --dump_images pixels computed on the device')
     return p
 
 
@@ -106,7 +103,7 @@ def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
     dec = oeng.Decoder(model, precision=args.precision)
     torch.cuda.synchronize()
     t0 = time.time()
-    out = dec.decode_frames(embeds=embeds, frames=frames, rgb8=True, f32=False, stats=True)
+    out = dec.decode_frames(embeds=embeds, frames=frames, rgb8=True, f32=False, stats=True, msssim=True)
     torch.cuda.synchronize()
     fps = n / (time.time() - t0)
     st = out['stats'].double().mean(0)
@@ -118,11 +115,8 @@ def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
         print(f'Saving predictions to {visual_dir}')
         for k, arr in enumerate(out['rgb8'].cpu().numpy()):
             Image.fromarray(arr).save(os.path.join(visual_dir, f'pred_{k}.png'))
-    ms = []
-    for k in range(n):                                               # untimed, as the FPS above is the decoder's
-        img = dec.decode_frames(rows=[k], embeds=embeds, rgb8=False, f32=True, stats=False)['img']
-        ms.append(utils.msssim_fn([img], [frames[k:k + 1]])[0, 0])
-    msg = (f'Eval: PSNR {psnr:.2f} dB, 8-bit PSNR {psnr8:.2f} dB, MS-SSIM {float(torch.stack(ms).mean()):.4f}, '
+    msssim = float(out['msssim'].mean())                             # per frame, from the same call (its launches are in the FPS above)
+    msg = (f'Eval: PSNR {psnr:.2f} dB, 8-bit PSNR {psnr8:.2f} dB, MS-SSIM {msssim:.4f}, '
            f'decode {fps:.1f} FPS (engine, {args.precision}), params {n_param / 1e6:.3f} M')
     if bits is not None:
         msg += f', bpp {bits / (n * hw[0] * hw[1]):.4f}'

@@ -88,6 +88,10 @@ def build_parser():
     p.add_argument('--synthetic_videos', type=int, default=0,
                    help='with --synthetic: independent synthetic videos of the job (seeds 1234 + v), dealt round-robin to the ranks '
                         '(default: one per rank)')
+    p.add_argument('--decoder', default='eager', choices=['eager', 'engine'],
+                   help='how an evaluation decodes.  eager: frame by frame (main_eval: the fp32 module forward; main_train: one engine '
+                        'decode per frame and metric); engine: the native engine at --precision, all frames in one call, PSNR (float '
+                        'and 8-bit), MS-SSIM and the --dump_images pixels computed on the device')
     p.add_argument('--ckpt_freq', type=int, default=0, help='checkpoint every K epochs (0: eval epochs and the last)')
     p.add_argument('--dist_backend', default=None, choices=['nccl', 'gloo'],
                    help='torch.distributed backend under a multi-process launcher (default: nccl = RCCL on GPUs)')
@@ -228,6 +232,14 @@ def evaluate(model, eng, args, val=None, gap=None):
     frames, embeds = val if val is not None else (eng.frames, eng.embeds)
     gap = args.test_gap if gap is None else gap
     idx = list(range(frames.shape[0])) if val is not None else [k * gap for k in range(frames.shape[0] // gap)]
+    if getattr(args, 'decoder', 'eager') == 'engine':
+        # one call: the merge runs once, PSNR and MS-SSIM per frame stay on the device (orn_engine_eval_frames)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = eng.decode_frames(rows=idx, embeds=embeds, frames=frames, rgb8=False, stats=True, msssim=True)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        return float(out['stats'][:, 1].mean()), len(idx) / dt, float(out['msssim'].mean())
     psnrs = []
     torch.cuda.synchronize()
     t0 = time.time()

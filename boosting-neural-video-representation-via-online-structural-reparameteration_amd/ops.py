@@ -235,3 +235,32 @@ def ms_ssim(pred, target) -> torch.Tensor:
     ws = _ws(nb, pred.device)
     check(lib().orn_msssim(ptr(pred), ptr(target), B, Ch, H, W, ptr(out), ptr(ws), c_size_t(ws.numel()), stream()), 'orn_msssim')
     return out[0]
+
+
+def ms_ssim_frames(pred, target, rows=None, chunk=None) -> torch.Tensor:
+    """One MS-SSIM value per frame, enqueued without a host sync (orn_msssim_frames): out[k] = ms_ssim(pred[k:k+1], target[rows[k]])
+    as utils.py:201-211 calls it with batch 1, bit-identical to `ms_ssim` on that pair.  pred [n,Ch,H,W]; target [*,Ch,H,W];
+    rows: indices into target (sequence or tensor; default: frame k against target[k]).  A sequence or host tensor is range-checked
+    here; a device tensor is taken as it is (checking it would synchronise).  chunk: frames per group of six launches (default
+    min(n, 8); the values do not depend on it)."""
+    pred, target = _f32c(pred.detach()), _f32c(target.detach())
+    n, Ch, H, W = pred.shape
+    if target.dim() != 4 or tuple(target.shape[1:]) != (Ch, H, W):
+        raise _lib.OrnError(f'ms_ssim_frames: target {tuple(target.shape)} vs pred {tuple(pred.shape)}')
+    if rows is None:
+        if target.shape[0] < n:
+            raise _lib.OrnError(f'ms_ssim_frames: {n} frames against {target.shape[0]} targets')
+    else:
+        rows = torch.as_tensor(rows)
+        if rows.numel() != n:
+            raise _lib.OrnError(f'ms_ssim_frames: {rows.numel()} rows for {n} frames')
+        if not rows.is_cuda and n and (int(rows.min()) < 0 or int(rows.max()) >= target.shape[0]):
+            raise _lib.OrnError(f'ms_ssim_frames: row index out of range [0, {target.shape[0]})')
+        rows = rows.to(pred.device, torch.int32).reshape(-1).contiguous()
+    out = torch.empty(n, device=pred.device)
+    if n == 0:
+        return out
+    ws = _ws(lib().orn_msssim_frames_ws_bytes(max(1, min(n, chunk or 8)), Ch, H, W), pred.device)
+    check(lib().orn_msssim_frames(ptr(pred), ptr(target), ptr(rows), n, Ch, H, W, ptr(out), ptr(ws), c_size_t(ws.numel()), stream()),
+          'orn_msssim_frames')
+    return out

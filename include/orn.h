@@ -34,7 +34,8 @@
 extern "C" {
 #endif
 
-#define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames */
+#define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames;
+                                  * + orn_msssim_frames*, orn_engine_eval_frames* */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -167,6 +168,18 @@ ORN_API int orn_loss_target_stats(const float *frames, int n, int Ch, int H, int
 ORN_API size_t orn_msssim_ws_bytes(int B, int Ch, int H, int W);
 ORN_API int orn_msssim(const float *pred, const float *target, int B, int Ch, int H, int W, float *out, void *ws,
                size_t ws_bytes, void *stream);
+/* The same metric for n frame pairs, one value per frame, without the sync: out[k] = ms_ssim(pred[k:k+1], targets[rows[k]:rows[k]+1],
+ * data_range=1), which is how utils.py:201-211 calls it per frame with batch 1 from the evaluation loops (main_train.py:377-438,
+ * main_eval.py:795-815).  pred [n][Ch][H][W]; targets [*][Ch][H][W]; rows: DEVICE int32[n] read on the device, NULL = identity
+ * (targets[k]).  One launch per pyramid level for a whole chunk of frames (the level kernel also writes the next level's 2x2
+ * average pool) and one finalize launch: six launches per chunk, nothing uploaded, nothing synchronised, capturable (the first
+ * loss / MS-SSIM call of a process uploads the 11 filter taps and must not be the captured one).  The workspace must hold at
+ * least one frame (orn_msssim_frames_ws_bytes with n = 1; ORN_E_WS otherwise); n is worked through in chunks of as many frames
+ * as ws_bytes holds, and the values do not depend on the chunk size.  Every sum keeps orn_msssim's order: out[k] is bit-identical
+ * to orn_msssim on frame k alone with B = 1.  Ch <= 64, min(H, W) must exceed 160, n == 0 is a no-op. */
+ORN_API size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W);       /* bytes for a chunk of n frames; 0 on bad arguments */
+ORN_API int orn_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int n, int Ch, int H, int W,
+                              float *out /* [n] */, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- A9  optim.Adam.step over one flat arena                          main_train.py:196,250 ---
  * p,g,m,v: n floats each.  step = 1-based global step.  weight decay 0, amsgrad off.
@@ -230,6 +243,19 @@ ORN_API int orn_engine_decode(orn_engine *e, const float *embed, float *img, voi
  * (one workspace). */
 ORN_API int orn_engine_decode_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n,
                                      const float *targets, uint8_t *rgb8, float *img, float *stats, void *stream);
+/* ---- N2 + N3  evaluate a fitted video: pixels, PSNR and MS-SSIM per frame   main_eval.py:795-815, main_train.py:377-438,
+ * utils.py:201-211 ----
+ * orn_engine_decode_frames plus one column: msssim float [n], the batched MS-SSIM above of each decoded frame against
+ * targets[rows[k]] (requires targets; min(H, W) of the decoder output must exceed 160).  Same loop (the weight-only work runs for
+ * frame 0 only) and the same output stage: rgb8 / img / stats hold exactly the bytes orn_engine_decode_frames writes.  After every
+ * chunk of decoded frames the six MS-SSIM launches run on the chunk's fp32 planes: the caller's img when given, else slots inside
+ * ws that the output kernel fills.  ws: orn_engine_eval_frames_ws_bytes for a chunk of >= 1 frames (16-byte aligned; the chunk
+ * used is the largest that fits, the values do not depend on it); the engine's own workspace is not used for any of it.
+ * msssim == NULL: exactly orn_engine_decode_frames (ws is not read).  No sync, capturable, one stream at a time. */
+ORN_API size_t orn_engine_eval_frames_ws_bytes(const orn_engine_desc *d, int chunk);       /* 0 on bad arguments */
+ORN_API int orn_engine_eval_frames(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const float *targets,
+                                   uint8_t *rgb8, float *img, float *stats /* [n][4] */, float *msssim /* [n] */,
+                                   void *ws, size_t ws_bytes, void *stream);
 /* One optimiser step.  frames [n_frames,3,H,W], embeds [n_frames,E] (device); sched: device array,
  * `cursor` a device int32 the step reads and post-increments, so `n` back-to-back steps consume
  * sched[cursor..cursor+n).  stats_out: device [n_slots][8] ring written at slot (cursor % n_slots). */
