@@ -154,61 +154,6 @@ int orn_launch_nhwc_to_nchw_f32(const float *src, int C, int Cp, int H, int W, i
     return 0;
 }
 
-// dbias: partial[blk][o'] = sum over the block's pixel rows of dypad interior; then reduced + un-permuted
-#define DB_MAXO 1536
-__global__ void __launch_bounds__(256) k_dbias_nhwc_partial(const h16 *__restrict__ dypad, int H, int W, int O, int rows_per_blk,
-                                                            float *__restrict__ partial)
-{
-    __shared__ float red[DB_MAXO];
-    const int o8 = O / 8;                       // 16-byte groups per pixel
-    const int nw = 256 / o8;                    // pixel lanes
-    const int grp = threadIdx.x % o8, lw = threadIdx.x / o8;
-    const int h_begin = blockIdx.x * rows_per_blk, h_end = min(H, h_begin + rows_per_blk);
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (lw < nw)
-        for (int h = h_begin; h < h_end; ++h) {
-            const h16 *row = dypad + ((size_t)(h + 1) * (W + 2) + 1) * O + grp * 8;
-            for (int w = lw; w < W; w += nw) {
-                const h16x8 v = *reinterpret_cast<const h16x8 *>(row + (size_t)w * O);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) s[k] += (float)v[k];
-            }
-        }
-    for (int i = threadIdx.x; i < O; i += 256) red[i] = 0.f;
-    __syncthreads();
-    for (int r = 0; r < nw; ++r) {              // fixed order: deterministic
-        if (lw == r)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) red[grp * 8 + k] += s[k];
-        __syncthreads();
-    }
-    for (int i = threadIdx.x; i < O; i += 256) partial[(size_t)blockIdx.x * O + i] = red[i];
-}
-
-__global__ void k_dbias_finish(const float *__restrict__ partial, int nblk, int O, int Cn, int s2, float gscale,
-                               float *__restrict__ dbf)
-{
-    const int op = blockIdx.x * blockDim.x + threadIdx.x;
-    if (op >= O) return;
-    float acc = 0.f;
-    for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * O + op];
-    const int ij = op / Cn, nn = op - ij * Cn;
-    dbf[nn * s2 + ij] = acc * gscale;
-}
-
-size_t orn_dbias_bf16_ws_floats(int H, int O) { return (size_t)orn_cdiv(H, 2) * O; }
-
-int orn_launch_dbias_bf16(const h16 *dypad, int H, int W, int O, int s, float gscale, float *partial, float *dbf, hipStream_t st)
-{
-    ORN_REQUIRE(O % 8 == 0 && O / 8 <= 256 && O <= DB_MAXO, "dbias_bf16: unsupported O=%d", O);
-    const int rows_per_blk = 2, nblk = orn_cdiv(H, rows_per_blk);
-    hipLaunchKernelGGL(k_dbias_nhwc_partial, dim3(nblk), dim3(256), 0, st, dypad, H, W, O, rows_per_blk, partial);
-    ORN_LAUNCH_CHECK("dbias_partial");
-    hipLaunchKernelGGL(k_dbias_finish, dim3(orn_cdiv(O, 128)), dim3(128), 0, st, partial, nblk, O, O / (s * s), s * s, gscale, dbf);
-    ORN_LAUNCH_CHECK("dbias_finish");
-    return 0;
-}
-
 // ================================================================================================
 // A5 head on the channels-last bf16 pre-activation of the last block (model.py:621-622):
 //   a = SiLU(z);  u = W a + b;  out = (tanh u + 1)/2 | sigmoid u           out: fp32 NCHW [3][H][W]
@@ -396,7 +341,7 @@ int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, con
     ORN_REQUIRE(H % sp == 0 && W % sp == 0, "head_bwd_bf16: H,W not divisible by stride");
     int blocks = orn_cdiv((long)H * W, 64);
     if (blocks > HB_BLOCKS) blocks = HB_BLOCKS;
-    float *partial = ws, *red = ws + (size_t)HB_BLOCKS * (3 * C + 3);
+    float *partial = ws;
     OrnLossFinalJob fj = {};
     if (fin) fj = *fin;
     const int nfin = (fin && fin->n_l1 > 0) ? 1 : 0;
@@ -408,7 +353,6 @@ int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, con
     }
     ORN_LAUNCH_CHECK("head_bwd_bf16");
     if (!dw) return 0;                  // deferred: rides along orn_launch_wgrad_bf16_batch (OrnHeadFinish)
-    (void)red;
     return orn_launch_head_finish_bf16(partial, blocks, C, 1.0f / gs_up, dw, db, st);
 }
 
@@ -419,9 +363,6 @@ static int a_conv_fwd(const void *xpad, const void *wb, const float *bias_p, int
 static int a_conv_dgrad(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev, void *dyprev, int sp,
                         float *dx_f32, hipStream_t st, int c_real)
 { return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32, st, c_real); }
-static int a_wgrad(const void *xpad, const void *dypad, int H, int W, int C, int O, int s, float gscale, float *slabs, float *dwf,
-                   float *dbf, hipStream_t st)
-{ return orn_launch_wgrad_bf16((const h16 *)xpad, (const h16 *)dypad, H, W, C, O, s, gscale, slabs, dwf, dbf, st); }
 static int a_to_nhwc(const float *src, int C, int Cp, int H, int W, void *dst, hipStream_t st)
 { return orn_launch_nchw_to_nhwc_pad_bf16(src, C, Cp, H, W, (h16 *)dst, st); }
 static int a_to_nchw_f32(const float *src, int C, int Cp, int H, int W, int nslab, float scale, float *dst, hipStream_t st, const OrnScaleState *sc)
@@ -434,7 +375,7 @@ static int a_head_bwd(const void *z, const float *w, const float *out, const flo
                       float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc, const OrnLossFinalJob *fin)
 { return orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs_up, (h16 *)dypad, dw, db, ws, st, sc, fin); }
 
-const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, a_wgrad, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
+const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
                         a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out};
 
 // ================================================================================================
@@ -479,48 +420,38 @@ __global__ void k_make_dy_bf16(const float *__restrict__ z, const float *__restr
 
 static inline size_t alh(size_t halfs) { return orn_align(halfs * 2) / 2; }
 
-#ifdef ORN_FP16
-extern "C" size_t orn_conv3x3_ps_silu_bf16_ws_bytes(int C, int O, int H, int W, int s);     // element size is the same: one definition
-#else
-extern "C" size_t orn_conv3x3_ps_silu_bf16_ws_bytes(int C, int O, int H, int W, int s)
-{
-    const size_t Hs = (size_t)H * s, Ws = (size_t)W * s, Cn = O / (s * s);
-    size_t b = 0;
-    b += alh((size_t)(H + 2) * (W + 2) * C) * 2;          // xpad
-    b += 2 * alh((size_t)9 * O * C + 96 * C) * 2;         // wb, wd (+ the rows a ragged last N tile reads past the end)
-    b += orn_align((size_t)O * 4);                        // bias'
-    b += alh(Hs * Ws * Cn) * 2;                           // z bf16
-    b += alh((Hs + 2) * (Ws + 2) * Cn) * 2;               // apad
-    b += alh((size_t)(H + 2) * (W + 2) * O + 128) * 2;    // dypad (+ what a ragged last wgrad tile reads past the end)
-    b += orn_align(orn_wgrad_bf16_ws_floats(H, W, O) * 4);
-    b += orn_align(orn_dbias_bf16_ws_floats(H, O) * 4);
-    b += orn_align((size_t)H * W * C * 4 * 8);            // dx fp32 NHWC (up to 8 chunk slabs)
-    return b;
-}
-#endif
-
 struct Bf16Ws {
     h16 *xpad, *wb, *wd, *zb, *apad, *dypad;
-    float *biasp, *slabs, *dbp, *dxn;
+    float *biasp, *slabs, *dxn;
+    size_t bytes;
 };
 
+// The per-op workspace layout, in one place: the slices of `ws` and their total size (ws == nullptr: the size alone, as layout()
+// of orn_engine.hip).
 static Bf16Ws carve_bf16(void *ws, int C, int O, int H, int W, int s)
 {
     const size_t Hs = (size_t)H * s, Ws = (size_t)W * s, Cn = O / (s * s);
-    unsigned char *p = (unsigned char *)ws;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { void *p = ws ? (unsigned char *)ws + off : nullptr; off += bytes; return p; };
     Bf16Ws r;
-    r.xpad = (h16 *)p; p += alh((size_t)(H + 2) * (W + 2) * C) * 2;
-    r.wb = (h16 *)p; p += alh((size_t)9 * O * C + 96 * C) * 2;
-    r.wd = (h16 *)p; p += alh((size_t)9 * O * C + 96 * C) * 2;
-    r.biasp = (float *)p; p += orn_align((size_t)O * 4);
-    r.zb = (h16 *)p; p += alh(Hs * Ws * Cn) * 2;
-    r.apad = (h16 *)p; p += alh((Hs + 2) * (Ws + 2) * Cn) * 2;
-    r.dypad = (h16 *)p; p += alh((size_t)(H + 2) * (W + 2) * O + 128) * 2;
-    r.slabs = (float *)p; p += orn_align(orn_wgrad_bf16_ws_floats(H, W, O) * 4);
-    r.dbp = (float *)p; p += orn_align(orn_dbias_bf16_ws_floats(H, O) * 4);
-    r.dxn = (float *)p;
+    r.xpad = (h16 *)take(alh((size_t)(H + 2) * (W + 2) * C) * 2);
+    r.wb = (h16 *)take(alh((size_t)9 * O * C + 96 * C) * 2);                 // (+ the rows a ragged last N tile reads past the end)
+    r.wd = (h16 *)take(alh((size_t)9 * O * C + 96 * C) * 2);
+    r.biasp = (float *)take(orn_align((size_t)O * 4));
+    r.zb = (h16 *)take(alh(Hs * Ws * Cn) * 2);
+    r.apad = (h16 *)take(alh((Hs + 2) * (Ws + 2) * Cn) * 2);
+    r.dypad = (h16 *)take(alh((size_t)(H + 2) * (W + 2) * O + 128) * 2);     // (+ what a ragged last wgrad tile reads past the end)
+    r.slabs = (float *)take(orn_align(orn_wgrad_bf16_ws_floats(H, W, O) * 4));
+    r.dxn = (float *)take(orn_align((size_t)H * W * C * 4 * 8));             // dx fp32 NHWC (up to 8 chunk slabs)
+    r.bytes = off;
     return r;
 }
+
+#ifdef ORN_FP16
+extern "C" size_t orn_conv3x3_ps_silu_bf16_ws_bytes(int C, int O, int H, int W, int s);     // element size is the same: one definition
+#else
+extern "C" size_t orn_conv3x3_ps_silu_bf16_ws_bytes(int C, int O, int H, int W, int s) { return carve_bf16(nullptr, C, O, H, W, s).bytes; }
+#endif
 
 // Same contract as orn_conv3x3_ps_silu_fwd (B = 1) but computed on the bf16 MFMA path.
 // `ws` must be zero-filled by the caller before the first use (the padded borders are never written).

@@ -163,20 +163,21 @@ ORN_API size_t orn_loss_target_stats_bytes(int n, int Ch, int H, int W);
 ORN_API int orn_loss_target_stats(const float *frames, int n, int Ch, int H, int W, float *out, void *stream);
 
 /* ---- N3  msssim_fn: pytorch_msssim.ms_ssim(pred, target, data_range=1, size_average=True)   utils.py:201-211
- * Logging metric of the reference's train/eval loops (main_train.py:254); synchronises the stream (not for the
- * captured training step).  out: one device float.  min(H, W) must exceed 160. */
+ * Logging metric of the reference's train/eval loops (main_train.py:254).  out: one device float, the mean over the B*Ch planes
+ * (B*Ch <= 64).  min(H, W) must exceed 160.  Six launches, nothing uploaded, nothing synchronised: capturable after one eager
+ * loss / MS-SSIM call of the process (see orn_msssim_frames).  orn_msssim_ws_bytes: 0 on bad arguments. */
 ORN_API size_t orn_msssim_ws_bytes(int B, int Ch, int H, int W);
 ORN_API int orn_msssim(const float *pred, const float *target, int B, int Ch, int H, int W, float *out, void *ws,
                size_t ws_bytes, void *stream);
-/* The same metric for n frame pairs, one value per frame, without the sync: out[k] = ms_ssim(pred[k:k+1], targets[rows[k]:rows[k]+1],
+/* The same metric for n frame pairs, one value per frame: out[k] = ms_ssim(pred[k:k+1], targets[rows[k]:rows[k]+1],
  * data_range=1), which is how utils.py:201-211 calls it per frame with batch 1 from the evaluation loops (main_train.py:377-438,
  * main_eval.py:795-815).  pred [n][Ch][H][W]; targets [*][Ch][H][W]; rows: DEVICE int32[n] read on the device, NULL = identity
  * (targets[k]).  One launch per pyramid level for a whole chunk of frames (the level kernel also writes the next level's 2x2
  * average pool) and one finalize launch: six launches per chunk, nothing uploaded, nothing synchronised, capturable (the first
  * loss / MS-SSIM call of a process uploads the 11 filter taps and must not be the captured one).  The workspace must hold at
  * least one frame (orn_msssim_frames_ws_bytes with n = 1; ORN_E_WS otherwise); n is worked through in chunks of as many frames
- * as ws_bytes holds, and the values do not depend on the chunk size.  Every sum keeps orn_msssim's order: out[k] is bit-identical
- * to orn_msssim on frame k alone with B = 1.  Ch <= 64, min(H, W) must exceed 160, n == 0 is a no-op. */
+ * as ws_bytes holds, and the values do not depend on the chunk size.  orn_msssim is this call with one group of B*Ch planes.
+ * Ch <= 64, min(H, W) must exceed 160, n == 0 is a no-op. */
 ORN_API size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W);       /* bytes for a chunk of n frames; 0 on bad arguments */
 ORN_API int orn_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int n, int Ch, int H, int W,
                               float *out /* [n] */, void *ws, size_t ws_bytes, void *stream);

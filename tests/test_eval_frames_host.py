@@ -35,3 +35,11 @@ def test_msssim_frames_workspace_and_argument_errors(orn):
     assert L.orn_engine_eval_frames_ws_bytes(None, 1) == 0
     assert L.orn_engine_eval_frames(None, None, None, 1, None, None, None, None, None, None, 0, None) == -1
     assert 'engine_decode_frames' in orn._lib.last_error()                     # msssim == NULL: the plain entry, its own text
+
+
+def test_single_call_msssim_is_one_group_of_planes(orn):
+    L = orn._lib.lib()
+    for B, Ch, H, W in [(1, 3, 200, 240), (2, 3, 161, 177)]:
+        assert L.orn_msssim_ws_bytes(B, Ch, H, W) == L.orn_msssim_frames_ws_bytes(1, B * Ch, H, W) > 0
+    assert L.orn_msssim(None, None, 1, 3, 200, 240, None, None, 0, None) == -1
+    assert 'msssim:' in orn._lib.last_error()

@@ -69,6 +69,48 @@ def test_bit_equal_to_single_frame_op(orn, shape):
     assert torch.equal(c.out, single), (c.out.tolist(), single.tolist())
 
 
+# float32 bit patterns (tensor.view(torch.int32)) of ops.ms_ssim as commit 68b8921 computed them on an MI355X, when orn_msssim still
+# had kernels of its own (k_ssim_cs_partial, k_avgpool2, k_msssim_finalize): printed by a script that called ops.ms_ssim on the
+# inputs named below, before those kernels were removed.  Today both entry points run the same kernels; these are the old values.
+# (a) every frame of _inputs(*shape) on its own (B = 1)
+RECORDED_PER_FRAME = {
+    (3, 161, 161): [1065145360, 1064602319, 1063822306],
+    (4, 180, 240): [1065143038, 1064598536, 1063788901, 1062865015],
+    (2, 176, 193): [1065152509, 1064587273],
+    (3, 161, 417): [1065149782, 1064586291, 1063802435],
+}
+# (b) the whole batch of _inputs(*shape) in one call: the mean over 12 and 9 planes
+RECORDED_BATCH = {(4, 180, 240): 1064098873, (3, 161, 417): 1064512836}
+# (c) the B = 2, 161 x 177 input of test_gpu_parity.test_msssim: 6 planes
+RECORDED_PARITY_2x161x177 = 1064252808
+
+
+def _bits(x):
+    return x.detach().reshape(-1).cpu().view(torch.int32).tolist()
+
+
+def test_bits_are_the_recorded_ones(orn):
+    assert set(RECORDED_PER_FRAME) == set(SHAPES)
+    for shape in SHAPES:
+        c = _case(orn, shape)
+        single = torch.stack([orn.ops.ms_ssim(c.p[k:k + 1], c.t[k:k + 1]) for k in range(shape[0])])
+        print(f'{shape}: frames {_bits(c.out)} single {_bits(single)} recorded {RECORDED_PER_FRAME[shape]}')
+        assert _bits(c.out) == RECORDED_PER_FRAME[shape]
+        assert _bits(single) == RECORDED_PER_FRAME[shape]
+    for shape, want in RECORDED_BATCH.items():
+        c = _case(orn, shape)
+        got = _bits(orn.ops.ms_ssim(c.p, c.t))
+        print(f'{shape}: batch {got} recorded {want}')
+        assert got == [want]
+    B, H, W = 2, 161, 177                                              # test_gpu_parity.test_msssim's construction
+    gen = torch.Generator().manual_seed(H + W)
+    t = torch.nn.functional.avg_pool2d(torch.rand(B, 3, H, W, generator=gen), 5, 1, 2)
+    p = (t + 0.05 * torch.randn(B, 3, H, W, generator=gen)).clamp(0, 1)
+    got = _bits(orn.ops.ms_ssim(p.cuda(), t.cuda()))
+    print(f'parity input 2x161x177: {got} recorded {RECORDED_PARITY_2x161x177}')
+    assert got == [RECORDED_PARITY_2x161x177]
+
+
 def test_row_indirection(orn):
     c = _case(orn, SHAPES[0])                                          # 3 frames: a 3-frame target table
     rows = [2, 0, 2, 1]
@@ -111,7 +153,7 @@ def test_chunking_does_not_change_the_bits(orn):
 
 
 def test_captured_in_a_graph_and_replayed(orn):
-    """No copy, no sync: the call records into a hipGraph and the replays follow inputs changed in place (orn_msssim cannot)."""
+    """No copy, no sync: the call records into a hipGraph and the replays follow inputs changed in place."""
     L = orn._lib.lib()
     c = _case(orn, SHAPES[2])
     n, _, H, W = c.p.shape
@@ -135,6 +177,55 @@ def test_captured_in_a_graph_and_replayed(orn):
     torch.cuda.synchronize()
     assert torch.equal(out, want[1]), (out.tolist(), want[1].tolist())
     assert not torch.equal(want[0], want[1])
+
+
+def _call_single(orn, p, t, out, ws, ws_bytes):
+    B, Ch, H, W = p.shape
+    ptr = orn._lib.ptr
+    return orn._lib.lib().orn_msssim(ptr(p), ptr(t), B, Ch, H, W, ptr(out), ptr(ws), ctypes.c_size_t(ws_bytes), orn._lib.stream())
+
+
+def test_single_call_is_capturable(orn):
+    """orn_msssim uploads nothing and does not synchronise: after one eager call it records into a hipGraph, and the replays
+    follow inputs changed in place."""
+    L = orn._lib.lib()
+    c = _case(orn, SHAPES[0])                                          # 161 x 161: the smallest legal image
+    first_p, first_t = c.p[0:1].contiguous(), c.t[0:1].contiguous()
+    second_p, second_t = c.t[1:2].contiguous(), c.p[2:3].contiguous()
+    want = [orn.ops.ms_ssim(first_p, first_t), orn.ops.ms_ssim(second_p, second_t)]     # eager (and the process's first call: the taps)
+    p, t = first_p.clone(), first_t.clone()
+    out = torch.zeros(1, device='cuda')
+    nbytes = L.orn_msssim_ws_bytes(1, 3, 161, 161)
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode='thread_local'):
+        rc = _call_single(orn, p, t, out, ws, nbytes)
+    assert rc == 0, orn._lib.last_error()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], want[0]), (out.tolist(), want[0].item())
+    p.copy_(second_p)
+    t.copy_(second_t)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], want[1]), (out.tolist(), want[1].item())
+    assert not torch.equal(want[0], want[1])
+
+
+def test_single_call_workspace_size(orn):
+    L = orn._lib.lib()
+    c = _case(orn, SHAPES[0])
+    p, t = c.p[0:1].contiguous(), c.t[0:1].contiguous()
+    nbytes = L.orn_msssim_ws_bytes(1, 3, 161, 161)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+    out = torch.zeros(1, device='cuda')
+    assert _call_single(orn, p, t, out, ws, nbytes - 1) == E_WS
+    assert 'workspace too small' in orn._lib.last_error()
+    assert _call_single(orn, p, t, out, ws, nbytes) == 0, orn._lib.last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], c.out[0])
 
 
 def test_argument_errors(orn):

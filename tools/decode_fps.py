@@ -6,7 +6,7 @@
   d  a + what main_eval does per frame with torch ops today: the L2 loss kernel for the PSNR and mul/add/clamp/uint8/permute
      for the pixels (kept on the device: the host copy of --dump_images is not counted)
   e  the engine evaluation before orn_engine_eval_frames: decode_frames -> stats, then per frame a single-frame decode and
-     utils.msssim_fn (which drains the stream once per frame)
+     utils.msssim_fn (one MS-SSIM call per frame)
   f  the one-call evaluation: decode_frames -> stats + per-frame MS-SSIM (orn_engine_eval_frames)
 
 Every variant is warmed up, then timed REPEATS times, the variants alternating inside a repeat; a timing is a host clock around
