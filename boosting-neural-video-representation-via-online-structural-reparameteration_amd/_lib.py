@@ -5,7 +5,26 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORN_MAX_LAYERS = 8
-LOSS_TYPES = {'L2': 0, 'L1': 1, 'Fusion6': 2}
+# ORN_LOSS_* of include/orn.h: every loss of the reference's loss_fn (utils.py:139-189) but the two FFT ones (Fusion13, Fusion15)
+LOSS_TYPES = {'L2': 0, 'L1': 1, 'Fusion6': 2, 'SSIM': 3, 'Fusion1': 4, 'Fusion2': 5, 'Fusion3': 6, 'Fusion4': 7, 'Fusion5': 8,
+              'Fusion7': 9, 'Fusion8': 10, 'Fusion9': 11, 'Fusion10': 12, 'Fusion11': 13, 'Fusion12': 14}
+LOSS_KIND_NONE, LOSS_KIND_SSIM, LOSS_KIND_MSSSIM = 0, 1, 2
+
+
+def loss_id(loss_type: str) -> int:
+    """ORN_LOSS_* of a loss_fn name; NotImplementedError (with what is built) for Fusion13 / Fusion15 and unknown names."""
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError(f'loss_type {loss_type!r} is not built (utils.py:139-189): the library has '
+                                  f'{", ".join(LOSS_TYPES)}; the FFT losses Fusion13 and Fusion15 are out of scope')
+    return LOSS_TYPES[loss_type]
+
+
+def loss_spec(loss_type: str):
+    """((w_l1, w_l2, w_struct), kind) of a loss name, from the library's one table (orn_loss_spec)."""
+    w = (c_float * 3)()
+    kind = c_int(0)
+    check(lib().orn_loss_spec(loss_id(loss_type), w, ctypes.byref(kind)), 'orn_loss_spec')
+    return tuple(float(x) for x in w), kind.value
 
 
 class OrnError(RuntimeError):
@@ -61,7 +80,9 @@ _SIGS = {
     'orn_head_fwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     'orn_head_bwd_ws_bytes': (c_size_t, [c_int] * 4),
     'orn_head_bwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    'orn_loss_spec': (c_int, [c_int, POINTER(c_float), POINTER(c_int)]),
     'orn_loss_ws_bytes': (c_size_t, [c_int] * 4),
+    'orn_loss_ws_bytes_for': (c_size_t, [c_int] * 5),
     'orn_loss_fwd_bwd': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
     'orn_loss_target_stats_bytes': (c_size_t, [c_int] * 4),
     'orn_loss_target_stats': (c_int, [P, c_int, c_int, c_int, c_int, P, P]),

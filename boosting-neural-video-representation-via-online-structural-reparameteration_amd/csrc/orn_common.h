@@ -259,6 +259,9 @@ struct OrnLossFinalJob {
     // optional (engine, deferred last block): this step's schedule state and scale, copied for the side branch, which still
     // reads them after the main stream has advanced to the next step; the copy's flag starts clear
     OrnStepCur *cur_copy; OrnScaleState *sc_copy;
+    // loss ids above ORN_LOSS_FUSION6 (orn_loss_spec): loss = w_l1 * L1 + w_l2 * MSE + w_struct * (1 - s), s the SSIM mean of the
+    // partials or, for the MS-SSIM kinds, the value k_msssim_coef left at ms_val
+    float w_l1, w_l2, w_struct; const float *ms_val;
 };
 // every thread of the work-group calls it (barriers inside); sd: 3 * blockDim.x doubles of LDS; blockDim.x a power of two
 __device__ __forceinline__ void orn_loss_finalize_block(const OrnLossFinalJob &j, double *sd)
@@ -276,11 +279,12 @@ __device__ __forceinline__ void orn_loss_finalize_block(const OrnLossFinalJob &j
     if (t == 0) {
         const float l1 = (float)(sd[0] / j.n_elem);
         const float mse = (float)(sd[nt] / j.n_elem);
-        const float ss = (j.loss_type == 2 /* ORN_LOSS_FUSION6 */) ? (float)(sd[2 * nt] / j.n_map) : 0.f;
+        const float ss = j.ms_val ? *j.ms_val : ((j.n_ssim > 0) ? (float)(sd[2 * nt] / j.n_map) : 0.f);
         float loss;
         if (j.loss_type == 0 /* L2 */) loss = mse;
         else if (j.loss_type == 1 /* L1 */) loss = l1;
-        else loss = 0.7f * l1 + 0.3f * (1.0f - ss);
+        else if (j.loss_type == 2 /* ORN_LOSS_FUSION6 */) loss = 0.7f * l1 + 0.3f * (1.0f - ss);
+        else loss = j.w_l1 * l1 + j.w_l2 * mse + j.w_struct * (1.0f - ss);
         orn_flag_nonfinite(j.sc, loss);                // a NaN / inf forward pass: no update from this step
         const float psnr = -10.0f * log10f(mse);
         j.stats[0] = loss * j.loss_scale; j.stats[1] = l1; j.stats[2] = mse; j.stats[3] = ss; j.stats[4] = psnr;

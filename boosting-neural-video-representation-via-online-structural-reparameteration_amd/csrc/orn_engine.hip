@@ -127,7 +127,7 @@ static void drop_graphs(orn_engine *e)
 extern "C" size_t orn_conv3x3_ps_silu_bwd_ws_bytes(int B, int C, int O, int H, int W);
 extern "C" size_t orn_erb_merge_bwd_ws_bytes(int C, int O);
 extern "C" size_t orn_head_bwd_ws_bytes(int B, int C, int H, int W);
-extern "C" size_t orn_loss_ws_bytes(int B, int Ch, int H, int W);
+extern "C" size_t orn_loss_ws_bytes_for(int loss_type, int B, int Ch, int H, int W);
 
 static int check_desc(const orn_engine_desc *d)
 {
@@ -148,7 +148,10 @@ static int check_desc(const orn_engine_desc *d)
         C = l.O / (l.s * l.s); H *= l.s; W *= l.s;
     }
     ORN_REQUIRE(d->n_params > 0 && d->n_params % 4 == 0, "engine: n_params must be a positive multiple of 4");
-    ORN_REQUIRE(d->loss_type >= 0 && d->loss_type <= 2, "engine: bad loss_type %d", d->loss_type);
+    const OrnLossSpec *sp = orn_loss_spec_of(d->loss_type);
+    ORN_REQUIRE(sp, "engine: bad loss_type %d", d->loss_type);
+    if (sp->kind == ORN_LOSS_KIND_MSSSIM)       // pytorch_msssim's own limit (H, W: the decoder's output by now)
+        ORN_REQUIRE((H < W ? H : W) > 160, "engine: the MS-SSIM losses need an output side above 160 (got %dx%d)", H, W);
     return 0;
 }
 
@@ -232,7 +235,7 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
     }
     const size_t isz = (size_t)3 * H * W;
     float *img = take(isz), *dimg = take(isz), *stats = take(8);
-    float *loss_ws = take(orn_loss_ws_bytes(1, 3, H, W) / 4);
+    float *loss_ws = take(orn_loss_ws_bytes_for(d->loss_type, 1, 3, H, W) / 4);    // ids 0..2: orn_loss_ws_bytes, to the byte
     const size_t s3 = (ff < d->n_layers) ? orn_half_ops_bf16()->head_bwd_ws_floats(Cn) : orn_head_bwd_ws_bytes(1, Cn, H, W) / 4;
     if (s3 > scratch) scratch = s3;
     float *scr = take(scratch);
@@ -892,7 +895,7 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
     const int nl = d.n_layers, ff = e->ff;
     OrnLossFinalJob fin = {};
     ORN_TRY(orn_launch_loss(e->img, frames, fidx, 3 * HWo, 1, 3, e->Hout, e->Wout, d.loss_type, 1.0f, e->stats, e->dimg,
-                            e->loss_ws, st, cur, stats_out, sc, d.loss_type == ORN_LOSS_FUSION6 ? e->tstats : nullptr,
+                            e->loss_ws, st, cur, stats_out, sc, orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? e->tstats : nullptr,
                             ff < nl ? &fin : nullptr));     // 16-bit engine: the finalize stage rides on the head's backward launch
     if (pipe) { fin.cur_copy = e->cur_side; fin.sc_copy = e->sc_side; }     // (the previous step's side branch was joined in forward())
     if (ff < nl)

@@ -103,11 +103,51 @@ int orn_launch_head_bwd_fused_f32(const float *z, const float *w, const float *o
 
 // orn_loss.hip
 int orn_loss_init();
+// The one table of loss ids (include/orn.h): loss = w_l1 * L1 + w_l2 * MSE + w_struct * (1 - s), weights of utils.py:142-172.
+struct OrnLossSpec { double w_l1, w_l2, w_struct; int kind; };      // doubles: the gradient scales are formed in double
+static inline const OrnLossSpec *orn_loss_spec_of(int loss_type)
+{
+    static const OrnLossSpec tab[ORN_LOSS_COUNT] = {
+        /* L2       */ {0.0, 1.0, 0.0, ORN_LOSS_KIND_NONE},   /* L1       */ {1.0, 0.0, 0.0, ORN_LOSS_KIND_NONE},
+        /* Fusion6  */ {0.7, 0.0, 0.3, ORN_LOSS_KIND_SSIM},   /* SSIM     */ {0.0, 0.0, 1.0, ORN_LOSS_KIND_SSIM},
+        /* Fusion1  */ {0.0, 0.3, 0.7, ORN_LOSS_KIND_SSIM},   /* Fusion2  */ {0.3, 0.0, 0.7, ORN_LOSS_KIND_SSIM},
+        /* Fusion3  */ {0.0, 0.5, 0.5, ORN_LOSS_KIND_SSIM},   /* Fusion4  */ {0.5, 0.0, 0.5, ORN_LOSS_KIND_SSIM},
+        /* Fusion5  */ {0.0, 0.7, 0.3, ORN_LOSS_KIND_SSIM},   /* Fusion7  */ {0.3, 0.7, 0.0, ORN_LOSS_KIND_NONE},
+        /* Fusion8  */ {0.5, 0.5, 0.0, ORN_LOSS_KIND_NONE},   /* Fusion9  */ {0.9, 0.0, 0.1, ORN_LOSS_KIND_SSIM},
+        /* Fusion10 */ {0.7, 0.0, 0.3, ORN_LOSS_KIND_MSSSIM}, /* Fusion11 */ {0.9, 0.0, 0.1, ORN_LOSS_KIND_MSSSIM},
+        /* Fusion12 */ {0.8, 0.0, 0.2, ORN_LOSS_KIND_MSSSIM}};
+    return (loss_type >= 0 && loss_type < ORN_LOSS_COUNT) ? &tab[loss_type] : nullptr;
+}
 int orn_launch_loss(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int B, int Ch,
                     int H, int W, int loss_type, float loss_scale, float *stats, float *dpred, float *ws,
                     hipStream_t st, const OrnStepCur *cur = nullptr, float *ring = nullptr, OrnScaleState *sc = nullptr,
-                    const float *tstats = nullptr,    // tstats: orn_loss_target_stats of the SAME frame table (Fusion6; indexed by *frame_idx)
+                    const float *tstats = nullptr,    // tstats: orn_loss_target_stats of the SAME frame table (SSIM kinds; indexed by *frame_idx)
                     OrnLossFinalJob *defer = nullptr);   // defer: the finalize stage is returned as a job instead of launched
+void orn_gauss_taps(float g[11]);        // pytorch_msssim _fspecial_gauss_1d(11, 1.5)
+// The five level launches of the batched MS-SSIM on F groups of Ch planes (no finalize); the pooled planes of levels 1..4 and the
+// per-tile partials stay in ws (orn_msssim_pyramid_floats) and are described by *out.
+struct OrnMsPyramid {
+    int Hs[5], Ws[5], nblk[5]; float nmap[5];
+    float *pooled[5][2];         // [level 1..4][pred, target]: [F*Ch][Hs][Ws]
+    float *part;                 // level l at part_off[l]: [F*Ch][nblk[l]][2] = {ssim, cs} tile sums
+    size_t part_off[5];
+};
+static inline void orn_msssim_geom(int H, int W, int Hs[5], int Ws[5])
+{
+    Hs[0] = H; Ws[0] = W;
+    for (int l = 1; l < 5; ++l) { Hs[l] = (Hs[l - 1] + 2 * (Hs[l - 1] % 2)) / 2; Ws[l] = (Ws[l - 1] + 2 * (Ws[l - 1] % 2)) / 2; }
+}
+size_t orn_msssim_pyramid_floats(size_t planes, int H, int W);
+int orn_launch_msssim_levels(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *ws,
+                             hipStream_t st, OrnMsPyramid *out);
+// orn_loss_msssim.hip: the MS-SSIM losses (kind ORN_LOSS_KIND_MSSSIM).  ms_ws: orn_loss_msssim_ws_floats floats, 16-byte aligned.
+// Writes dpred (null: forward only) and the level-0 {|d|, d^2} tile partials part_l1 (the 16x64 tiling of orn_launch_loss);
+// *ms_val: where the coefficient launch leaves the MS-SSIM value for the finalize stage.
+int orn_loss_msssim_init();
+size_t orn_loss_msssim_ws_floats(size_t planes, int H, int W);
+int orn_launch_loss_msssim(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int planes, int H, int W,
+                           float g_l1, float g_l2, float w_struct_scaled, float *dpred, float *part_l1, float *ms_ws, hipStream_t st,
+                           const float **ms_val);
 // Batched MS-SSIM (orn_msssim_frames): one chunk of F frames, pred [F][Ch][H][W] against targets[rows[k]] (rows null: targets[k]),
 // out [F]; ws: orn_msssim_frames_ws_bytes(F, ...) bytes.  Six launches, no copy, no sync.  orn_msssim_frames_chunk: the most frames
 // (<= n) whose workspace fits in ws_bytes, 0 if not even one.

@@ -53,7 +53,8 @@ struct LossP {
 #define F6_LDS_FLOATS (2 * F6_PH * F6_PWP + 5 * F6_PH * F6_DWP + 16)
 
 enum { TC_NONE = 0, TC_READ = 1, TC_FILL = 2 };
-template <bool GRAD, int TC>
+// L2T: the pixel term of the gradient is g_l2 * d (Fusion1 / 3 / 5: MSE + SSIM) instead of g_l1 * sign(d)
+template <bool GRAD, int TC, bool L2T = false>
 __global__ void __launch_bounds__(256) k_fusion6(LossP q)
 {
     extern __shared__ __attribute__((aligned(16))) float f6s[];
@@ -289,7 +290,7 @@ __global__ void __launch_bounds__(256) k_fusion6(LossP q)
             sabs += fabsf(d);
             ssq = fmaf(d, d, ssq);
             if (GRAD) {
-                float g = q.g_l1 * ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
+                float g = L2T ? q.g_l2 * d : q.g_l1 * ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
                 g -= q.g_ssim * (am[o] + 2.f * p * aq[o] + tg * ar[o]);
                 q.dpred[(size_t)plane * HW + oo] = g;
             }
@@ -306,7 +307,7 @@ __global__ void __launch_bounds__(256) k_fusion6(LossP q)
     }
 }
 
-// L1 / L2 losses (no SSIM term).  LT / GRAD are compile-time: the per-pixel loop carries no loss-type or null-pointer branches
+// L1 / L2 losses (no SSIM term), and LT == ORN_LOSS_FUSION7: both terms (Fusion7 / Fusion8).  LT / GRAD are compile-time: the per-pixel loop carries no loss-type or null-pointer branches
 template <int LT, bool GRAD>
 __global__ void __launch_bounds__(256) k_loss_grad(LossP q)
 {
@@ -330,6 +331,7 @@ __global__ void __launch_bounds__(256) k_loss_grad(LossP q)
         if (GRAD) {
             float g;
             if (LT == ORN_LOSS_L2) g = q.g_l2 * d;
+            else if (LT == ORN_LOSS_FUSION7) g = fmaf(q.g_l2, d, q.g_l1 * ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f)));
             else g = q.g_l1 * ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f));
             q.dpred[(size_t)plane * HW + o] = g;
         }
@@ -352,17 +354,23 @@ __global__ void __launch_bounds__(256) k_loss_finalize(OrnLossFinalJob j)
 
 static bool g_gauss_ready = false;
 
-static int ensure_gauss()
+// pytorch_msssim _fspecial_gauss_1d(11, 1.5): fp32 exp, fp32 normalise
+void orn_gauss_taps(float g[11])
 {
-    if (g_gauss_ready) return 0;
-    // pytorch_msssim _fspecial_gauss_1d(11, 1.5): fp32 exp, fp32 normalise
-    float g[11], s = 0.f;
+    float s = 0.f;
     for (int i = 0; i < 11; ++i) {
         const float c = (float)(i - 5);
         g[i] = expf(-(c * c) / (2.0f * 1.5f * 1.5f));
         s += g[i];
     }
     for (int i = 0; i < 11; ++i) g[i] /= s;
+}
+
+static int ensure_gauss()
+{
+    if (g_gauss_ready) return 0;
+    float g[11];
+    orn_gauss_taps(g);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g));
     if (e != hipSuccess) {
         orn_set_error("loss: hipMemcpyToSymbol failed: %s", hipGetErrorString(e));
@@ -390,13 +398,36 @@ static LossGeom loss_geom(int B, int Ch, int H, int W)
 
 extern "C" size_t orn_loss_ws_bytes(int B, int Ch, int H, int W) { return loss_geom(B, Ch, H, W).total * 4; }
 
+extern "C" int orn_loss_spec(int loss_type, float *weights3, int *kind)
+{
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    ORN_REQUIRE(sp, "loss: loss_type %d is not built", loss_type);
+    if (weights3) { weights3[0] = (float)sp->w_l1; weights3[1] = (float)sp->w_l2; weights3[2] = (float)sp->w_struct; }
+    if (kind) *kind = sp->kind;
+    return 0;
+}
+
+// the MS-SSIM kinds append their own region (orn_loss_msssim.hip) behind the tile partials every loss type has
+extern "C" size_t orn_loss_ws_bytes_for(int loss_type, int B, int Ch, int H, int W)
+{
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    if (!sp || B <= 0 || Ch <= 0 || H <= 0 || W <= 0) return 0;
+    size_t f = loss_geom(B, Ch, H, W).total;
+    if (sp->kind == ORN_LOSS_KIND_MSSSIM) {
+        if ((H < W ? H : W) <= 160 || (long)B * Ch > 64) return 0;
+        f += orn_loss_msssim_ws_floats((size_t)B * Ch, H, W);
+    }
+    return f * 4;
+}
+
 static int ensure_fusion6_lds()
 {
     static bool done = false;
     if (done) return 0;
     hipError_t e = hipSuccess;
     const void *kerns[] = {(const void *)k_fusion6<true, TC_NONE>, (const void *)k_fusion6<false, TC_NONE>, (const void *)k_fusion6<true, TC_READ>,
-                           (const void *)k_fusion6<false, TC_READ>, (const void *)k_fusion6<false, TC_FILL>};
+                           (const void *)k_fusion6<false, TC_READ>, (const void *)k_fusion6<false, TC_FILL>,
+                           (const void *)k_fusion6<true, TC_NONE, true>, (const void *)k_fusion6<true, TC_READ, true>};
     for (const void *k : kerns)
         if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS_FLOATS * 4);
     if (e != hipSuccess) { orn_set_error("loss: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
@@ -405,18 +436,24 @@ static int ensure_fusion6_lds()
 }
 
 // Must be called once outside any graph capture (hipMemcpyToSymbol is synchronous).
-int orn_loss_init() { ORN_TRY(ensure_gauss()); return ensure_fusion6_lds(); }
+int orn_loss_init() { ORN_TRY(ensure_gauss()); ORN_TRY(ensure_fusion6_lds()); return orn_loss_msssim_init(); }
 
 int orn_launch_loss(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int B, int Ch,
                     int H, int W, int loss_type, float loss_scale, float *stats, float *dpred, float *ws,
                     hipStream_t st, const OrnStepCur *cur, float *ring, OrnScaleState *sc, const float *tstats, OrnLossFinalJob *defer)
 {
-    ORN_REQUIRE(loss_type == ORN_LOSS_L2 || loss_type == ORN_LOSS_L1 || loss_type == ORN_LOSS_FUSION6,
-                "loss: unsupported loss_type %d", loss_type);
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    ORN_REQUIRE(sp, "loss: unsupported loss_type %d", loss_type);
     ORN_TRY(orn_loss_init());
     static_assert(SS_TH == F6_TH && SS_TW == F6_TW, "one tiling for all loss kernels");
     const LossGeom g = loss_geom(B, Ch, H, W);
-    if (loss_type == ORN_LOSS_FUSION6) ORN_REQUIRE(g.Hv > 0 && g.Wv > 0, "loss: SSIM needs H,W > 10 (got %dx%d)", H, W);
+    const bool ssim = sp->kind == ORN_LOSS_KIND_SSIM, msssim = sp->kind == ORN_LOSS_KIND_MSSSIM;
+    if (ssim) ORN_REQUIRE(g.Hv > 0 && g.Wv > 0, "loss: SSIM needs H,W > 10 (got %dx%d)", H, W);
+    if (msssim) {
+        ORN_REQUIRE((H < W ? H : W) > 160, "loss: the MS-SSIM losses need an image side above 160 (got %dx%d)", H, W);
+        ORN_REQUIRE(g.planes <= 64, "loss: the MS-SSIM losses take at most 64 planes (got %d)", g.planes);
+        ORN_REQUIRE(!frame_idx || frame_stride == (size_t)Ch * H * W, "loss: MS-SSIM: frames must be contiguous");
+    }
     LossP q;
     q.pred = pred; q.target = target; q.frame_idx = frame_idx; q.frame_stride = frame_stride;
     q.planes = g.planes; q.H = H; q.W = W; q.Hv = g.Hv; q.Wv = g.Wv;
@@ -425,24 +462,38 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
     q.tstats = const_cast<float *>(tstats); q.tstats_stride = 2 * g.nmap;
     q.vec4 = (W % 4 == 0 && ((uintptr_t)pred | (uintptr_t)target) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx)) ? 1 : 0;
     const double n = (double)g.planes * H * W;
-    q.g_l1 = (float)((loss_type == ORN_LOSS_FUSION6 ? 0.7 : 1.0) * loss_scale / n);
-    q.g_l2 = (float)(2.0 * loss_scale / n);
-    q.g_ssim = g.nmap ? (float)(0.3 * loss_scale / (double)g.nmap) : 0.f;
+    // (ids 0..2: the values they have always had -- 0.7 * loss_scale / n, 2.0 * loss_scale / n, 0.3 * loss_scale / nmap)
+    q.g_l1 = (float)(sp->w_l1 * loss_scale / n);
+    q.g_l2 = (float)(2.0 * sp->w_l2 * loss_scale / n);
+    q.g_ssim = g.nmap ? (float)(sp->w_struct * loss_scale / (double)g.nmap) : 0.f;
     q.tiles_w = g.tw; q.tiles_h = g.th;
     const int n_tiles = g.planes * g.tw * g.th;
-    {
+    const float *ms_val = nullptr;
+    if (msssim) {
+        ORN_TRY(orn_launch_loss_msssim(pred, target, frame_idx, frame_stride, g.planes, H, W, q.g_l1, q.g_l2, (float)(sp->w_struct * loss_scale),
+                                       dpred, q.part_l1, ws + g.total, st, &ms_val));
+    } else {
         const dim3 gr(g.tw * g.th, g.planes), bl(256);
         const bool gd = q.dpred != nullptr;
-        if (loss_type == ORN_LOSS_FUSION6) {
-            if (tstats) { if (gd) hipLaunchKernelGGL((k_fusion6<true, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q); else hipLaunchKernelGGL((k_fusion6<false, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q); }
-            else if (gd) hipLaunchKernelGGL((k_fusion6<true, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q); else hipLaunchKernelGGL((k_fusion6<false, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+        const bool l2t = sp->w_l2 != 0.0;      // SSIM kinds: an L2 pixel term in place of the L1 one (no loss has both)
+        if (ssim) {
+            if (tstats) {
+                if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+                else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_READ, true>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+                else hipLaunchKernelGGL((k_fusion6<true, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+            }
+            else if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+            else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_NONE, true>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+            else hipLaunchKernelGGL((k_fusion6<true, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q);
         }
         else if (loss_type == ORN_LOSS_L2) { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L2, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L2, false>), gr, bl, 0, st, q); }
-        else { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, false>), gr, bl, 0, st, q); }
+        else if (loss_type == ORN_LOSS_L1) { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, false>), gr, bl, 0, st, q); }
+        else { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_FUSION7, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, false>), gr, bl, 0, st, q); }
+        ORN_LAUNCH_CHECK("loss");
     }
-    ORN_LAUNCH_CHECK("loss");
-    const OrnLossFinalJob fj = {q.part_ssim, loss_type == ORN_LOSS_FUSION6 ? n_tiles : 0, q.part_l1, n_tiles, n, (double)g.nmap, loss_type,
-                                loss_scale, stats, cur, ring, sc};
+    OrnLossFinalJob fj = {q.part_ssim, ssim ? n_tiles : 0, q.part_l1, n_tiles, n, (double)g.nmap, loss_type,
+                          loss_scale, stats, cur, ring, sc};
+    fj.w_l1 = (float)sp->w_l1; fj.w_l2 = (float)sp->w_l2; fj.w_struct = (float)sp->w_struct; fj.ms_val = ms_val;
     if (defer) { *defer = fj; return 0; }              // the caller runs it as a rider of a later launch
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, st, fj);
     ORN_LAUNCH_CHECK("loss_finalize");
@@ -479,8 +530,16 @@ extern "C" int orn_loss_fwd_bwd(const float *pred, const float *target, int B, i
 {
     ORN_REQUIRE(pred && target && stats && ws, "loss_fwd_bwd: null pointer");
     ORN_REQUIRE(B > 0 && Ch > 0 && H > 0 && W > 0, "loss_fwd_bwd: bad sizes");
-    if (ws_bytes < orn_loss_ws_bytes(B, Ch, H, W)) {
-        orn_set_error("loss_fwd_bwd: workspace %zu < %zu", ws_bytes, orn_loss_ws_bytes(B, Ch, H, W));
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    ORN_REQUIRE(sp, "loss_fwd_bwd: unsupported loss_type %d", loss_type);
+    if (sp->kind == ORN_LOSS_KIND_MSSSIM) {
+        ORN_REQUIRE((H < W ? H : W) > 160, "loss_fwd_bwd: the MS-SSIM losses need an image side above 160 (got %dx%d)", H, W);
+        ORN_REQUIRE((long)B * Ch <= 64, "loss_fwd_bwd: the MS-SSIM losses take at most 64 planes (got %ld)", (long)B * Ch);
+        ORN_REQUIRE((uintptr_t)ws % 16 == 0, "loss_fwd_bwd: the MS-SSIM losses need a 16-byte aligned workspace");
+    }
+    const size_t need = orn_loss_ws_bytes_for(loss_type, B, Ch, H, W);
+    if (ws_bytes < need) {
+        orn_set_error("loss_fwd_bwd: workspace %zu < %zu", ws_bytes, need);
         return ORN_E_WS;
     }
     return orn_launch_loss(pred, target, nullptr, 0, B, Ch, H, W, loss_type, loss_scale, stats, dpred, (float *)ws,
@@ -632,12 +691,6 @@ __global__ void __launch_bounds__(256) k_msssim_frames_finalize(const float *__r
     }
 }
 
-static void msssim_geom(int H, int W, int Hs[5], int Ws[5])
-{
-    Hs[0] = H; Ws[0] = W;
-    for (int l = 1; l < 5; ++l) { Hs[l] = (Hs[l - 1] + 2 * (Hs[l - 1] % 2)) / 2; Ws[l] = (Ws[l - 1] + 2 * (Ws[l - 1] % 2)) / 2; }
-}
-
 // floats of one chunk's workspace: pooled pred / target planes of levels 1..4, then every level's per-tile partials
 static size_t msssim_frames_floats(size_t planes, const int Hs[5], const int Ws[5], float *pooled[5][2], float **part, float *base)
 {
@@ -656,7 +709,7 @@ extern "C" size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W)
 {
     if (n <= 0 || Ch <= 0 || Ch > 64 || (H < W ? H : W) <= 160) return 0;
     int Hs[5], Ws[5];
-    msssim_geom(H, W, Hs, Ws);
+    orn_msssim_geom(H, W, Hs, Ws);
     return msssim_frames_floats((size_t)n * Ch, Hs, Ws, nullptr, nullptr, nullptr) * 4;
 }
 
@@ -668,34 +721,55 @@ int orn_msssim_frames_chunk(int n, int Ch, int H, int W, size_t ws_bytes)
     return F;
 }
 
-// One chunk: F frames whose workspace fits (the callers check).  Six launches.
-int orn_launch_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *out,
-                             float *ws, hipStream_t st)
+size_t orn_msssim_pyramid_floats(size_t planes, int H, int W)
 {
     int Hs[5], Ws[5];
-    msssim_geom(H, W, Hs, Ws);
+    orn_msssim_geom(H, W, Hs, Ws);
+    return msssim_frames_floats(planes, Hs, Ws, nullptr, nullptr, nullptr);
+}
+
+// The five level launches of one chunk (F frames whose workspace fits: the callers check); *out describes what they left in ws.
+int orn_launch_msssim_levels(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *ws,
+                             hipStream_t st, OrnMsPyramid *out)
+{
+    OrnMsPyramid &py = *out;
+    orn_msssim_geom(H, W, py.Hs, py.Ws);
+    const int *Hs = py.Hs, *Ws = py.Ws;
     const size_t planes = (size_t)F * Ch;
-    float *pooled[5][2] = {}, *part = nullptr;
-    msssim_frames_floats(planes, Hs, Ws, pooled, &part, ws);
-    OrnMsGeom g;
+    for (int k = 0; k < 2; ++k) py.pooled[0][k] = nullptr;
+    py.part = nullptr;
+    msssim_frames_floats(planes, Hs, Ws, py.pooled, &py.part, ws);
+    float *part = py.part;
     OrnMsLevel q = {};
     q.x = pred; q.y = targets; q.rows = rows; q.Ch = Ch;
     size_t poff = 0;
     for (int l = 0; l < 5; ++l) {
         q.H = Hs[l]; q.W = Ws[l];
         q.tiles_w = orn_cdiv(Ws[l] - 10, SS_TW); q.tiles_h = orn_cdiv(Hs[l] - 10, SS_TH);
-        g.nblk[l] = q.tiles_w * q.tiles_h;
-        g.nmap[l] = (float)(Hs[l] - 10) * (float)(Ws[l] - 10);
+        py.nblk[l] = q.tiles_w * q.tiles_h;
+        py.nmap[l] = (float)(Hs[l] - 10) * (float)(Ws[l] - 10);
         q.part = part + poff;
-        poff += 2 * planes * g.nblk[l];
-        if (l < 4) { q.nx = pooled[l + 1][0]; q.ny = pooled[l + 1][1]; q.Ho = Hs[l + 1]; q.Wo = Ws[l + 1]; q.ph = Hs[l] % 2; q.pw = Ws[l] % 2; }
+        py.part_off[l] = poff;
+        poff += 2 * planes * py.nblk[l];
+        if (l < 4) { q.nx = py.pooled[l + 1][0]; q.ny = py.pooled[l + 1][1]; q.Ho = Hs[l + 1]; q.Wo = Ws[l + 1]; q.ph = Hs[l] % 2; q.pw = Ws[l] % 2; }
         else { q.nx = q.ny = nullptr; q.Ho = q.Wo = q.ph = q.pw = 0; }
-        hipLaunchKernelGGL(k_msssim_level, dim3(g.nblk[l], (unsigned)planes), dim3(256), 0, st, q);
+        hipLaunchKernelGGL(k_msssim_level, dim3(py.nblk[l], (unsigned)planes), dim3(256), 0, st, q);
         ORN_LAUNCH_CHECK("msssim_level");
         q.x = q.nx; q.y = q.ny; q.rows = nullptr;
     }
+    return 0;
+}
+
+// One chunk: F frames whose workspace fits (the callers check).  Six launches.
+int orn_launch_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *out,
+                             float *ws, hipStream_t st)
+{
+    OrnMsPyramid py;
+    ORN_TRY(orn_launch_msssim_levels(pred, targets, rows, F, Ch, H, W, ws, st, &py));
+    OrnMsGeom g;
+    for (int l = 0; l < 5; ++l) { g.nblk[l] = py.nblk[l]; g.nmap[l] = py.nmap[l]; }
     const int fpb = 256 / Ch;
-    hipLaunchKernelGGL(k_msssim_frames_finalize, dim3(orn_cdiv(F, fpb)), dim3(256), 0, st, part, g, F, Ch, out);
+    hipLaunchKernelGGL(k_msssim_frames_finalize, dim3(orn_cdiv(F, fpb)), dim3(256), 0, st, py.part, g, F, Ch, out);
     ORN_LAUNCH_CHECK("msssim_frames_finalize");
     return 0;
 }

@@ -52,7 +52,7 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
     d.embed_len, d.stem_dim = model.stem[0].in_features, model.stem[0].out_features
     d.fc_h, d.fc_w, d.fc_dim = model.fc_h, model.fc_w, model.fc_dim
     d.sigmoid = int(bool(model.sigmoid))
-    d.loss_type = _lib.LOSS_TYPES[loss_type]
+    d.loss_type = _lib.loss_id(loss_type)
     d.precision = precision
     d.beta1, d.beta2, d.eps = beta1, beta2, eps
     d.stem_w0, d.stem_b0 = layout['stem.0.weight'][0], layout['stem.0.bias'][0]
@@ -245,7 +245,7 @@ class TrainEngine(_Decoding):
         check(lib().orn_engine_create(byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.adam_m),
                                       _lib.ptr(self.adam_v), _lib.ptr(self.ws), c_size_t(nbytes), byref(self._h)),
               'orn_engine_create')
-        self.target_cache = bool(target_cache) and loss_type == 'Fusion6'
+        self.target_cache = bool(target_cache) and _lib.loss_spec(loss_type)[1] == _lib.LOSS_KIND_SSIM
         self.tstats = None
         self.n_slots = n_slots
         self.stats_ring = torch.zeros(n_slots, 8, device=dev)
@@ -269,7 +269,7 @@ class TrainEngine(_Decoding):
             raise OrnError(f'embeds {tuple(embeds.shape)} vs ({frames.shape[0]}, {self.desc.embed_len})')
         self.frames = frames.to(self.device, torch.float32).contiguous()
         self.embeds = embeds.to(self.device, torch.float32).contiguous()
-        # Fusion6: the target side of the SSIM statistics, once per video (two valid-map planes per image plane: 2.9 GB for
+        # SSIM kinds (SSIM, Fusion1-6, Fusion9: the maps are the same): the target side of the SSIM statistics, once per video (two valid-map planes per image plane: 2.9 GB for
         # 132 frames of 720p, 29 GB for 600 of 1080p, of 288 GB); the step then filters three maps instead of five.
         # Skipped when it does not fit beside the video with room to spare.
         self.tstats = None

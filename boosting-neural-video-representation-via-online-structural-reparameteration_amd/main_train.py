@@ -58,7 +58,9 @@ def build_parser():
     p.add_argument('--lr_type', type=str, default='cosine')
     p.add_argument('--lr_steps', default=[], type=float, nargs='+')
     p.add_argument('--beta', type=float, default=0.5)
-    p.add_argument('--loss_type', type=str, default='L2')
+    p.add_argument('--loss_type', type=str, default='L2',
+                   help='utils.py:139-189: L2, L1, SSIM, Fusion1-12 (Fusion10-12 train towards MS-SSIM and need an output side above 160); '
+                        'the FFT losses Fusion13 / Fusion15 are not built')
     p.add_argument('--lw', type=float, default=1.0)
     p.add_argument('--sigmoid', action='store_true')
     p.add_argument('--deploy', action='store_true', default=False)

@@ -184,9 +184,9 @@ class HeadFn(torch.autograd.Function):
 
 # ---- A7 / A10 ------------------------------------------------------------------------------
 def loss_stats(pred, target, loss_type: str = 'Fusion6', want_grad: bool = True, loss_scale: float = 1.0):
-    """-> (stats[8] device tensor, dpred or None).  stats = [loss, L1, MSE, SSIM, PSNR, 0, 0, 0]."""
-    if loss_type not in _lib.LOSS_TYPES:
-        raise NotImplementedError(f'loss_type {loss_type!r}: only L2, L1 and Fusion6 are built (utils.py:139-189)')
+    """-> (stats[8] device tensor, dpred or None).  stats = [loss, L1, MSE, SSIM (MS-SSIM for Fusion10-12), PSNR, 0, 0, 0].
+    loss_type: any name of _lib.LOSS_TYPES; the MS-SSIM losses need min(H, W) > 160."""
+    lt = _lib.loss_id(loss_type)
     pred, target = _f32c(pred), _f32c(target)
     if pred.shape != target.shape or pred.dim() != 4:
         raise _lib.OrnError(f'loss: shapes {tuple(pred.shape)} vs {tuple(target.shape)}')
@@ -194,9 +194,9 @@ def loss_stats(pred, target, loss_type: str = 'Fusion6', want_grad: bool = True,
     dev = pred.device
     stats = torch.empty(8, device=dev)
     dpred = torch.empty_like(pred) if want_grad else None
-    nb = lib().orn_loss_ws_bytes(B, Ch, H, W)
+    nb = lib().orn_loss_ws_bytes_for(lt, B, Ch, H, W)      # 0 for a shape the loss does not take: the call below says why
     ws = _ws(nb, dev)
-    check(lib().orn_loss_fwd_bwd(ptr(pred), ptr(target), B, Ch, H, W, _lib.LOSS_TYPES[loss_type], c_float(loss_scale),
+    check(lib().orn_loss_fwd_bwd(ptr(pred), ptr(target), B, Ch, H, W, lt, c_float(loss_scale),
                                  ptr(stats), ptr(dpred), ptr(ws), c_size_t(ws.numel()), stream()), 'orn_loss_fwd_bwd')
     return stats, dpred
 

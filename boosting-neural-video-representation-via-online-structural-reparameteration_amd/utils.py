@@ -32,7 +32,7 @@ class PositionalEncoding(nn.Module):
 
 
 def loss_fn(pred, target, args):
-    """utils.py:139-189 for the loss types the hot path builds (L2, L1, Fusion6)."""
+    """utils.py:139-189 for the loss types the hot path builds: all but the FFT losses Fusion13 / Fusion15 (_lib.LOSS_TYPES)."""
     return ops.LossFn.apply(pred, target.detach(), args.loss_type)
 
 

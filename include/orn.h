@@ -35,7 +35,8 @@ extern "C" {
 #endif
 
 #define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames;
-                                  * + orn_msssim_frames*, orn_engine_eval_frames* */
+                                  * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
+                                  * orn_loss_ws_bytes_for */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -144,17 +145,51 @@ ORN_API int orn_head_bwd(const float *a, const float *w, const float *out, const
                  int W, int sigmoid, float *da, float *dw, float *db, void *ws, size_t ws_bytes,
                  void *stream);
 
-/* ---- A7 + A10  loss_fn (L2 | L1 | Fusion6) and psnr_fn               utils.py:139-199 ---------
+/* ---- A7 + A10  loss_fn (every loss but the two FFT ones) and psnr_fn   utils.py:139-199 ---------
  * pred/target [B,Ch,H,W].  stats (device, 8 floats):
- *   [0] loss  [1] mean|p-t|  [2] mean (p-t)^2  [3] ssim (0 unless Fusion6)  [4] psnr = -10 log10(mse)
- * dpred = dLoss/dpred * loss_scale (NULL: forward only). */
+ *   [0] loss  [1] mean|p-t|  [2] mean (p-t)^2  [3] ssim for the SSIM kinds, ms_ssim for the MS-SSIM kinds, else 0
+ *   [4] psnr = -10 log10(mse)
+ * dpred = dLoss/dpred * loss_scale (NULL: forward only).
+ * Every id resolves through one table (orn_loss_spec) to loss = w_l1 * L1 + w_l2 * MSE + w_struct * (1 - s) with s = ssim
+ * (kind ORN_LOSS_KIND_SSIM) or ms_ssim (ORN_LOSS_KIND_MSSSIM); the weights are those of utils.py:142-172.  Fusion13 / Fusion15
+ * (FFT terms) are not built and have no id.
+ *   kind SSIM: one launch, the 16x64-tile kernel of Fusion6 (80 KB of LDS) with other gradient weights; an L2 term takes the
+ *     place of the L1 term at compile time.  Fusion7 / Fusion8 (kind NONE) are the plain L1 / L2 kernel with both terms.
+ *   kind MSSSIM (min(H, W) > 160 and B*Ch <= 64, else ORN_E_ARG): 5 + 1 + 5 launches.  The five level launches of orn_msssim on the
+ *     step's planes (pooled planes and per-tile partials stay in ws); one coefficient launch (level means, their product, the value
+ *     of stats[3] -- bit-equal to orn_msssim on the same pair -- and per plane and level dLoss/d(level mean) / map size); then levels
+ *     4..0 backwards: per 16x64 tile the filtered maps are recomputed in LDS, the derivative maps of the CS map (levels 0..3) or the
+ *     SSIM map (level 4) go through the adjoint 11-tap filter, and the 2x2 average pool's adjoint of the level above is added.  Level
+ *     0 adds the L1 / L2 term and writes dpred.  No atomics, fixed-order sums. */
 #define ORN_LOSS_L2 0
 #define ORN_LOSS_L1 1
 #define ORN_LOSS_FUSION6 2
+#define ORN_LOSS_SSIM 3
+#define ORN_LOSS_FUSION1 4
+#define ORN_LOSS_FUSION2 5
+#define ORN_LOSS_FUSION3 6
+#define ORN_LOSS_FUSION4 7
+#define ORN_LOSS_FUSION5 8
+#define ORN_LOSS_FUSION7 9
+#define ORN_LOSS_FUSION8 10
+#define ORN_LOSS_FUSION9 11
+#define ORN_LOSS_FUSION10 12
+#define ORN_LOSS_FUSION11 13
+#define ORN_LOSS_FUSION12 14
+#define ORN_LOSS_COUNT 15
+#define ORN_LOSS_KIND_NONE 0
+#define ORN_LOSS_KIND_SSIM 1
+#define ORN_LOSS_KIND_MSSSIM 2
+/* weights3 (host) = {w_l1, w_l2, w_struct}, *kind = ORN_LOSS_KIND_*; ORN_E_ARG for an id that is not built. */
+ORN_API int orn_loss_spec(int loss_type, float *weights3, int *kind);
+/* orn_loss_ws_bytes: the workspace of ids 0..2 and of every kind but MSSSIM.  orn_loss_ws_bytes_for: the workspace of any id (the
+ * same number for those; the MS-SSIM kinds add both pyramids, the level gradients and the coefficients); 0 for an unknown id and
+ * for an MS-SSIM id with min(H, W) <= 160 or B*Ch > 64.  orn_loss_fwd_bwd checks ws_bytes against the latter. */
 ORN_API size_t orn_loss_ws_bytes(int B, int Ch, int H, int W);
+ORN_API size_t orn_loss_ws_bytes_for(int loss_type, int B, int Ch, int H, int W);
 ORN_API int orn_loss_fwd_bwd(const float *pred, const float *target, int B, int Ch, int H, int W, int loss_type,
                      float loss_scale, float *stats, float *dpred, void *ws, size_t ws_bytes, void *stream);
-/* Fusion6, engine only: the TARGET side of the SSIM statistics (utils.py:160 -> pytorch_msssim ssim: the 11-tap Gaussian of
+/* SSIM kinds (SSIM, Fusion1-6, Fusion9), engine only: the TARGET side of the SSIM statistics (utils.py:160 -> pytorch_msssim ssim: the 11-tap Gaussian of
  * t and of t*t on the valid map) of `n` resident frames [n][Ch][H][W] -> out [n][2][Ch][H-10][W-10] (orn_loss_target_stats_bytes).
  * A video's frames never change during its fit, so the engine can be handed this table once (orn_engine_set_target_stats) and
  * its steps then filter three maps (p, p*p, p*t) instead of five; same taps and fmaf order as the in-step form: results are
@@ -206,7 +241,7 @@ typedef struct orn_engine_desc {
     int32_t erb;                    /* 1: ERB online merge; 0: single 3x3 conv per block */
     int32_t embed_len, stem_dim, fc_h, fc_w, fc_dim;
     int32_t sigmoid;                /* head activation (model.py:622) */
-    int32_t loss_type;              /* ORN_LOSS_* */
+    int32_t loss_type;              /* ORN_LOSS_* (an MS-SSIM kind needs an output with min(H, W) > 160) */
     int32_t precision;              /* 0: fp32 everywhere; 1: bf16, 2: IEEE fp16 activations + 16-bit MFMA convs (fp32 accumulate) */
     double beta1, beta2, eps;
     int64_t stem_w0, stem_b0, stem_w1, stem_b1, head_w, head_b;
@@ -268,7 +303,7 @@ ORN_API int orn_engine_train_step(orn_engine *e, const float *frames, const floa
  * weight = weight_orig * mask, so pruned entries never receive a gradient -- and its frozen tensors. */
 ORN_API int orn_engine_set_grad_mask(orn_engine *e, const float *mask);
 /* Optional table of orn_loss_target_stats for the frame table the following steps are given (device, 16-byte aligned, caller-owned,
- * alive while set; null removes it).  Fusion6 only; other loss types ignore it. */
+ * alive while set; null removes it).  Used by the SSIM kinds (SSIM, Fusion1-6, Fusion9); other loss types ignore it. */
 ORN_API int orn_engine_set_target_stats(orn_engine *e, const float *stats);
 /* One eager training step with HIP events around the conv launches, on the launch stream; synchronises it.  ms_out (host,
  * 2*n_layers + 2 floats): [i] forward conv of layer i, [n_layers + i] dgrad launch of layer i (0: none), [2*n_layers] the
