@@ -5,6 +5,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORN_MAX_LAYERS = 8
+ORN_MAX_BATCH = 16
 # ORN_LOSS_* of include/orn.h: every loss of the reference's loss_fn (utils.py:139-189) but the two FFT ones (Fusion13, Fusion15)
 LOSS_TYPES = {'L2': 0, 'L1': 1, 'Fusion6': 2, 'SSIM': 3, 'Fusion1': 4, 'Fusion2': 5, 'Fusion3': 6, 'Fusion4': 7, 'Fusion5': 8,
               'Fusion7': 9, 'Fusion8': 10, 'Fusion9': 11, 'Fusion10': 12, 'Fusion11': 13, 'Fusion12': 14}
@@ -101,6 +102,9 @@ _SIGS = {
     'orn_engine_train_step': (c_int, [P, P, P, P, P, P, c_int32, P]),
     'orn_engine_train_steps_graph': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
     'orn_engine_train_steps': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
+    'orn_engine_batch_ws_bytes': (c_size_t, [POINTER(EngineDesc), c_int]),
+    'orn_engine_set_batch_ws': (c_int, [P, P, c_size_t, c_int]),
+    'orn_engine_train_steps_batch': (c_int, [P, P, P, P, P, P, c_int32, c_int32, c_int32, P]),
     'orn_engine_profile_step': (c_int, [P, P, P, P, P, P, c_int32, P, P]),
     'orn_engine_set_grad_mask': (c_int, [P, P]),
     'orn_engine_set_target_stats': (c_int, [P, P]),

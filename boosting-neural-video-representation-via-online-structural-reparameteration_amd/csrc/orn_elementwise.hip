@@ -704,3 +704,89 @@ extern "C" int orn_adam_step(float *p, const float *g, float *m, float *v, size_
     ORN_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "adam_step: arenas must be 16-byte aligned");
     return orn_launch_adam(p, g, m, v, n, lr, step, nullptr, beta1, beta2, eps, 1.0f, (hipStream_t)stream, nullptr);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Batched step (-b B, orn_engine_train_steps_batch): gradient accumulation and the batch's ring record
+// ------------------------------------------------------------------------------------------------
+// One launch per frame over the directly written gradient slots (OrnAccumTable).  HBM-bound: each work-group streams
+// ORN_ACCUM_CHUNK floats of one range, 16 bytes per lane where the range allows (ranges start 16-byte aligned in a 256-byte
+// aligned arena; their lengths are arbitrary, so the last float4 of a range may be a scalar tail).  Every element is owned by
+// one thread and the frames are summed in launch order: no atomics, bit-identical from run to run.
+template <int MODE>
+__device__ __forceinline__ float orn_accum_op(float a, float g, float inv_b)
+{
+    if (MODE == 0) return g;
+    if (MODE == 1) return __fadd_rn(a, g);
+    return __fmul_rn(__fadd_rn(a, g), inv_b);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_grad_accum(const OrnAccumTable t, float *__restrict__ g, float *__restrict__ acc, float inv_b)
+{
+    int r = 0;
+    while (r + 1 < t.n && (int)blockIdx.x >= t.blk_end[r]) ++r;
+    const int b0 = r > 0 ? t.blk_end[r - 1] : 0;
+    const size_t len = (size_t)t.len[r];
+    float *gp = g + t.off[r], *ap = acc + t.off[r];
+    float *dst = MODE == 2 ? gp : ap;
+    const bool vec = (t.off[r] & 3) == 0;
+    const size_t i0 = (size_t)((int)blockIdx.x - b0) * ORN_ACCUM_CHUNK;
+#pragma unroll
+    for (int k = 0; k < ORN_ACCUM_CHUNK / 1024; ++k) {
+        const size_t i = i0 + ((size_t)k * 256 + threadIdx.x) * 4;
+        if (i >= len) return;
+        if (vec && i + 4 <= len) {
+            const float4 gv = *reinterpret_cast<const float4 *>(gp + i);
+            float4 av = gv;
+            if (MODE != 0) av = *reinterpret_cast<const float4 *>(ap + i);
+            float4 o;
+            o.x = orn_accum_op<MODE>(av.x, gv.x, inv_b); o.y = orn_accum_op<MODE>(av.y, gv.y, inv_b);
+            o.z = orn_accum_op<MODE>(av.z, gv.z, inv_b); o.w = orn_accum_op<MODE>(av.w, gv.w, inv_b);
+            *reinterpret_cast<float4 *>(dst + i) = o;
+        } else {
+            const size_t i1 = i + 4 < len ? i + 4 : len;
+            for (size_t j = i; j < i1; ++j) dst[j] = orn_accum_op<MODE>(MODE != 0 ? ap[j] : 0.f, gp[j], inv_b);
+        }
+    }
+}
+
+int orn_launch_grad_accum(const OrnAccumTable &t, float *g, float *acc, int mode, float inv_b, hipStream_t st)
+{
+    ORN_REQUIRE(g && acc && t.n > 0 && t.n <= ORN_ACCUM_MAX_RANGES && mode >= 0 && mode <= 2, "grad_accum: bad arguments");
+    const dim3 gr(t.blk_end[t.n - 1]);
+    if (mode == 0) hipLaunchKernelGGL(k_grad_accum<0>, gr, dim3(256), 0, st, t, g, acc, inv_b);
+    else if (mode == 1) hipLaunchKernelGGL(k_grad_accum<1>, gr, dim3(256), 0, st, t, g, acc, inv_b);
+    else hipLaunchKernelGGL(k_grad_accum<2>, gr, dim3(256), 0, st, t, g, acc, inv_b);
+    ORN_LAUNCH_CHECK("grad_accum");
+    return 0;
+}
+
+// One work-group: the per-frame records of the loss finalize stage -> the optimiser step's ring record.  loss, L1, MSE, s: means
+// over the frames, summed in double in frame order; PSNR from the batch-mean MSE (psnr_fn on the whole batch, utils.py:191; the
+// expression of orn_loss_finalize_block, so that B equal frames give a single frame's bits).
+__global__ void __launch_bounds__(64) k_batch_stats(const float *__restrict__ fs, int B, const OrnStepCur *__restrict__ cur, float *__restrict__ ring)
+{
+    __shared__ double mean[4];
+    const int t = threadIdx.x;
+    if (t < 4) {
+        double s = 0.0;
+        for (int j = 0; j < B; ++j) s += (double)fs[(size_t)j * 8 + t];
+        mean[t] = s / (double)B;
+    }
+    __syncthreads();
+    if (t == 0) {
+        float *r = ring + (size_t)cur->slot * 8;
+        const float mse = (float)mean[2];
+        r[0] = (float)mean[0]; r[1] = (float)mean[1]; r[2] = mse; r[3] = (float)mean[3];
+        r[4] = -10.0f * log10f(mse);
+        r[5] = cur->lr; r[6] = (float)cur->frame; r[7] = (float)cur->step;
+    }
+}
+
+int orn_launch_batch_stats(const float *frame_stats, int B, const OrnStepCur *cur, float *ring, hipStream_t st)
+{
+    ORN_REQUIRE(frame_stats && cur && ring && B >= 1, "batch_stats: bad arguments");
+    hipLaunchKernelGGL(k_batch_stats, dim3(1), dim3(64), 0, st, frame_stats, B, cur, ring);
+    ORN_LAUNCH_CHECK("batch_stats");
+    return 0;
+}

@@ -94,6 +94,15 @@ struct orn_engine {
     bool fork_behind_dgrad;          // the side branch forks behind the last block's dgrad; else behind the lower blocks' slab reduction
     int last_smax;                   // split-K slab cap of the last block's weight gradient, in every form of the step (0: the default rule)
     bool side_busy;                  // a side branch is in flight (joined by the next step's forward or at the end of the call)
+    // Batched step (orn_engine_train_steps_batch): the directly written gradient slots as ranges of the arena (built at creation),
+    // and the caller's batch workspace (orn_engine_set_batch_ws; null: none): accumulation arena, the frame table of the step in
+    // flight (one schedule state per frame, filled by k_advance_batch; slot = the frame's place in the batch) and the per-frame
+    // stats the loss's finalize stage writes through that slot
+    OrnAccumTable acc_tab;
+    float *b_acc;
+    OrnStepCur *b_cur;
+    float *b_stats;
+    int b_max;
     // orn_engine_profile_step: HIP events around every forward conv launch of an eager step
     bool prof;
     hipEvent_t prof_ev[4 * ORN_MAX_LAYERS + 4];      // pairs: forward conv of layer i, dgrad launch of layer i, wgrad batch, its reduction
@@ -308,6 +317,26 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     e->ops = (d->precision == 2) ? orn_half_ops_f16() : orn_half_ops_bf16();
     e->gs = (d->precision == 2) ? 1048576.0f : 1.0f;
     layout(d, e);
+    {   // batched step: the gradient slots the backward writes directly (ERB: dWf / dbf in the 3x3 branch's slots; the other
+        // branches' gradients come from the merge backward, which runs once per optimiser step on the summed dWf)
+        OrnAccumTable &t = e->acc_tab;
+        t.n = 0;
+        int blocks = 0;
+        auto add = [&](int64_t off, int64_t len) {
+            t.off[t.n] = off; t.len[t.n] = len;
+            blocks += orn_cdiv((long)len, ORN_ACCUM_CHUNK);
+            t.blk_end[t.n++] = blocks;
+        };
+        for (int i = 0; i < d->n_layers; ++i) {
+            add(d->layer[i].w3x3, (int64_t)d->layer[i].O * d->layer[i].C * 9);
+            add(d->layer[i].b3x3, d->layer[i].O);
+        }
+        const int64_t Nout = (int64_t)d->fc_h * d->fc_w * d->fc_dim;
+        add(d->head_w, (int64_t)3 * e->Cn_last); add(d->head_b, 3);
+        add(d->stem_w0, (int64_t)d->stem_dim * d->embed_len); add(d->stem_b0, d->stem_dim);
+        add(d->stem_w1, Nout * d->stem_dim); add(d->stem_b1, Nout);
+        e->b_acc = nullptr; e->b_cur = nullptr; e->b_stats = nullptr; e->b_max = 0;
+    }
     {   // the one-pixel borders of the channels-last buffers must be (and stay) zero
         hipError_t rc = hipMemset(ws, 0, need);
         if (rc == hipSuccess) rc = hipDeviceSynchronize();
@@ -535,6 +564,58 @@ __global__ void k_advance(const orn_step_sched *__restrict__ sched, int32_t *cur
         cur->sqrt_bc2 = (float)sqrt(bc2);
         cur->slot = n_slots > 0 ? c % n_slots : 0;
         if (threadIdx.x == 0) *cursor = c0 + count;
+    }
+}
+
+// The batched form of the advance (orn_engine_train_steps_batch): ONE optimiser step that consumes `batch` schedule entries.  Flags
+// and scale are processed once, as k_advance does for a group of one step (one clean step credited per optimiser step, however
+// many frames it had).  step (less the skipped steps) and lr come from the first entry, the frames from all of them:
+//   cur0   the optimiser step's state: Adam's scalars, the first frame, the ring slot (optimiser-step index % n_slots)
+//   bcur   the frame table: the same state per frame j, with frame = sched[c0 + j].frame and slot = j (where the loss's finalize
+//          stage leaves that frame's stats)
+__global__ void k_advance_batch(const orn_step_sched *__restrict__ sched, int32_t *cursor, int32_t n_slots, double beta1, double beta2,
+                                OrnStepCur *cur0, OrnStepCur *bcur, int batch, OrnScaleState *sc)
+{
+    const int32_t c0 = *cursor;
+    __shared__ int32_t skipped;
+    if (threadIdx.x == 0) {
+        int nflag = 0;
+        for (int r = 0; r < ORN_SCALE_SLOTS; ++r)
+            if (sc[r].flag) { nflag += 1; sc[r].flag = 0; }
+        const int32_t late = __atomic_load_n(&sc->late_skipped, __ATOMIC_RELAXED);      // (left by pipelined calls before this one)
+        if (late != sc->late_seen) { nflag += 1; sc->late_seen = late; }
+        float gs = sc->gs;
+        if (nflag) {
+            gs = fmaxf(gs * 0.5f, 1.0f);
+            sc->good = 0; sc->backoffs += 1;
+        } else {
+            sc->good += sc->launched;
+            if (sc->good >= ORN_SCALE_GROWTH_INTERVAL && gs < sc->gs_max) { gs *= 2.0f; sc->good = 0; }
+        }
+        sc->launched = 1;
+        for (int r = 0; r < ORN_SCALE_SLOTS; ++r) { sc[r].gs = gs; sc[r].inv_gs = 1.0f / gs; }
+        skipped = sc->skipped;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < batch) {
+        const int j = threadIdx.x;
+        const orn_step_sched s0 = sched[c0];
+        const int32_t step = max(s0.step - skipped, 1);
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        OrnStepCur c;
+        c.frame = sched[c0 + j].frame;
+        c.step = step;
+        c.lr = s0.lr;
+        c.step_size = (float)((double)s0.lr / bc1);
+        c.sqrt_bc2 = (float)sqrt(bc2);
+        c.slot = j;
+        c.pad[0] = c.pad[1] = 0;
+        bcur[j] = c;
+        if (j == 0) {
+            c.slot = n_slots > 0 ? (c0 / batch) % n_slots : 0;
+            *cur0 = c;
+            *cursor = c0 + batch;
+        }
     }
 }
 
@@ -873,6 +954,10 @@ struct StepOpts {
     int cur = 0;            // the step itself runs on e->cur[cur]
     bool pipe = false;      // the pipelined form (struct orn_engine, `side`): the last block's weight-gradient chain leaves this step on the side stream
     bool more = false;      // (pipelined form) another step follows in this call
+    // batched step (orn_engine_train_steps_batch; with advance = 0, the batched advance has run): this call is frame `bframe` of an
+    // optimiser step of `batch` frames.  It reads its frame from the frame table, leaves its stats there, and ends in the accumulate
+    // launch; frames 1.. skip the merge forward; the last frame goes on to the one merge backward, the ring record and Adam.
+    int batch = 0, bframe = 0;
 };
 
 // forward -> loss / head -> dgrad chain -> stem -> weight gradients -> merge backward -> Adam
@@ -884,18 +969,19 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
     float *P = e->params, *G = e->grads;
     const int Nout = d.fc_h * d.fc_w * d.fc_dim;
     const size_t HWo = (size_t)e->Hout * e->Wout;
-    OrnStepCur *cur = e->cur + o.cur;
+    const bool batched = o.batch > 0;
+    OrnStepCur *cur = batched ? e->b_cur + o.bframe : e->cur + o.cur;
     if (o.advance > 0) {
         hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, d.beta1, d.beta2, e->cur, o.advance, e->sc /* all entries */);
         ORN_LAUNCH_CHECK("advance");
     }
     OrnScaleState *const sc = e->sc + o.cur;            // this step's entry: its own flag, the shared scale
     const int *fidx = &cur->frame;
-    ORN_TRY(forward(e, embeds, fidx, true, st, (pipe && e->side_busy) ? 1 : 0));
+    ORN_TRY(forward(e, embeds, fidx, true, st, (batched && o.bframe > 0) ? (int)MERGE_NONE : (pipe && e->side_busy) ? 1 : 0));
     const int nl = d.n_layers, ff = e->ff;
     OrnLossFinalJob fin = {};
     ORN_TRY(orn_launch_loss(e->img, frames, fidx, 3 * HWo, 1, 3, e->Hout, e->Wout, d.loss_type, 1.0f, e->stats, e->dimg,
-                            e->loss_ws, st, cur, stats_out, sc, orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? e->tstats : nullptr,
+                            e->loss_ws, st, cur, batched ? e->b_stats : stats_out, sc, orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? e->tstats : nullptr,
                             ff < nl ? &fin : nullptr));     // 16-bit engine: the finalize stage rides on the head's backward launch
     if (pipe) { fin.cur_copy = e->cur_side; fin.sc_copy = e->sc_side; }     // (the previous step's side branch was joined in forward())
     if (ff < nl)
@@ -952,6 +1038,14 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
                                 e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr));
     if (ff < nl) ORN_TRY(fast_weight_grads(e, st, pipe, sc, &l2job, &w0job));
     if (pipe && !e->fork_behind_dgrad) ORN_TRY(side_branch_backward(e, st));     // fork: behind the lower blocks' slab reduction
+    if (batched) {
+        // every directly written gradient slot holds this frame's gradient: fold it into the batch's sum (B == 1: it is the sum)
+        if (o.batch > 1)
+            ORN_TRY(orn_launch_grad_accum(e->acc_tab, G, e->b_acc, o.bframe == 0 ? 0 : (o.bframe + 1 < o.batch ? 1 : 2), 1.0f / (float)o.batch, st));
+        if (o.bframe + 1 < o.batch) return 0;
+        cur = e->cur;                                   // the optimiser step's own state (k_advance_batch)
+        if (stats_out) ORN_TRY(orn_launch_batch_stats(e->b_stats, o.batch, cur, stats_out, st));
+    }
     if (d.erb) ORN_TRY(merge_backward(e, e->mset[pipe ? 1 : 0], st, sc));
     if (pipe) {
         // this stream's Adam launch covers everything below the last block; its skip decision is mirrored for the side branch's launch
@@ -995,6 +1089,69 @@ extern "C" int orn_engine_train_steps(orn_engine *e, const float *frames, const 
         if (hrc != hipSuccess && rc == 0) { orn_set_error("engine_train_steps: join: %s", hipGetErrorString(hrc)); rc = (int)hrc; }
     }
     return rc;
+}
+
+// ---- batched step (-b B): B frames per optimiser step, gradients summed on the device (include/orn.h, N5) ----
+// batch workspace, in floats: the accumulation arena (arena layout, so a range has one offset in both), the frame table, the
+// per-frame stats
+static size_t batch_ws_layout(const orn_engine_desc *d, int max_batch, size_t *cur_off, size_t *stats_off)
+{
+    size_t off = al((size_t)d->n_params);
+    if (cur_off) *cur_off = off;
+    off += al((sizeof(OrnStepCur) * (size_t)max_batch + 3) / 4);
+    if (stats_off) *stats_off = off;
+    off += al((size_t)8 * max_batch);
+    return off * 4;
+}
+
+extern "C" size_t orn_engine_batch_ws_bytes(const orn_engine_desc *d, int max_batch)
+{
+    if (max_batch < 1 || max_batch > ORN_MAX_BATCH || check_desc(d) != 0) return 0;
+    return batch_ws_layout(d, max_batch, nullptr, nullptr);
+}
+
+extern "C" int orn_engine_set_batch_ws(orn_engine *e, void *ws, size_t bytes, int max_batch)
+{
+    ORN_REQUIRE(e, "engine_set_batch_ws: null engine");
+    if (!ws) { e->b_acc = nullptr; e->b_cur = nullptr; e->b_stats = nullptr; e->b_max = 0; return 0; }
+    ORN_REQUIRE(max_batch >= 1 && max_batch <= ORN_MAX_BATCH, "engine_set_batch_ws: max_batch=%d outside [1, %d]", max_batch, ORN_MAX_BATCH);
+    ORN_REQUIRE((uintptr_t)ws % 256 == 0, "engine_set_batch_ws: workspace must be 256-byte aligned");
+    const OrnAccumTable &t = e->acc_tab;
+    for (int r = 0; r < t.n; ++r)       // (the accumulate launch writes exactly these ranges of both arenas)
+        ORN_REQUIRE(t.off[r] >= 0 && t.len[r] > 0 && t.off[r] + t.len[r] <= e->d.n_params,
+                    "engine_set_batch_ws: gradient range %d [%lld, +%lld) lies outside the arena", r, (long long)t.off[r], (long long)t.len[r]);
+    size_t cur_off, stats_off;
+    const size_t need = batch_ws_layout(&e->d, max_batch, &cur_off, &stats_off);
+    if (bytes < need) { orn_set_error("engine_set_batch_ws: workspace %zu < %zu", bytes, need); return ORN_E_WS; }
+    e->b_acc = (float *)ws;
+    e->b_cur = (OrnStepCur *)((float *)ws + cur_off);
+    e->b_stats = (float *)ws + stats_off;
+    e->b_max = max_batch;
+    return 0;
+}
+
+// n_steps optimiser steps of `batch` frames each, serial form, on the caller's stream: per step the batched advance, then the
+// frames one behind the other (train_step, StepOpts::batch).
+extern "C" int orn_engine_train_steps_batch(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                                            int32_t *cursor, float *stats_out, int32_t n_slots, int32_t n_steps, int32_t batch, void *stream)
+{
+    ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps_batch: bad arguments");
+    ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps_batch: engine was created without grads / Adam arenas");
+    ORN_REQUIRE(e->b_acc, "engine_train_steps_batch: no batch workspace (orn_engine_set_batch_ws)");
+    ORN_REQUIRE(batch >= 1 && batch <= e->b_max, "engine_train_steps_batch: batch=%d outside [1, %d] (max_batch of the workspace)", batch, e->b_max);
+    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
+    hipStream_t st = (hipStream_t)stream;
+    StepOpts o;
+    o.advance = 0;
+    o.batch = batch;
+    for (int k = 0; k < n_steps; ++k) {
+        hipLaunchKernelGGL(k_advance_batch, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, e->d.beta1, e->d.beta2, e->cur, e->b_cur, (int)batch,
+                           e->sc /* all entries */);
+        ORN_LAUNCH_CHECK("advance_batch");
+        for (o.bframe = 0; o.bframe < batch; ++o.bframe)
+            ORN_TRY(train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, st, o));
+    }
+    return 0;
 }
 
 // One EAGER training step with HIP events around every layer's forward conv launch, on the launch stream:

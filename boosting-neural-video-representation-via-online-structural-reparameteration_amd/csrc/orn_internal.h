@@ -23,6 +23,15 @@ int orn_launch_adam(float *p, const float *g, float *m, float *v, size_t n, doub
                     OrnScaleState *mirror = nullptr,       // (engine, deferred last block) the skip decision is also stored into mirror->mirrored
                     bool count_skip = true,                // false: a skipped launch does not count (the step's other Adam launch does)
                     OrnScaleState *late = nullptr);        // (side branch) a skip of sc->flag alone, not mirrored, counts in late->late_skipped
+// Batched step (orn_engine_train_steps_batch): the gradient slots the backward writes directly, as ranges of the arena (floats;
+// 2 per block + the head's 2 + the stem's 4).  blk_end[r]: work-groups of ranges 0..r (ORN_ACCUM_CHUNK floats each).
+#define ORN_ACCUM_MAX_RANGES (2 * ORN_MAX_LAYERS + 6)
+#define ORN_ACCUM_CHUNK 2048
+struct OrnAccumTable { int n; int blk_end[ORN_ACCUM_MAX_RANGES]; int64_t off[ORN_ACCUM_MAX_RANGES], len[ORN_ACCUM_MAX_RANGES]; };
+// mode 0 (first frame): acc = g;  1: acc = acc + g;  2 (last frame): g = (acc + g) * inv_b, one rounded multiply
+int orn_launch_grad_accum(const OrnAccumTable &t, float *g, float *acc, int mode, float inv_b, hipStream_t st);
+// per-frame stats [B][8] (the loss finalize's records) -> the optimiser step's ring record at cur->slot, means in double
+int orn_launch_batch_stats(const float *frame_stats, int B, const OrnStepCur *cur, float *ring, hipStream_t st);
 
 // orn_stage0.hip: the fp32 block below the first 16-bit one (tiny stem image), forward / backward as one launch each
 bool orn_stage0_supported(int C, int O, int H, int W, int s);

@@ -297,13 +297,20 @@ class TrainEngine(_Decoding):
         self._sched_len = arr.shape[0]
 
     # ---- stepping -----------------------------------------------------------------------------
-    def run(self, n_steps: int, graph=None):
+    def run(self, n_steps: int, graph=None, batch: int = 1):
         """Enqueue `n_steps` optimiser steps consuming the uploaded schedule (no host sync).
+        batch > 1 (-b B, main_train.py:205-254): every optimiser step takes `batch` consecutive schedule entries -- the caller
+        uploads n_steps * batch of them -- and applies the mean of their frames' gradients (orn_engine_train_steps_batch: serial
+        form, no graph form); `global_step` and applied_steps() count optimiser steps.
         graph=None (default): orn_engine_train_steps -- plain stream launches, pipelined over the engine's second stream where the
         engine can (16-bit modes; include/orn.h); graph=True: hipGraph replay of the serial step; graph=False: one
         orn_engine_train_step call per step.  All three give bit-identical results, except for a step that only the pipelined form's
         late overflow checks flag (a late-only skip: the serial forms skip the whole step, the pipelined form all but the lower
         blocks' update; counted in scale_state()['late_skipped'], include/orn.h)."""
+        if batch != 1:
+            if graph:
+                raise OrnError('run: the batched step has no graph form (graph=True with batch > 1)')
+            return self.run_batched(n_steps, batch)
         if self.frames is None or self.sched is None:
             raise OrnError('set_video() and set_schedule() first')
         cur = torch.cuda.current_stream()
@@ -322,6 +329,32 @@ class TrainEngine(_Decoding):
                 check(lib().orn_engine_train_step(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
                                                   _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots), st),
                       'orn_engine_train_step')
+        cur.wait_stream(self.stream)
+        self.global_step += n_steps
+
+    def run_batched(self, n_steps: int, batch: int):
+        """`n_steps` optimiser steps of `batch` frames each through orn_engine_train_steps_batch (what run() calls for batch > 1;
+        batch = 1 gives the bits of the single-frame step).  The batch workspace is allocated on first use and grows with `batch`."""
+        if self.frames is None or self.sched is None:
+            raise OrnError('set_video() and set_schedule() first')
+        if not 1 <= batch <= _lib.ORN_MAX_BATCH:
+            raise OrnError(f'run: batch={batch} outside [1, {_lib.ORN_MAX_BATCH}]')
+        if n_steps * batch > getattr(self, '_sched_len', 0):
+            raise OrnError(f'run: {n_steps} steps of {batch} frames need {n_steps * batch} schedule entries, {getattr(self, "_sched_len", 0)} uploaded')
+        if getattr(self, '_batch_max', 0) < batch:
+            nbytes = lib().orn_engine_batch_ws_bytes(byref(self.desc), batch)
+            if nbytes == 0:
+                raise OrnError('orn_engine_batch_ws_bytes: ' + _lib.last_error())
+            torch.cuda.synchronize()                            # (steps in flight may still use the workspace this one replaces)
+            self._batch_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            check(lib().orn_engine_set_batch_ws(self._h, _lib.ptr(self._batch_ws), c_size_t(nbytes), batch), 'orn_engine_set_batch_ws')
+            self._batch_max = batch
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        check(lib().orn_engine_train_steps_batch(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
+                                                 _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots),
+                                                 c_int32(n_steps), c_int32(batch), c_void_p(self.stream.cuda_stream)),
+              'orn_engine_train_steps_batch')
         cur.wait_stream(self.stream)
         self.global_step += n_steps
 

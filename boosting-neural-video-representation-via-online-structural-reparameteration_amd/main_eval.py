@@ -126,6 +126,10 @@ def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
 
 def main(argv=None):
     args = eval_parser().parse_args(argv)
+    if args.finetune and args.batchSize > 1:
+        # the fine-tune's loop takes one frame per optimiser step; a -b it ignored would silently be another recipe
+        raise ValueError(f'--finetune with -b/--batchSize {args.batchSize}: the prune fine-tune steps one frame at a time; use -b 1 '
+                         '(batched steps are built for main_train only)')
     args.warmup = int(args.warmup * args.epochs)          # main_eval.py:106 (as main_train.parse_args): warm-up in epochs
     outf = os.path.join('result', args.outf, f'{args.suffix}')
     # a job that fitted several videos wrote one sub-directory per video (main_train.video_outf)

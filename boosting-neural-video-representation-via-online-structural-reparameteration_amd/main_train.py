@@ -287,6 +287,29 @@ def train(args):
 FALLBACK = {'fp16': 'bf16', 'bf16': 'fp32'}
 
 
+def check_batch_size(B: int, n: int):
+    """-b / --batchSize against the number of training frames (the loader drops the last partial batch, main_train.py:205)."""
+    if B < 1 or B > oeng._lib.ORN_MAX_BATCH:
+        raise ValueError(f'-b/--batchSize {B}: the engine takes 1 to {oeng._lib.ORN_MAX_BATCH} frames per optimiser step')
+    if B > n:
+        raise ValueError(f'-b/--batchSize {B} is larger than the {n} training frames: with drop_last an epoch would have no step')
+
+
+def epoch_entries(order, epoch, n, B, args, skipped_carry=0):
+    """The schedule entries (frame, Adam step, lr) of one epoch, main_train.py:205-254 with DataLoader(batch_size=B, drop_last=True):
+    `order` is the epoch's permutation (already cut short by --debug), of which len(order) // B batches are used; batch i takes
+    frames order[i*B:(i+1)*B] and the LR of adjust_lr(epoch, i, n): `i` is the BATCH index while data_size stays the frame count n
+    (main_train.py:247, kept).  Adam's step advances by one per batch; every entry of a batch carries the batch's step and lr (the
+    engine reads them from the first).  skipped_carry: steps skipped by engines a precision fall-back replaced."""
+    steps = len(order) // B
+    entries = []
+    for i in range(steps):
+        step = epoch * steps + i + 1 - skipped_carry
+        lr = utils.lr_value(epoch % args.epochs, i, n, args)
+        entries += [(f, step, lr) for f in order[i * B:(i + 1) * B]]
+    return entries
+
+
 def fit_video(args, name, vid_index, rank, _inject=None):
     """One fit.  _inject(epoch, eng): test hook, called after the epoch's start-of-epoch snapshot."""
     torch.manual_seed(args.manualSeed)                              # main_train.py:162
@@ -320,7 +343,10 @@ def fit_video(args, name, vid_index, rank, _inject=None):
     best = Best()
     best_snap, best_dirty = None, False
     start = time.time()
-    steps_per_epoch = min(n, 11) if args.debug else n
+    B = args.batchSize
+    frames_per_epoch = min(n, 11) if args.debug else n
+    check_batch_size(B, frames_per_epoch)
+    steps_per_epoch = frames_per_epoch // B                         # optimiser steps (drop_last)
     skipped_before = 0
     epoch = 0
     while epoch < args.epochs:
@@ -328,16 +354,15 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         if _inject is not None:
             _inject(epoch, eng)
         g.manual_seed(args.manualSeed + epoch)
-        order = torch.randperm(n, generator=g).tolist()[:steps_per_epoch]
+        order = torch.randperm(n, generator=g).tolist()[:frames_per_epoch]
         # Adam's step numbers: the device subtracts the steps THIS engine skipped; steps skipped by an engine a fall-back replaced
         # (eng.skipped_carry) are taken off here, so the bias corrections count applied steps only, whatever the history
-        entries = [(f, epoch * steps_per_epoch + i + 1 - eng.skipped_carry, utils.lr_value(epoch % args.epochs, i, n, args))
-                   for i, f in enumerate(order)]
+        entries = epoch_entries(order, epoch, n, B, args, eng.skipped_carry)
         eng.set_schedule(entries)
-        eng.run(len(entries))
-        st = eng.stats(len(entries))                                 # syncs once per epoch
+        eng.run(steps_per_epoch, batch=B)                            # B = 1: the pipelined single-frame step, as ever
+        st = eng.stats(steps_per_epoch)                              # syncs once per epoch
         sc = eng.scale_state()                                       # (the stats read above has already synchronised)
-        warn = skipped_steps_warning(skipped_before, steps_skipped(sc), len(entries), precision, sc['scale'])
+        warn = skipped_steps_warning(skipped_before, steps_skipped(sc), steps_per_epoch, precision, sc['scale'])
         if warn and precision in FALLBACK:
             # The fit has left this precision's number range: skipped steps change nothing, so it
             # would burn the remaining epochs.  Go back to the start of this epoch and continue in the next wider
@@ -366,7 +391,7 @@ def fit_video(args, name, vid_index, rank, _inject=None):
             best.train_psnr = train_psnr
             best_snap, best_dirty = Snapshot(eng, epoch), True
         line = (f'[{time.strftime("%Y/%m/%d %H:%M:%S")}] Rank:{rank}, Video:{name}, Epoch[{epoch + 1}/{args.epochs}], lr:{st[-1, 5]:.2e} '
-                f'PSNR: {train_psnr:.2f}, best: {float(best.train_psnr):.2f}, loss: {st[:, 0].mean():.5f}, '
+                f'PSNR: {train_psnr:.2f}, best: {float(best.train_psnr):.2f}, loss: {st[:, 0].mean():.5f}, steps: {steps_per_epoch}, '
                 f'{(time.time() - start) / (epoch + 1):.3f} s/epoch')
         say(line, console=epoch % max(1, args.print_freq // 10) == 0 or epoch == args.epochs - 1)
         is_eval = (epoch + 1) % args.eval_freq == 0 or epoch > args.epochs - 10     # main_train.py:303
@@ -405,7 +430,7 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         say(f'precision: started in {args.precision}, finished in {precision}')
     say(f'Training complete in: {time.time() - start:.1f}s', console=False)
     log.close()
-    return float(best.train_psnr), float(args.epochs * steps_per_epoch), float(eng.global_step)
+    return float(best.train_psnr), float(args.epochs * steps_per_epoch * B), float(eng.global_step)
 
 
 def main(argv=None):

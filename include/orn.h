@@ -36,7 +36,8 @@ extern "C" {
 
 #define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames;
                                   * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
-                                  * orn_loss_ws_bytes_for */
+                                  * orn_loss_ws_bytes_for; + ORN_MAX_BATCH, orn_engine_batch_ws_bytes, orn_engine_set_batch_ws,
+                                  * orn_engine_train_steps_batch */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -325,6 +326,35 @@ ORN_API int orn_engine_train_steps(orn_engine *e, const float *frames, const flo
 ORN_API int orn_engine_train_steps_graph(orn_engine *e, const float *frames, const float *embeds,
                                  const orn_step_sched *sched, int32_t *cursor, float *stats_out,
                                  int32_t n_slots, int32_t n_steps, void *stream);
+/* ---- N5  -b / --batchSize: B frames per optimiser step                main_train.py:205-254, utils.py:139-199 ----
+ * loss_fn on a stacked batch is the mean over its frames of the single-frame loss (L1 / MSE: means over all elements; ssim /
+ * ms_ssim with size_average: means over B*Ch planes), so the batch gradient is the mean of the per-frame gradients.  A batched
+ * step runs, on the caller's stream alone (serial form: no side stream, no graph):
+ *   the batched advance (flags and scale once per optimiser step, one clean step credited, the frame table filled);
+ *   frame 0: the single-frame step's launches up to its last directly written gradient (merge forward included);
+ *   frames 1..B-1: the same with the forward's merge left out -- the parameters have not changed, so the merged kernels, their
+ *     16-bit operand copies and the merge backward's half copies of frame 0 stay valid;
+ *   behind each frame one accumulate launch over the slots the backward writes directly (ERB: every block's w3x3 / b3x3 slot,
+ *     which holds dWf / dbf; the head's and the stem's tensors; vanilla: every slot), frames summed in fp32 in frame order,
+ *     ((g0 + g1) + g2) + ...; frame 0 writes the accumulator (no zeroing pass), the last frame's launch writes
+ *     G = (acc + g_last) * (1.0f / B), one rounded multiply, back into the gradient arena (B == 1: no launch, G is frame 0's);
+ *   then ONE merge backward (ERB; it is linear in dWf), the batch record, ONE Adam launch.
+ * No atomics: run-to-run bit-identical.  The loss scale is constant within a step; a non-finite value in any frame skips the whole
+ * optimiser step (parameters and moments untouched, `skipped` + 1, one halving at the next advance, Adam's count excludes it).
+ * Ring record of an optimiser step, slot (optimiser-step index % n_slots) with the index = cursor / batch at its start:
+ * {loss, L1, MSE, s, PSNR, lr, frame, step}: loss, L1, MSE, s are the means over the frames, summed in double in frame order;
+ * PSNR = -10 log10 of the batch-mean MSE (psnr_fn takes the MSE over the whole batch, utils.py:191); frame is the batch's first.
+ * An optimiser step consumes `batch` consecutive schedule entries: the frames come from all of them, step and lr from the first.
+ * batch == 1 gives the bits of orn_engine_train_step.
+ * The batch workspace is caller-owned device memory (256-byte aligned, alive while set; null removes it): the accumulation arena
+ * (arena layout), the frame table of the step in flight and [max_batch][8] per-frame stats.  The engine's own workspace is
+ * unchanged by it.  ORN_E_ARG for a missing workspace, batch < 1 or batch > max_batch. */
+#define ORN_MAX_BATCH 16
+ORN_API size_t orn_engine_batch_ws_bytes(const orn_engine_desc *d, int max_batch);      /* 0 on bad arguments */
+ORN_API int orn_engine_set_batch_ws(orn_engine *e, void *ws, size_t bytes, int max_batch);
+ORN_API int orn_engine_train_steps_batch(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                                 int32_t *cursor, float *stats_out, int32_t n_slots, int32_t n_steps, int32_t batch,
+                                 void *stream);
 /* Dynamic loss scale + non-finite guard (the reference trains in fp32 and has neither; torch.cuda.amp.GradScaler is the
  * model).  The 16-bit gradient tensors of precision 2 travel multiplied by a scale held in device memory (2^20 at creation;
  * 1 for the other precisions).  A step whose gradients (or loss) are not finite leaves parameters and Adam moments untouched
