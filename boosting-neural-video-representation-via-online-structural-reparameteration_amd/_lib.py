@@ -105,6 +105,8 @@ _SIGS = {
     'orn_engine_batch_ws_bytes': (c_size_t, [POINTER(EngineDesc), c_int]),
     'orn_engine_set_batch_ws': (c_int, [P, P, c_size_t, c_int]),
     'orn_engine_train_steps_batch': (c_int, [P, P, P, P, P, P, c_int32, c_int32, c_int32, P]),
+    'orn_engine_step_forward': (c_int, [P, P, P, P, P, c_int32, POINTER(c_void_p), P]),
+    'orn_engine_step_backward': (c_int, [P, P, P, P, P, P, c_int32, P]),
     'orn_engine_profile_step': (c_int, [P, P, P, P, P, P, c_int32, P, P]),
     'orn_engine_set_grad_mask': (c_int, [P, P]),
     'orn_engine_set_target_stats': (c_int, [P, P]),

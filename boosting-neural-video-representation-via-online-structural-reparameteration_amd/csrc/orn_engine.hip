@@ -103,6 +103,10 @@ struct orn_engine {
     OrnStepCur *b_cur;
     float *b_stats;
     int b_max;
+    // Split step (orn_engine_step_forward / orn_engine_step_backward): the forward half has run on open_st and its activations wait
+    // for the backward half; every other entry that would overwrite them is refused meanwhile (ORN_E_STATE)
+    bool open;
+    hipStream_t open_st;
     // orn_engine_profile_step: HIP events around every forward conv launch of an eager step
     bool prof;
     hipEvent_t prof_ev[4 * ORN_MAX_LAYERS + 4];      // pairs: forward conv of layer i, dgrad launch of layer i, wgrad batch, its reduction
@@ -110,6 +114,16 @@ struct orn_engine {
 
 #define ORN_GRAPH_UNROLL 4
 static_assert(ORN_SCALE_SLOTS >= ORN_GRAPH_UNROLL, "one scale-state entry per step of the unrolled graph");
+
+// While a split step is open the engine's activations belong to its backward: every other stepping, decoding and evaluation
+// entry is refused until orn_engine_step_backward has closed it.
+#define ORN_REQUIRE_CLOSED(e, name)                                                                                         \
+    do {                                                                                                                    \
+        if ((e)->open) {                                                                                                    \
+            orn_set_error(name ": a split step is open (orn_engine_step_forward); orn_engine_step_backward closes it");    \
+            return ORN_E_STATE;                                                                                             \
+        }                                                                                                                   \
+    } while (0)
 
 static inline size_t al(size_t floats) { return orn_align(floats * 4) / 4; }
 
@@ -309,6 +323,7 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     e->ws = (float *)ws;
     e->graph = nullptr; e->graph_exec = nullptr; e->graph_u = nullptr; e->graph_exec_u = nullptr;
     e->prof = false;
+    e->open = false; e->open_st = nullptr;
     for (int k = 0; k < 3; ++k) { e->mset[k].n = 0; e->mset[k].mh_host = nullptr; }
     e->side = nullptr;
     for (auto ev : SIDE_EVENTS) e->*ev = nullptr;
@@ -741,6 +756,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
 extern "C" int orn_engine_decode(orn_engine *e, const float *embed, float *img, void *stream)
 {
     ORN_REQUIRE(e && embed && img, "engine_decode: null pointer");
+    ORN_REQUIRE_CLOSED(e, "engine_decode");
     hipStream_t st = (hipStream_t)stream;
     ORN_TRY(forward(e, embed, nullptr, false, st));
     hipError_t rc = hipMemcpyAsync(img, e->img, (size_t)3 * e->Hout * e->Wout * 4, hipMemcpyDeviceToDevice, st);
@@ -784,6 +800,7 @@ extern "C" int orn_engine_decode_frames(orn_engine *e, const float *embeds, cons
                                         uint8_t *rgb8, float *img, float *stats, void *stream)
 {
     ORN_REQUIRE(e && embeds, "engine_decode_frames: null engine / embeds");
+    ORN_REQUIRE_CLOSED(e, "engine_decode_frames");
     ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_decode_frames: n=%d frames need a device array of n row indices", n);
     ORN_REQUIRE(rgb8 || img || stats, "engine_decode_frames: no output asked for (rgb8, img and stats are all null)");
     ORN_REQUIRE(!stats || targets, "engine_decode_frames: stats need targets");
@@ -812,6 +829,7 @@ extern "C" int orn_engine_eval_frames(orn_engine *e, const float *embeds, const 
 {
     if (!msssim) return orn_engine_decode_frames(e, embeds, rows, n, targets, rgb8, img, stats, stream);
     ORN_REQUIRE(e && embeds, "engine_eval_frames: null engine / embeds");
+    ORN_REQUIRE_CLOSED(e, "engine_eval_frames");
     ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_eval_frames: n=%d frames need a device array of n row indices", n);
     ORN_REQUIRE(targets, "engine_eval_frames: msssim needs targets");
     ORN_REQUIRE((e->Hout < e->Wout ? e->Hout : e->Wout) > 160, "engine_eval_frames: msssim: image side must exceed 160 (got %dx%d)", e->Hout, e->Wout);
@@ -960,9 +978,27 @@ struct StepOpts {
     int batch = 0, bframe = 0;
 };
 
-// forward -> loss / head -> dgrad chain -> stem -> weight gradients -> merge backward -> Adam
-static int train_step(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
-                      int32_t *cursor, float *stats_out, int32_t n_slots, hipStream_t st, const StepOpts &o = StepOpts())
+// A step in two halves, split at the loss: step_front produces e->img (schedule advance + training forward), step_back consumes
+// dLoss/dimg and the loss's finalize job (head -> dgrad chain -> stem -> weight gradients -> merge backward -> Adam).  train_step runs
+// a built-in loss between them; the split entries (orn_engine_step_forward / _backward) leave that place to the caller.
+static OrnStepCur *step_cur(const orn_engine *e, const StepOpts &o) { return o.batch > 0 ? e->b_cur + o.bframe : e->cur + o.cur; }
+
+static int step_front(orn_engine *e, const float *embeds, const orn_step_sched *sched, int32_t *cursor, int32_t n_slots, hipStream_t st,
+                      const StepOpts &o)
+{
+    const orn_engine_desc &d = e->d;
+    if (o.advance > 0) {
+        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, d.beta1, d.beta2, e->cur, o.advance, e->sc /* all entries */);
+        ORN_LAUNCH_CHECK("advance");
+    }
+    const int *fidx = &step_cur(e, o)->frame;
+    return forward(e, embeds, fidx, true, st, (o.batch > 0 && o.bframe > 0) ? (int)MERGE_NONE : (o.pipe && e->side_busy) ? 1 : 0);
+}
+
+// dimg: dLoss/d(e->img), fp32 planar (the engine's own buffer, or the caller's in a split step); fin: the loss's finalize stage for a
+// 16-bit engine's head backward to carry (n_l1 == 0: none)
+static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnLossFinalJob &fin, float *stats_out, hipStream_t st,
+                     const StepOpts &o)
 {
     const orn_engine_desc &d = e->d;
     const bool pipe = o.pipe;
@@ -970,27 +1006,18 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
     const int Nout = d.fc_h * d.fc_w * d.fc_dim;
     const size_t HWo = (size_t)e->Hout * e->Wout;
     const bool batched = o.batch > 0;
-    OrnStepCur *cur = batched ? e->b_cur + o.bframe : e->cur + o.cur;
-    if (o.advance > 0) {
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, sched, cursor, n_slots, d.beta1, d.beta2, e->cur, o.advance, e->sc /* all entries */);
-        ORN_LAUNCH_CHECK("advance");
-    }
+    OrnStepCur *cur = step_cur(e, o);
     OrnScaleState *const sc = e->sc + o.cur;            // this step's entry: its own flag, the shared scale
     const int *fidx = &cur->frame;
-    ORN_TRY(forward(e, embeds, fidx, true, st, (batched && o.bframe > 0) ? (int)MERGE_NONE : (pipe && e->side_busy) ? 1 : 0));
     const int nl = d.n_layers, ff = e->ff;
-    OrnLossFinalJob fin = {};
-    ORN_TRY(orn_launch_loss(e->img, frames, fidx, 3 * HWo, 1, 3, e->Hout, e->Wout, d.loss_type, 1.0f, e->stats, e->dimg,
-                            e->loss_ws, st, cur, batched ? e->b_stats : stats_out, sc, orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? e->tstats : nullptr,
-                            ff < nl ? &fin : nullptr));     // 16-bit engine: the finalize stage rides on the head's backward launch
     if (pipe) { fin.cur_copy = e->cur_side; fin.sc_copy = e->sc_side; }     // (the previous step's side branch was joined in forward())
     if (ff < nl)
-        ORN_TRY(e->ops->head_bwd(e->L[nl - 1].zb, P + d.head_w, e->img, e->dimg, e->Cn_last, e->Hout, e->Wout, d.sigmoid,
+        ORN_TRY(e->ops->head_bwd(e->L[nl - 1].zb, P + d.head_w, e->img, dimg, e->Cn_last, e->Hout, e->Wout, d.sigmoid,
                                  d.layer[nl - 1].s, e->gs, e->L[nl - 1].dypad, nullptr, nullptr, e->head_ws, st, sc, &fin));   // dW / db: finished with the wgrad batch
     const bool head_fused32 = f32_head_on_z(e);
-    const OrnHeadBwdFuse hfuse = {P + d.head_w, e->img, e->dimg, d.sigmoid, G + d.head_w, G + d.head_b, e->head_ws};
+    const OrnHeadBwdFuse hfuse = {P + d.head_w, e->img, dimg, d.sigmoid, G + d.head_w, G + d.head_b, e->head_ws};
     if (ff >= nl && !head_fused32)
-        ORN_TRY(orn_launch_head_bwd(e->L[nl - 1].a, P + d.head_w, e->img, e->dimg, 1, e->Cn_last, HWo, d.sigmoid, e->L[nl - 1].da,
+        ORN_TRY(orn_launch_head_bwd(e->L[nl - 1].a, P + d.head_w, e->img, dimg, 1, e->Cn_last, HWo, d.sigmoid, e->L[nl - 1].da,
                                     G + d.head_w, G + d.head_b, e->scratch, st));
     if (ff >= nl) {
         // fp32 engine: every layer's dgrad kernel (flipped taps, transposed) in one launch instead of one per layer
@@ -1058,13 +1085,68 @@ static int train_step(orn_engine *e, const float *frames, const float *embeds, c
     return 0;
 }
 
+// forward -> loss -> backward -> Adam: both halves around the engine's own loss
+static int train_step(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                      int32_t *cursor, float *stats_out, int32_t n_slots, hipStream_t st, const StepOpts &o = StepOpts())
+{
+    const orn_engine_desc &d = e->d;
+    ORN_TRY(step_front(e, embeds, sched, cursor, n_slots, st, o));
+    const OrnStepCur *cur = step_cur(e, o);
+    OrnLossFinalJob fin = {};
+    ORN_TRY(orn_launch_loss(e->img, frames, &cur->frame, (size_t)3 * e->Hout * e->Wout, 1, 3, e->Hout, e->Wout, d.loss_type, 1.0f, e->stats, e->dimg,
+                            e->loss_ws, st, cur, o.batch > 0 ? e->b_stats : stats_out, e->sc + o.cur,
+                            orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? e->tstats : nullptr,
+                            e->ff < d.n_layers ? &fin : nullptr));     // 16-bit engine: the finalize stage rides on the head's backward launch
+    return step_back(e, embeds, e->dimg, fin, stats_out, st, o);
+}
+
 extern "C" int orn_engine_train_step(orn_engine *e, const float *frames, const float *embeds,
                                      const orn_step_sched *sched, int32_t *cursor, float *stats_out, int32_t n_slots,
                                      void *stream)
 {
     ORN_REQUIRE(e && frames && embeds && sched && cursor, "engine_train_step: null pointer");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_step: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_train_step");
     return train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, (hipStream_t)stream);
+}
+
+// ---- the split step: the caller's own loss between the two halves (include/orn.h) ----
+extern "C" int orn_engine_step_forward(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                                       int32_t *cursor, int32_t n_slots, const float **pred, void *stream)
+{
+    ORN_REQUIRE(e && frames && embeds && sched && cursor && pred, "engine_step_forward: null pointer");
+    ORN_REQUIRE(e->grads && e->m && e->v, "engine_step_forward: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_step_forward");
+    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
+    ORN_TRY(step_front(e, embeds, sched, cursor, n_slots, (hipStream_t)stream, StepOpts()));
+    *pred = e->img;
+    e->open = true;
+    e->open_st = (hipStream_t)stream;
+    return 0;
+}
+
+extern "C" int orn_engine_step_backward(orn_engine *e, const float *frames, const float *embeds, const float *dpred,
+                                        const float *loss, float *stats_out, int32_t n_slots, void *stream)
+{
+    ORN_REQUIRE(e && frames && embeds, "engine_step_backward: null pointer");
+    (void)n_slots;                  // (the ring slot was fixed by the forward half's advance)
+    if (!e->open) {
+        orn_set_error("engine_step_backward: no open step (orn_engine_step_forward first)");
+        return ORN_E_STATE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ORN_REQUIRE(st == e->open_st, "engine_step_backward: not the stream of the step's forward half");
+    ORN_REQUIRE((uintptr_t)dpred % 4 == 0 && (uintptr_t)loss % 4 == 0, "engine_step_backward: dpred / loss must be float-aligned");
+    e->open = false;
+    const orn_engine_desc &d = e->d;
+    const OrnStepCur *cur = e->cur;
+    ORN_TRY(orn_launch_loss_ext(e->img, frames, &cur->frame, (size_t)3 * e->Hout * e->Wout, 3, e->Hout, e->Wout, dpred, loss, e->stats,
+                                e->loss_ws, st, cur, stats_out, e->sc));
+    if (!dpred)                     // abandoned: the flag is up, so this launch changes nothing and counts the skipped step
+        return orn_launch_adam(e->params, e->grads, e->m, e->v, (size_t)d.n_params, 0.0, 1, cur, d.beta1, d.beta2, d.eps, 1.0f, st, e->gmask,
+                               e->sc, e->sc);
+    OrnLossFinalJob none = {};      // (16-bit engines: nothing rides on the head's backward launch)
+    return step_back(e, embeds, dpred, none, stats_out, st, StepOpts());
 }
 
 // n_steps steps enqueued on `stream` (no graph): where the engine can (struct orn_engine, `side`) in the pipelined form, the
@@ -1075,6 +1157,7 @@ extern "C" int orn_engine_train_steps(orn_engine *e, const float *frames, const 
 {
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_train_steps");
     hipStream_t st = (hipStream_t)stream;
     int rc = 0;
     StepOpts o;
@@ -1137,6 +1220,7 @@ extern "C" int orn_engine_train_steps_batch(orn_engine *e, const float *frames, 
 {
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps_batch: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps_batch: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_train_steps_batch");
     ORN_REQUIRE(e->b_acc, "engine_train_steps_batch: no batch workspace (orn_engine_set_batch_ws)");
     ORN_REQUIRE(batch >= 1 && batch <= e->b_max, "engine_train_steps_batch: batch=%d outside [1, %d] (max_batch of the workspace)", batch, e->b_max);
     assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
@@ -1161,6 +1245,7 @@ extern "C" int orn_engine_profile_step(orn_engine *e, const float *frames, const
 {
     ORN_REQUIRE(e && frames && embeds && sched && cursor && ms_out, "engine_profile_step: null pointer");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_profile_step: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_profile_step");
     hipStream_t st = (hipStream_t)stream;
     const int nl = e->d.n_layers;
     for (int i = 0; i < 4 * ORN_MAX_LAYERS + 4; ++i)
@@ -1200,6 +1285,7 @@ extern "C" int orn_engine_train_steps_graph(orn_engine *e, const float *frames, 
 {
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps_graph: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps_graph: engine was created without grads / Adam arenas");
+    ORN_REQUIRE_CLOSED(e, "engine_train_steps_graph");
     hipStream_t st = (hipStream_t)stream;
     const bool same = e->graph_exec && e->g_frames == frames && e->g_embeds == embeds && e->g_sched == sched &&
                       e->g_cursor == cursor && e->g_stats == stats_out && e->g_slots == n_slots && e->g_stream == st;

@@ -132,6 +132,13 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
                     hipStream_t st, const OrnStepCur *cur = nullptr, float *ring = nullptr, OrnScaleState *sc = nullptr,
                     const float *tstats = nullptr,    // tstats: orn_loss_target_stats of the SAME frame table (SSIM kinds; indexed by *frame_idx)
                     OrnLossFinalJob *defer = nullptr);   // defer: the finalize stage is returned as a job instead of launched
+// The loss stage of a split step (orn_engine_step_backward): the caller supplies dLoss/dpred and the loss value (device; optional).
+// Two launches: per-tile {|d|, d^2} partials of pred - target[*frame_idx] + a NaN / inf scan of dpred into sc->flag, then a
+// one-work-group finalize (stats and ring record {loss, L1, MSE, 0, PSNR, ...}; a non-finite loss raises the flag).  dpred null:
+// the step is abandoned -- no scan, the flag goes up.  ws: orn_loss_ws_bytes(1, Ch, H, W) bytes.
+int orn_launch_loss_ext(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int Ch, int H, int W,
+                        const float *dpred, const float *loss, float *stats, float *ws, hipStream_t st, const OrnStepCur *cur,
+                        float *ring, OrnScaleState *sc);
 void orn_gauss_taps(float g[11]);        // pytorch_msssim _fspecial_gauss_1d(11, 1.5)
 // The five level launches of the batched MS-SSIM on F groups of Ch planes (no finalize); the pooled planes of levels 1..4 and the
 // per-tile partials stay in ws (orn_msssim_pyramid_floats) and are described by *out.

@@ -352,6 +352,108 @@ __global__ void __launch_bounds__(256) k_loss_finalize(OrnLossFinalJob j)
     orn_loss_finalize_block(j, sd);
 }
 
+// The loss of a SPLIT step (orn_engine_step_forward / orn_engine_step_backward): the caller computed the loss and dLoss/dpred itself.
+// What is left for the device: the {|d|, d^2} tile partials of pred - target that every built-in loss leaves in part_l1 (L1, MSE, PSNR
+// of the step's record), and a scan of the caller's gradient for NaN / inf (the step's flag: Adam then skips the step).  One 16x64
+// tile per work-group as in k_loss_grad; VEC4 (W % 4 == 0, 16-byte aligned planes): one float4 of each tensor per thread.
+struct LossExtP {
+    const float *pred, *target, *dpred;      // dpred null: no scan (an abandoned step)
+    const int *frame_idx;
+    size_t frame_stride;
+    int H, W, tiles_w;
+    float *part_l1;                          // [n_blocks][2]
+    OrnScaleState *sc;
+};
+
+template <bool VEC4>
+__global__ void __launch_bounds__(256) k_loss_ext(LossExtP q)
+{
+    __shared__ float sred[16];
+    const int t = threadIdx.x;
+    const int plane = blockIdx.y;
+    const int tw = blockIdx.x % q.tiles_w, th = blockIdx.x / q.tiles_w;
+    const int y0 = th * SS_TH, x0 = tw * SS_TW;
+    const size_t HW = (size_t)q.H * q.W;
+    const float *pp = q.pred + (size_t)plane * HW;
+    const float *tp = q.target + (q.frame_idx ? (size_t)(*q.frame_idx) * q.frame_stride : 0) + (size_t)plane * HW;
+    const float *gp = q.dpred ? q.dpred + (size_t)plane * HW : nullptr;
+    float sabs = 0.f, ssq = 0.f;
+    bool bad = false;
+    if (VEC4) {
+        const int r = t / (SS_TW / 4), c = (t - r * (SS_TW / 4)) * 4;
+        const int gy = y0 + r, gx = x0 + c;
+        if (gy < q.H && gx < q.W) {                        // W % 4 == 0: the whole float4 lies inside the row
+            const size_t o = (size_t)gy * q.W + gx;
+            const float4 p = *reinterpret_cast<const float4 *>(pp + o), tg = *reinterpret_cast<const float4 *>(tp + o);
+            const float d[4] = {p.x - tg.x, p.y - tg.y, p.z - tg.z, p.w - tg.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { sabs += fabsf(d[k]); ssq = fmaf(d[k], d[k], ssq); }
+            if (gp) {
+                const float4 g = *reinterpret_cast<const float4 *>(gp + o);
+                bad = !(fabsf(g.x) <= 3.0e38f) || !(fabsf(g.y) <= 3.0e38f) || !(fabsf(g.z) <= 3.0e38f) || !(fabsf(g.w) <= 3.0e38f);
+            }
+        }
+    } else {
+        for (int idx = t; idx < SS_TH * SS_TW; idx += 256) {
+            const int r = idx / SS_TW, c = idx - r * SS_TW;
+            const int gy = y0 + r, gx = x0 + c;
+            if (gy >= q.H || gx >= q.W) continue;
+            const size_t o = (size_t)gy * q.W + gx;
+            const float d = pp[o] - tp[o];
+            sabs += fabsf(d);
+            ssq = fmaf(d, d, ssq);
+            if (gp) bad = bad || !(fabsf(gp[o]) <= 3.0e38f);
+        }
+    }
+    if (bad) orn_flag_nonfinite(q.sc, __builtin_inff());
+    const float ta = orn_block_sum(sabs, sred);
+    const float tq = orn_block_sum(ssq, sred);
+    if (t == 0) {
+        const size_t bi = (size_t)plane * gridDim.x + blockIdx.x;
+        q.part_l1[2 * bi] = ta;
+        q.part_l1[2 * bi + 1] = tq;
+    }
+}
+
+// Finalize stage of the split step, one work-group: the partials summed as orn_loss_finalize_block sums them (strided per thread
+// in double, then the fixed tree), the step's stats and ring record, and the checks of what the caller handed in.
+struct LossExtFinal {
+    const float *part_l1; int n_l1; double n_elem;
+    const float *loss;             // the caller's loss value (device; null: the record holds 0)
+    int abandon;                   // the caller gave the step up: its flag goes up whatever the values
+    float *stats; const OrnStepCur *cur; float *ring; OrnScaleState *sc;
+};
+
+__global__ void __launch_bounds__(256) k_loss_ext_finalize(LossExtFinal j)
+{
+    __shared__ double sd[2 * 256];
+    const int t = threadIdx.x, nt = blockDim.x;
+    double a = 0.0, b = 0.0;
+    for (int i = t; i < j.n_l1; i += nt) { a += (double)j.part_l1[2 * i]; b += (double)j.part_l1[2 * i + 1]; }
+    sd[t] = a; sd[nt + t] = b;
+    __syncthreads();
+    for (int s = nt >> 1; s > 0; s >>= 1) {
+        if (t < s) { sd[t] += sd[t + s]; sd[nt + t] += sd[nt + t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const float l1 = (float)(sd[0] / j.n_elem);
+        const float mse = (float)(sd[nt] / j.n_elem);
+        const float loss = j.loss ? *j.loss : 0.f;
+        orn_flag_nonfinite(j.sc, loss);                // the caller's loss is NaN / inf: no update from this step
+        orn_flag_nonfinite(j.sc, mse);                 // so is the forward pass itself
+        if (j.abandon && j.sc) j.sc->flag = 1;
+        const float psnr = -10.0f * log10f(mse);
+        j.stats[0] = loss; j.stats[1] = l1; j.stats[2] = mse; j.stats[3] = 0.f; j.stats[4] = psnr;
+        j.stats[5] = 0.f; j.stats[6] = 0.f; j.stats[7] = 0.f;
+        if (j.ring) {
+            float *r = j.ring + (size_t)j.cur->slot * 8;
+            r[0] = loss; r[1] = l1; r[2] = mse; r[3] = 0.f; r[4] = psnr;
+            r[5] = j.cur->lr; r[6] = (float)j.cur->frame; r[7] = (float)j.cur->step;
+        }
+    }
+}
+
 static bool g_gauss_ready = false;
 
 // pytorch_msssim _fspecial_gauss_1d(11, 1.5): fp32 exp, fp32 normalise
@@ -497,6 +599,29 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
     if (defer) { *defer = fj; return 0; }              // the caller runs it as a rider of a later launch
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, st, fj);
     ORN_LAUNCH_CHECK("loss_finalize");
+    return 0;
+}
+
+// The loss stage of a split step (k_loss_ext + its finalize launch).  ws: orn_loss_ws_bytes floats, the part_l1 region of the layout
+// every loss type shares.  dpred null: the step is abandoned (no scan, the flag goes up).
+int orn_launch_loss_ext(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int Ch, int H, int W,
+                        const float *dpred, const float *loss, float *stats, float *ws, hipStream_t st, const OrnStepCur *cur,
+                        float *ring, OrnScaleState *sc)
+{
+    const LossGeom g = loss_geom(1, Ch, H, W);
+    LossExtP q;
+    q.pred = pred; q.target = target; q.dpred = dpred; q.frame_idx = frame_idx; q.frame_stride = frame_stride;
+    q.H = H; q.W = W; q.tiles_w = g.tw;
+    q.part_l1 = ws + g.off_pl;
+    q.sc = sc;
+    const bool vec4 = W % 4 == 0 && ((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx);
+    const dim3 gr(g.tw * g.th, g.planes), bl(256);
+    if (vec4) hipLaunchKernelGGL(k_loss_ext<true>, gr, bl, 0, st, q);
+    else hipLaunchKernelGGL(k_loss_ext<false>, gr, bl, 0, st, q);
+    ORN_LAUNCH_CHECK("loss_ext");
+    const LossExtFinal fj = {q.part_l1, g.planes * g.tw * g.th, (double)g.planes * H * W, loss, dpred ? 0 : 1, stats, cur, ring, sc};
+    hipLaunchKernelGGL(k_loss_ext_finalize, dim3(1), dim3(256), 0, st, fj);
+    ORN_LAUNCH_CHECK("loss_ext_finalize");
     return 0;
 }
 

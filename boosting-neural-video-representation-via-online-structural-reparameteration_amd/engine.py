@@ -7,6 +7,8 @@ memory), gradients and Adam state get arenas of the same shape, the video is res
 every step reads its frame index / LR / step count from a device-side schedule, so whole epochs are
 enqueued without a host sync -- as plain stream launches pipelined over the engine's second stream
 (`run()`'s default, orn_engine_train_steps) or as hipGraph replays of the serial step (`graph=True`).
+A loss the library does not build trains through the split step (`step_with` / `run_with`): the engine's
+forward, a torch function of its output on the caller's stream, the engine's backward and Adam.
 """
 import ctypes
 from ctypes import byref, c_int32, c_size_t, c_void_p
@@ -253,6 +255,10 @@ class TrainEngine(_Decoding):
         self.sched = None
         self.frames = None
         self.embeds = None
+        self._sched_host = None                            # host copy of the uploaded schedule and of the device cursor: which
+        self._cursor_host = 0                              # frame the next step takes is known without a sync (step_with)
+        self._sched_len = 0
+        self.open_frame = None
         self.global_step = 0
         self.skipped_carry = 0                             # steps skipped by engines this one replaced (main_train fall-back)
         self.out_hw = _out_hw(model)
@@ -295,6 +301,7 @@ class TrainEngine(_Decoding):
         self.sched[:arr.shape[0]].copy_(torch.from_numpy(arr), non_blocking=False)
         self.cursor.zero_()
         self._sched_len = arr.shape[0]
+        self._sched_host, self._cursor_host = arr, 0
 
     # ---- stepping -----------------------------------------------------------------------------
     def run(self, n_steps: int, graph=None, batch: int = 1):
@@ -331,6 +338,7 @@ class TrainEngine(_Decoding):
                       'orn_engine_train_step')
         cur.wait_stream(self.stream)
         self.global_step += n_steps
+        self._cursor_host += n_steps
 
     def run_batched(self, n_steps: int, batch: int):
         """`n_steps` optimiser steps of `batch` frames each through orn_engine_train_steps_batch (what run() calls for batch > 1;
@@ -357,6 +365,87 @@ class TrainEngine(_Decoding):
               'orn_engine_train_steps_batch')
         cur.wait_stream(self.stream)
         self.global_step += n_steps
+        self._cursor_host += n_steps * batch
+
+    # ---- the split step: a caller-supplied loss (orn_engine_step_forward / orn_engine_step_backward) --------------------------
+    def forward_step(self) -> torch.Tensor:
+        """First half of one optimiser step: the schedule advance and the training forward, enqueued without a host sync.
+        Returns the engine's output as a [1,3,H,W] fp32 VIEW into its workspace (no copy), ordered before the caller's current
+        stream.  The step is now open: until backward_step() every other stepping or decoding call of this engine raises OrnError.
+        `open_frame` holds the index of the step's frame (its target is frames[open_frame]), from the host copy of the schedule."""
+        if self.frames is None or self.sched is None:
+            raise OrnError('set_video() and set_schedule() first')
+        if self._cursor_host >= self._sched_len:
+            raise OrnError(f'forward_step: the uploaded schedule ({self._sched_len} entries) is used up')
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        pred = c_void_p()
+        check(lib().orn_engine_step_forward(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
+                                            _lib.ptr(self.cursor), c_int32(self.n_slots), byref(pred), c_void_p(self.stream.cuda_stream)),
+              'orn_engine_step_forward')
+        cur.wait_stream(self.stream)
+        self.open_frame = int(self._sched_host[self._cursor_host, 0])
+        self._cursor_host += 1
+        H, W = self.out_hw
+        off = pred.value - self.ws.data_ptr()                   # the pointer lies inside the engine's workspace tensor
+        assert 0 <= off and off + 12 * H * W <= self.ws.numel(), 'image pointer outside the workspace'
+        return self.ws[off:off + 12 * H * W].view(torch.float32).view(1, 3, H, W)
+
+    def backward_step(self, dpred: Optional[torch.Tensor], loss: Optional[torch.Tensor] = None):
+        """Second half: the backward from dpred = dLoss/dpred of the UNSCALED loss ([1,3,H,W] or [3,H,W], fp32, contiguous, on the
+        engine's device; read in place), merge backward and Adam, enqueued without a host sync.  loss: optional one-element device
+        tensor, the step's stats[0].  A NaN / inf in either skips the step (scale_state()['skipped']).  dpred=None abandons the
+        open step: nothing is applied and it counts as skipped."""
+        H, W = self.out_hw
+        if dpred is not None:
+            if not isinstance(dpred, torch.Tensor) or not dpred.is_cuda or dpred.device != self.device:
+                raise OrnError(f'backward_step: dpred must be a tensor on {self.device}')
+            if dpred.dtype != torch.float32 or tuple(dpred.shape) not in ((1, 3, H, W), (3, H, W)):
+                raise OrnError(f'backward_step: dpred {dpred.dtype} {tuple(dpred.shape)} vs float32 (1, 3, {H}, {W})')
+            if not dpred.is_contiguous():
+                raise OrnError('backward_step: dpred must be contiguous')
+        if loss is not None:
+            if not isinstance(loss, torch.Tensor) or not loss.is_cuda or loss.device != self.device or loss.numel() != 1:
+                raise OrnError(f'backward_step: loss must be a one-element tensor on {self.device}')
+            loss = loss.detach().to(torch.float32).reshape(1)
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        check(lib().orn_engine_step_backward(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(dpred), _lib.ptr(loss),
+                                             _lib.ptr(self.stats_ring), c_int32(self.n_slots), c_void_p(self.stream.cuda_stream)),
+              'orn_engine_step_backward')
+        cur.wait_stream(self.stream)
+        for t in (dpred, loss):                                 # allocated on the caller's stream, read on the engine's
+            if t is not None:
+                t.record_stream(self.stream)
+        self._seam_keep = (dpred, loss)
+        self.global_step += 1
+
+    def step_with(self, fn) -> torch.Tensor:
+        """One optimiser step on the objective fn(pred, target) -> scalar tensor: pred is the engine's output [1,3,H,W] (a leaf that
+        requires grad, sharing the engine's memory), target the step's frame [1,3,H,W]; fn is built from torch ops (and ops.LossFn)
+        on the current stream.  Its gradient comes from torch.autograd.grad; forward, backward, merge backward, Adam, the
+        non-finite guard and the loss scale stay on the engine.  No host sync.  If fn raises, the step is abandoned (counted as
+        skipped) and the exception propagates.  Returns the detached loss."""
+        pred = self.forward_step().detach().requires_grad_(True)
+        target = self.frames[self.open_frame:self.open_frame + 1]
+        try:
+            with torch.enable_grad():
+                loss = fn(pred, target)
+                if not isinstance(loss, torch.Tensor) or loss.numel() != 1:
+                    raise OrnError('step_with: fn(pred, target) must return a one-element tensor')
+                (g,) = torch.autograd.grad(loss.reshape(()), pred)
+        except BaseException:
+            self.backward_step(None)
+            raise
+        loss = loss.detach()
+        self.backward_step(g.contiguous(), loss)
+        return loss
+
+    def run_with(self, fn, n_steps: int):
+        """`n_steps` optimiser steps of step_with(fn), consuming the uploaded schedule like run() (single frame per step; no
+        batched, pipelined or graph form)."""
+        for _ in range(n_steps):
+            self.step_with(fn)
 
     def set_grad_mask(self, masks=None):
         """0/1 gradient masks per parameter name ({name: tensor like the parameter}; missing names = 1); None removes
@@ -389,6 +478,7 @@ class TrainEngine(_Decoding):
                                             c_void_p(self.stream.cuda_stream)), 'orn_engine_profile_step')
         cur.wait_stream(self.stream)
         self.global_step += 1
+        self._cursor_host += 1
         v = [float(x) for x in ms]
         return {'fwd': v[:n], 'dgrad': v[n:2 * n], 'wgrad': v[2 * n], 'wgrad_reduce': v[2 * n + 1]}
 

@@ -60,7 +60,7 @@ def build_parser():
     p.add_argument('--beta', type=float, default=0.5)
     p.add_argument('--loss_type', type=str, default='L2',
                    help='utils.py:139-189: L2, L1, SSIM, Fusion1-12 (Fusion10-12 train towards MS-SSIM and need an output side above 160); '
-                        'the FFT losses Fusion13 / Fusion15 are not built')
+                        'the FFT losses Fusion13 / Fusion15 are not built (see --custom_loss)')
     p.add_argument('--lw', type=float, default=1.0)
     p.add_argument('--sigmoid', action='store_true')
     p.add_argument('--deploy', action='store_true', default=False)
@@ -94,6 +94,10 @@ def build_parser():
                    help='how an evaluation decodes.  eager: frame by frame (main_eval: the fp32 module forward; main_train: one engine '
                         'decode per frame and metric); engine: the native engine at --precision, all frames in one call, PSNR (float '
                         'and 8-bit), MS-SSIM and the --dump_images pixels computed on the device')
+    p.add_argument('--custom_loss', default=None, metavar='MODULE:FUNCTION',
+                   help='train on FUNCTION(pred, target) -> scalar tensor of the importable MODULE instead of --loss_type: torch ops on '
+                        'the engine\'s output, differentiated by autograd, with the rest of the step on the engine (-b 1 only).  '
+                        'orn_amd.custom_losses:fusion_freq_ssim / :fusion_freq_msssim are the reference\'s two FFT objectives')
     p.add_argument('--ckpt_freq', type=int, default=0, help='checkpoint every K epochs (0: eval epochs and the last)')
     p.add_argument('--dist_backend', default=None, choices=['nccl', 'gloo'],
                    help='torch.distributed backend under a multi-process launcher (default: nccl = RCCL on GPUs)')
@@ -255,9 +259,47 @@ def evaluate(model, eng, args, val=None, gap=None):
     return float(torch.stack(psnrs).mean()), len(psnrs) / dt, float(torch.stack(ms).mean())
 
 
+def parse_loss_spec(spec: str):
+    """'MODULE:FUNCTION' of --custom_loss -> (module name, function name); ValueError for anything else."""
+    mod, sep, fn = (spec or '').partition(':')
+    if not sep or not mod or not fn or ':' in fn or not all(part.isidentifier() for part in mod.split('.') + fn.split('.')):
+        raise ValueError(f'--custom_loss {spec!r}: expected MODULE:FUNCTION, e.g. orn_amd.custom_losses:fusion_freq_ssim')
+    return mod, fn
+
+
+def load_custom_loss(spec: str):
+    """The callable a --custom_loss spec names; ValueError if the spec is malformed, the module cannot be imported or has no
+    such callable.  Touches no GPU."""
+    import importlib
+    mod, fn = parse_loss_spec(spec)
+    try:
+        obj = importlib.import_module(mod)
+    except ImportError as e:
+        raise ValueError(f'--custom_loss {spec!r}: cannot import {mod}: {e}') from e
+    for part in fn.split('.'):
+        if not hasattr(obj, part):
+            raise ValueError(f'--custom_loss {spec!r}: {mod} has no attribute {fn}')
+        obj = getattr(obj, part)
+    if not callable(obj):
+        raise ValueError(f'--custom_loss {spec!r}: {mod}.{fn} is not callable')
+    return obj
+
+
+def custom_loss_of(args):
+    """The --custom_loss callable of a run (None without the flag), checked against -b before any GPU work."""
+    spec = getattr(args, 'custom_loss', None)
+    if not spec:
+        return None
+    fn = load_custom_loss(spec)
+    if args.batchSize != 1:
+        raise ValueError(f'--custom_loss trains one frame per optimiser step: -b/--batchSize {args.batchSize} is not supported with it (use -b 1)')
+    return fn
+
+
 def train(args):
     """One independent fit per video; the videos of the job are dealt round-robin to the ranks (dist_utils.shard_videos), each
     into its own output directory, so ranks never write the same file.  Returns {video name: best train PSNR} of this rank."""
+    custom_loss_of(args)                                            # a bad --custom_loss fails here, before any GPU work
     rank, local, world = du.env_world()
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
     dist = du.init(getattr(args, 'dist_backend', None))
@@ -312,6 +354,7 @@ def epoch_entries(order, epoch, n, B, args, skipped_carry=0):
 
 def fit_video(args, name, vid_index, rank, _inject=None):
     """One fit.  _inject(epoch, eng): test hook, called after the epoch's start-of-epoch snapshot."""
+    custom = custom_loss_of(args)
     torch.manual_seed(args.manualSeed)                              # main_train.py:162
     PE = utils.PositionalEncoding(args.embed)
     args.embed_length = PE.embed_length
@@ -359,7 +402,10 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         # (eng.skipped_carry) are taken off here, so the bias corrections count applied steps only, whatever the history
         entries = epoch_entries(order, epoch, n, B, args, eng.skipped_carry)
         eng.set_schedule(entries)
-        eng.run(steps_per_epoch, batch=B)                            # B = 1: the pipelined single-frame step, as ever
+        if custom is not None:
+            eng.run_with(custom, steps_per_epoch)                    # the split step: the engine around a torch objective
+        else:
+            eng.run(steps_per_epoch, batch=B)                        # B = 1: the pipelined single-frame step, as ever
         st = eng.stats(steps_per_epoch)                              # syncs once per epoch
         sc = eng.scale_state()                                       # (the stats read above has already synchronised)
         warn = skipped_steps_warning(skipped_before, steps_skipped(sc), steps_per_epoch, precision, sc['scale'])

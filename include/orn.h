@@ -37,7 +37,7 @@ extern "C" {
 #define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames;
                                   * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
                                   * orn_loss_ws_bytes_for; + ORN_MAX_BATCH, orn_engine_batch_ws_bytes, orn_engine_set_batch_ws,
-                                  * orn_engine_train_steps_batch */
+                                  * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -153,7 +153,8 @@ ORN_API int orn_head_bwd(const float *a, const float *w, const float *out, const
  * dpred = dLoss/dpred * loss_scale (NULL: forward only).
  * Every id resolves through one table (orn_loss_spec) to loss = w_l1 * L1 + w_l2 * MSE + w_struct * (1 - s) with s = ssim
  * (kind ORN_LOSS_KIND_SSIM) or ms_ssim (ORN_LOSS_KIND_MSSSIM); the weights are those of utils.py:142-172.  Fusion13 / Fusion15
- * (FFT terms) are not built and have no id.
+ * (FFT terms) are not built and have no id: such an objective -- any objective -- trains through the split step below
+ * (orn_engine_step_forward / orn_engine_step_backward), which takes dLoss/dpred from the caller.
  *   kind SSIM: one launch, the 16x64-tile kernel of Fusion6 (80 KB of LDS) with other gradient weights; an L2 term takes the
  *     place of the L1 term at compile time.  Fusion7 / Fusion8 (kind NONE) are the plain L1 / L2 kernel with both terms.
  *   kind MSSSIM (min(H, W) > 160 and B*Ch <= 64, else ORN_E_ARG): 5 + 1 + 5 launches.  The five level launches of orn_msssim on the
@@ -299,6 +300,29 @@ ORN_API int orn_engine_eval_frames(orn_engine *e, const float *embeds, const int
 ORN_API int orn_engine_train_step(orn_engine *e, const float *frames, const float *embeds,
                           const orn_step_sched *sched, int32_t *cursor, float *stats_out, int32_t n_slots,
                           void *stream);
+/* ---- N6  a caller-supplied loss: the step split at the loss              utils.py:139-189 (loss_fn is ordinary Python) ----
+ * orn_engine_train_step in two calls, with the loss left to the caller: any function of the engine's output whose value and
+ * gradient the caller can compute on the device (torch ops on the same stream, no host synchronisation needed).
+ * orn_engine_step_forward: the schedule advance for one step and the training forward, exactly as orn_engine_train_step runs them.
+ *   *pred receives the engine's own fp32 planar image [3,H,W] (device; inside the engine's workspace; no copy).  The step is now
+ *   OPEN: until orn_engine_step_backward has run, every other stepping, decoding and evaluation entry of this engine -- and a second
+ *   orn_engine_step_forward -- returns ORN_E_STATE, since it would overwrite the activations the backward needs.
+ * orn_engine_step_backward: needs an open step (ORN_E_STATE otherwise) and the stream of its forward half.
+ *   dpred  device fp32 [3,H,W], planar and contiguous: dLoss/dpred of the UNSCALED loss (the engine applies its own loss scale in
+ *          the head's backward, as in every other step).  It is read in place by the head's backward (no copy): alive and unchanged
+ *          until the stream has passed the call.  NULL abandons the step: its flag is raised and the Adam launch runs, so the
+ *          step is skipped and counted like any other skipped step (parameters and moments untouched, `skipped` + 1).
+ *   loss   optional device float: becomes stats[0] of the step's record (NULL: 0).  A non-finite value skips the step.
+ *   The record: {loss, L1, MSE, 0, PSNR, lr, frame, step}; L1, MSE and PSNR of pred against the step's frame, as for every built-in
+ *   loss (per 16x64 tile in fp32, tiles in double, fixed order, no atomics).  A NaN or infinity anywhere in dpred skips the step.
+ *   From the head's backward on it runs the launches of orn_engine_train_step (serial form: no side stream, no graph), so a
+ *   caller that hands in what orn_loss_fwd_bwd computes gets the bits of a built-in step.
+ * Neither call synchronises.  frames / embeds / sched / cursor / stats_out / n_slots as for orn_engine_train_step, the same in
+ * both halves.  There is no batched, pipelined or graph form of the split step. */
+ORN_API int orn_engine_step_forward(orn_engine *e, const float *frames, const float *embeds, const orn_step_sched *sched,
+                            int32_t *cursor, int32_t n_slots, const float **pred, void *stream);
+ORN_API int orn_engine_step_backward(orn_engine *e, const float *frames, const float *embeds, const float *dpred,
+                             const float *loss, float *stats_out, int32_t n_slots, void *stream);
 /* Optional 0/1 gradient mask in the arena layout (device, float, 16-byte aligned; null removes it): gradients are
  * multiplied by it before Adam.  The prune fine-tune of main_eval.py:213-531 -- torch.nn.utils.prune keeps
  * weight = weight_orig * mask, so pruned entries never receive a gradient -- and its frozen tensors. */
