@@ -91,6 +91,8 @@ _SIGS = {
     'orn_msssim': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     'orn_msssim_frames_ws_bytes': (c_size_t, [c_int] * 4),
     'orn_msssim_frames': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'orn_frames_ingest_u8': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
+    'orn_frames_pool_f32': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
     'orn_adam_step': (c_int, [P, P, P, P, c_size_t, c_double, c_double, c_double, c_double, c_int, P]),
     'orn_engine_ws_bytes': (c_size_t, [POINTER(EngineDesc)]),
     'orn_engine_create': (c_int, [POINTER(EngineDesc), P, P, P, P, P, c_size_t, POINTER(c_void_p)]),

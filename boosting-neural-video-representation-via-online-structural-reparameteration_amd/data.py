@@ -93,18 +93,51 @@ class FrameDir:
             t = t.permute(0, 2, 1)
         return t, self.frame_idx[valid]
 
-    def load(self, device='cuda'):
+    def item_hwc(self, idx: int):
+        """(uint8 HWC numpy array as PIL decodes it, transposed on the host when taller than wide; normalised time) of sample idx."""
+        import os
+        import numpy as np
+        from PIL import Image
+        valid = idx * self.frame_gap
+        img = np.asarray(Image.open(os.path.join(self.main_dir, self.frame_path[valid])).convert('RGB'), dtype=np.uint8)
+        if img.shape[0] > img.shape[1]:
+            img = img.transpose(1, 0, 2)
+        return np.ascontiguousarray(img), self.frame_idx[valid]
+
+    def load(self, device='cuda', out_hw=None, chunk: int = 16):
         """All samples at once: frames [n,3,H,W] fp32 in [0,1] resident on `device`, times [n] fp32 (torch.tensor of the
-        Python doubles, as model.py:68 makes them)."""
+        Python doubles, as model.py:68 makes them).
+        out_hw=(h, w): the frames as the reference's step sees them, F.adaptive_avg_pool2d(data, (h, w)) (main_train.py:239) -- on a
+        GPU from the uint8 pixels, uploaded `chunk` frames at a time and pooled there (ops.ingest_frames: the host never holds an
+        fp32 copy); on the CPU with torch's own op (host data loading, not the hot path)."""
         if len(self) == 0:
             raise FileNotFoundError(f'no frames in {self.main_dir}')
+        if out_hw is not None and torch.device(device).type == 'cuda':
+            import numpy as np
+            from . import ops
+            n, chunk = len(self), max(1, int(chunk))
+            frames, times, shape = None, [], None
+            for k0 in range(0, n, chunk):
+                items = [self.item_hwc(k) for k in range(k0, min(k0 + chunk, n))]
+                times += [t for _, t in items]
+                shape = shape or items[0][0].shape
+                if any(a.shape != shape for a, _ in items):
+                    raise ValueError(f'frames of different sizes in {self.main_dir}')
+                u8 = torch.from_numpy(np.stack([a for a, _ in items])).to(device)
+                if frames is None:
+                    frames = torch.empty(n, 3, int(out_hw[0]), int(out_hw[1]), device=u8.device)
+                ops.ingest_frames(u8, out_hw, out=frames[k0:k0 + len(items)])
+            return frames, torch.tensor(times, dtype=torch.float32)
         items = [self.item(k) for k in range(len(self))]
         # ToTensor's arithmetic on the host (uint8 -> fp32, / 255 correctly rounded), then one upload: a device-side division
         # may be compiled to a reciprocal multiply and differ in the last bit
-        frames = torch.stack([f.float().div(255.0) for f, _ in items]).contiguous().to(device)
-        return frames, torch.tensor([t for _, t in items], dtype=torch.float32)
+        frames = torch.stack([f.float().div(255.0) for f, _ in items]).contiguous()
+        if out_hw is not None:
+            frames = torch.nn.functional.adaptive_avg_pool2d(frames, (int(out_hw[0]), int(out_hw[1]))).contiguous()
+        return frames.to(device), torch.tensor([t for _, t in items], dtype=torch.float32)
 
 
-def load_png_dir(main_dir: str, vid_list=(None,), frame_gap: int = 1, device='cuda'):
-    """(frames [n,3,H,W] fp32 on `device`, times [n] fp32) of a frame directory with CustomDataSet's indexing (FrameDir)."""
-    return FrameDir(main_dir, vid_list, frame_gap).load(device)
+def load_png_dir(main_dir: str, vid_list=(None,), frame_gap: int = 1, device='cuda', out_hw=None):
+    """(frames [n,3,H,W] fp32 on `device`, times [n] fp32) of a frame directory with CustomDataSet's indexing (FrameDir);
+    out_hw=(h, w): pooled to that size as the reference's step pools its target (FrameDir.load)."""
+    return FrameDir(main_dir, vid_list, frame_gap).load(device, out_hw)

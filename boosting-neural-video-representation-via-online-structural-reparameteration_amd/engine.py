@@ -118,15 +118,13 @@ class _Decoding:
             is less than 160 high (utils.msssim_fn's rule).  chunk: frames per group of MS-SSIM launches, which sizes the workspace
             (default min(n, 8); the values do not depend on it)."""
         embeds = self.embeds if embeds is None else embeds.to(self.device, torch.float32).contiguous()
-        frames = self.frames if frames is None else frames.to(self.device, torch.float32).contiguous()
+        frames = self.frames if frames is None else self._target_frames(frames, 'decode_frames: ')
         if embeds is None:
             raise OrnError('decode_frames: no embeds given and no video resident (set_video)')
         if embeds.dim() != 2 or embeds.shape[1] != self.desc.embed_len:
             raise OrnError(f'decode_frames: embeds {tuple(embeds.shape)} vs (*, {self.desc.embed_len})')
         if (stats or msssim) and frames is None:
             raise OrnError('decode_frames: stats and msssim need target frames (frames=, or set_video)')
-        if frames is not None and tuple(frames.shape[1:]) != (3,) + tuple(self.out_hw):
-            raise OrnError(f'decode_frames: frames {tuple(frames.shape)} do not match the decoder output {self.out_hw}')
         if rows is None:
             rows = torch.arange(embeds.shape[0], dtype=torch.int32)
         rows = torch.as_tensor(rows).to(torch.int32).reshape(-1)
@@ -161,6 +159,23 @@ class _Decoding:
                                                  _lib.stream()), 'orn_engine_decode_frames')
         self._decode_keep = (embeds, frames, rows)          # alive until the stream has drained
         return out
+
+    def _target_frames(self, frames: torch.Tensor, what: str = '') -> torch.Tensor:
+        """Target frames as the engine reads them: fp32 [N,3,h,w] on the device at the decoder's output size.  fp32 [N,3,H,W] or
+        uint8 [N,H,W,3] (as PIL decodes it) of another size are pooled there as the reference pools every target,
+        F.adaptive_avg_pool2d(data, output.shape[-2:]) (main_train.py:239,420; main_eval.py:467,807), by ops.ingest_frames."""
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise OrnError(f'{what}frames must be a [N,3,H,W] tensor (or uint8 [N,H,W,3]), got {tuple(getattr(frames, "shape", ()))}')
+        if frames.dtype == torch.uint8:
+            if frames.shape[3] != 3:
+                raise OrnError(f'{what}uint8 frames {tuple(frames.shape)} are not [N,H,W,3]')
+            return ops.ingest_frames(frames.to(self.device), self.out_hw)
+        if frames.shape[1] != 3:
+            raise OrnError(f'{what}frames {tuple(frames.shape)} are not [N,3,H,W]')
+        frames = frames.to(self.device, torch.float32).contiguous()
+        if tuple(frames.shape[2:]) != tuple(self.out_hw):
+            frames = ops.ingest_frames(frames, self.out_hw)
+        return frames
 
     def _eval_ws(self, chunk: int) -> torch.Tensor:
         """The workspace of orn_engine_eval_frames for `chunk` frames, cached on the object (kept alive; it only grows)."""
@@ -268,12 +283,13 @@ class TrainEngine(_Decoding):
 
     # ---- data ---------------------------------------------------------------------------------
     def set_video(self, frames: torch.Tensor, embeds: torch.Tensor):
-        """frames [N,3,H,W] fp32 in [0,1] (resident in HBM), embeds [N,E] (PE of k/N)."""
-        if tuple(frames.shape[1:]) != (3,) + self.out_hw:
-            raise OrnError(f'frames {tuple(frames.shape)} do not match the decoder output {self.out_hw}')
+        """frames [N,3,H,W] fp32 in [0,1] (resident in HBM), embeds [N,E] (PE of k/N).  Frames of another size than the decoder's
+        output, or uint8 [N,H,W,3], are pooled to it once, on the device (_target_frames): the target-statistics cache, the
+        schedule, every step form and the evaluation see the pooled table only."""
+        frames = self._target_frames(frames)
         if embeds.shape != (frames.shape[0], self.desc.embed_len):
             raise OrnError(f'embeds {tuple(embeds.shape)} vs ({frames.shape[0]}, {self.desc.embed_len})')
-        self.frames = frames.to(self.device, torch.float32).contiguous()
+        self.frames = frames
         self.embeds = embeds.to(self.device, torch.float32).contiguous()
         # SSIM kinds (SSIM, Fusion1-6, Fusion9: the maps are the same): the target side of the SSIM statistics, once per video (two valid-map planes per image plane: 2.9 GB for
         # 132 frames of 720p, 29 GB for 600 of 1080p, of 288 GB); the step then filters three maps instead of five.

@@ -142,7 +142,15 @@ def load_frames(args, hw, device, name, vid_index, gap):
             keep = [k * gap for k in range(n // gap)]
             frames, pos = frames[keep].contiguous(), pos[keep]
         return frames, pos
-    return odata.load_png_dir(f'../data/{name.lower()}', args.vid, gap, device)
+    # a frame directory of any size: the target of every step and evaluation is F.adaptive_avg_pool2d(data, output.shape[-2:])
+    # (main_train.py:239,420; main_eval.py:467,807) -- frames are constant during a fit, so they are pooled once, on the device
+    fd = odata.FrameDir(f'../data/{name.lower()}', args.vid, gap)
+    if len(fd):
+        src_hw = tuple(fd.item_hwc(0)[0].shape[:2])
+        if src_hw != tuple(hw):
+            print(f'{name}: frames {src_hw[0]}x{src_hw[1]} are pooled to the decoder output {hw[0]}x{hw[1]} '
+                  f'(adaptive_avg_pool2d, main_train.py:239)', flush=True)
+    return fd.load(device, out_hw=tuple(hw))
 
 
 class Best:

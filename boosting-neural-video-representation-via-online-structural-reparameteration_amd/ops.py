@@ -264,3 +264,31 @@ def ms_ssim_frames(pred, target, rows=None, chunk=None) -> torch.Tensor:
     check(lib().orn_msssim_frames(ptr(pred), ptr(target), ptr(rows), n, Ch, H, W, ptr(out), ptr(ws), c_size_t(ws.numel()), stream()),
           'orn_msssim_frames')
     return out
+
+
+# ---- K11 -----------------------------------------------------------------------------------
+def ingest_frames(src, out_hw, chunk=None, out=None) -> torch.Tensor:
+    """ToTensor + F.adaptive_avg_pool2d(data, out_hw) as main_train.py:200,239 form a target, on the device, bit-identical to ATen's
+    CPU result.  src: uint8 [n,H,W,3] as PIL decodes it (orn_frames_ingest_u8) or fp32 [n,3,H,W] (orn_frames_pool_f32), on the GPU.
+    Returns fp32 [n,3,h,w]; out_hw == (H, W) gives exactly ToTensor / an exact copy.  chunk: frames per launch (default: all; the
+    values do not depend on it).  out: an fp32 [n,3,h,w] tensor (or slice of one along n) to fill in place of a new one -- a caller
+    that uploads a long video piece by piece ingests each piece into its slice, so the source is never resident as a whole."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise _lib.OrnError('ingest_frames: liborn ops need tensors on the GPU (there is no CPU path)')
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3:
+        (n, H, W), fn, what = src.shape[:3], lib().orn_frames_ingest_u8, 'orn_frames_ingest_u8'
+    elif src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] == 3:
+        n, (H, W), fn, what = src.shape[0], src.shape[2:], lib().orn_frames_pool_f32, 'orn_frames_pool_f32'
+    else:
+        raise _lib.OrnError(f'ingest_frames: {src.dtype} {tuple(src.shape)} is neither uint8 [n,H,W,3] nor float32 [n,3,H,W]')
+    src = src.contiguous()
+    if out is None:
+        out = torch.empty(n, 3, h, w, device=src.device)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (n, 3, h, w) or out.device != src.device or not out.is_contiguous()):
+        raise _lib.OrnError(f'ingest_frames: out {out.dtype} {tuple(out.shape)} vs contiguous float32 {(n, 3, h, w)} on {src.device}')
+    step = n if chunk is None else max(1, int(chunk))
+    for k in range(0, n, max(step, 1)):
+        m = min(step, n - k)
+        check(fn(ptr(src[k:k + m]), m, H, W, ptr(out[k:k + m]), h, w, stream()), what)
+    return out

@@ -37,7 +37,8 @@ extern "C" {
 #define ORN_VERSION 120          /* 0.1.2: + orn_loss_target_stats*, orn_engine_set_target_stats (round 3); + orn_engine_decode_frames;
                                   * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
                                   * orn_loss_ws_bytes_for; + ORN_MAX_BATCH, orn_engine_batch_ws_bytes, orn_engine_set_batch_ws,
-                                  * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step) */
+                                  * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step);
+                                  * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -219,7 +220,21 @@ ORN_API size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W);       /*
 ORN_API int orn_msssim_frames(const float *pred, const float *targets, const int32_t *rows, int n, int Ch, int H, int W,
                               float *out /* [n] */, void *ws, size_t ws_bytes, void *stream);
 
-/* ---- A9  optim.Adam.step over one flat arena                          main_train.py:196,250 ---
+/* ---- K11  ToTensor + F.adaptive_avg_pool2d(data, (h, w))      main_train.py:200,239,420; main_eval.py:467,807 ----
+ * The reference pools every target to the decoder's output size inside the step; a video's frames never change during its fit, so
+ * this runs once per video.  ATen's CPU arithmetic, bit for bit: output (i, j) is the fp32 sum, row-major from 0, over rows
+ * [floor(i*H/h), ceil((i+1)*H/h)) and the same in W / w, divided by the window height and then by the window width (two correctly
+ * rounded divisions); h > H or w > W (upsampling) follows the same formula.  A byte's value is (float)b / 255.0f correctly rounded
+ * (ToTensor), from a table.  h == H && w == W gives exactly ToTensor (uint8 entry) and an exact copy (fp32 entry).
+ * One launch per 65535 frames, no workspace, no atomics, capturable; src and dst must not overlap unless they are equal at
+ * identity size (fp32 entry).  Every side at most 32768; ORN_E_ARG when a single output pixel's source row does not fit the
+ * kernel's staging buffer (more than about 2700 source columns per output column).  n == 0 is a no-op. */
+ORN_API int orn_frames_ingest_u8(const uint8_t *src /* device [n][H][W][3], interleaved as PIL decodes it */,
+                                 int n, int H, int W, float *dst /* device [n][3][h][w] planar */, int h, int w, void *stream);
+ORN_API int orn_frames_pool_f32(const float *src /* device [n][3][H][W] */, int n, int H, int W,
+                                float *dst /* device [n][3][h][w] */, int h, int w, void *stream);
+
+/* ---- A9  optim.Adam.step over one flat arena                         main_train.py:196,250 ---
  * p,g,m,v: n floats each.  step = 1-based global step.  weight decay 0, amsgrad off.
  * Hyper-parameters are doubles (as Python holds them): 1-beta, lr/(1-beta1^t) and sqrt(1-beta2^t)
  * are formed in double and rounded to fp32 once, exactly as torch.optim.Adam does. */
