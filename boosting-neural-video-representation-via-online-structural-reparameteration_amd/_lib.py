@@ -59,6 +59,7 @@ _SIGS = {
     'orn_last_error': (c_int, [c_char_p, c_size_t]),
     'orn_pe_fwd': (c_int, [P, c_int, P, c_int, P, P]),
     'orn_stem_fwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    'orn_stem_bwd_ws_bytes': (c_size_t, [c_int] * 3),
     'orn_stem_bwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     'orn_erb_merge_fwd': (c_int, [P] * 9 + [c_int, c_int, P, P, P, P]),
     'orn_erb_merge_bwd_ws_bytes': (c_size_t, [c_int, c_int]),
@@ -125,7 +126,12 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_conv_dgrad_f16': (c_int, [P, P] + [c_int] * 4 + [P, P, c_int, P, c_int, P]),
                'orn_debug_merge_h16_bwd': (c_int, [c_int, P, P, P, P, P]),
                'orn_debug_decode_out_ws_bytes': (c_size_t, []),
-               'orn_debug_decode_out_f32': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P])}
+               'orn_debug_decode_out_f32': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+               'orn_debug_stage0_supported': (c_int, [c_int] * 5),
+               'orn_debug_stage0_slabs': (c_int, [c_int] * 2),
+               'orn_debug_stage0_fwd': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, c_int, P]),
+               'orn_debug_stage0_bwd': (c_int, [P, P, P, P, c_int, c_int, c_float] + [c_int] * 5 + [P, P, P, P, P]),
+               'orn_debug_stem_bwd_slabs': (c_int, [P] * 6 + [c_int] * 4 + [P] * 5 + [c_size_t, P])}
 
 _lib = None
 

@@ -224,7 +224,7 @@ int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_strid
                         float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab, OrnStemW0Job *defer_w0,
                         OrnStemL2Job *defer_l2)
 {
-    // ws: dpre2 [B*Nout] | dpre1 [B*Hd] | dh1 [B*Hd] | partial [CHUNKS*B*Hd]
+    // ws (orn_stem_bwd_ws_floats): dpre2 [B*Nout] | dpre1 [B*Hd] | dh1 [B*Hd] | partial [CHUNKS*B*Hd], at B == 1 [cdiv(Nout,16)][Hd]
     float *dpre2 = ws;
     float *dpre1 = dpre2 + (size_t)B * Nout;
     float *dh1 = dpre1 + (size_t)B * Hd;
@@ -275,6 +275,29 @@ extern "C" int orn_stem_bwd(const float *embed, const float *w1, const float *pr
     ORN_REQUIRE(B > 0 && E > 0 && Hd > 0 && Nout > 0, "stem_bwd: bad sizes");
     return orn_launch_stem_bwd(embed, nullptr, 0, w1, pre1, h1, pre2, dh2, B, E, Hd, Nout, dw0, db0, dw1, db1, ws,
                                (hipStream_t)stream, 1, nullptr, nullptr);
+}
+
+extern "C" size_t orn_stem_bwd_ws_bytes(int B, int Hd, int Nout)
+{
+    if (B <= 0 || Hd <= 0 || Nout <= 0) return 0;
+    return orn_stem_bwd_ws_floats(B, Hd, Nout) * sizeof(float);
+}
+
+// test entry point (include/orn_debug.h): the B == 1 form with the upstream gradient as partial rows, launched as the engine's
+// non-deferred path launches it
+extern "C" int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                                        const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0,
+                                        float *dw1, float *db1, float *ws, size_t ws_bytes, void *stream)
+{
+    ORN_REQUIRE(embed && w1 && pre1 && h1 && pre2 && dh2_slabs && dw0 && db0 && dw1 && db1 && ws, "debug_stem_bwd_slabs: null pointer");
+    ORN_REQUIRE(nslab >= 1 && E > 0 && Hd > 0 && Nout > 0, "debug_stem_bwd_slabs: bad sizes");
+    if (ws_bytes < orn_stem_bwd_ws_bytes(1, Hd, Nout) || (uintptr_t)ws % 4 != 0) {
+        orn_set_error("debug_stem_bwd_slabs: workspace of %zu bytes, needs orn_stem_bwd_ws_bytes = %zu, 4-byte aligned", ws_bytes,
+                      orn_stem_bwd_ws_bytes(1, Hd, Nout));
+        return ORN_E_WS;
+    }
+    return orn_launch_stem_bwd(embed, nullptr, 0, w1, pre1, h1, pre2, dh2_slabs, 1, E, Hd, Nout, dw0, db0, dw1, db1, ws,
+                               (hipStream_t)stream, nslab, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

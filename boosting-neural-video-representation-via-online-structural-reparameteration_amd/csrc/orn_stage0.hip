@@ -412,3 +412,24 @@ int orn_launch_stage0_bwd(const float *x, const float *wf, const float *z, const
     const size_t n = (size_t)C * H * W;
     return orn_launch_reduce_rows(slabs, nwg, n, n, dx, st);
 }
+
+// ---- test entry points (include/orn_debug.h): the two launchers as the engine calls them, without riders, pack or scale state ----
+extern "C" int orn_debug_stage0_supported(int C, int O, int H, int W, int s) { return orn_stage0_supported(C, O, H, W, s) ? 1 : 0; }
+
+extern "C" int orn_debug_stage0_slabs(int O, int s) { return (O >= 1 && s >= 1 && O % (s * s) == 0) ? orn_stage0_slabs(O, s) : 0; }
+
+extern "C" int orn_debug_stage0_fwd(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
+                                    void *xpad_next, int Cp, int precision, void *stream)
+{
+    ORN_REQUIRE(x && wf && bf, "debug_stage0_fwd: null pointer");
+    return orn_launch_stage0_fwd(x, wf, bf, C, O, H, W, s, z, xpad_next, Cp, precision, (hipStream_t)stream, 0, nullptr, nullptr, 0);
+}
+
+extern "C" int orn_debug_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
+                                    int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream)
+{
+    ORN_REQUIRE(x && wf, "debug_stage0_bwd: null pointer");
+    ORN_REQUIRE(orn_stage0_supported(C, O, H, W, s), "stage0: unsupported C=%d O=%d H=%d W=%d s=%d", C, O, H, W, s);
+    ORN_REQUIRE(O / (s * s) <= Cp && (uintptr_t)slabs % 16 == 0, "debug_stage0_bwd: Cp below O / s^2, or slabs not 16-byte aligned");
+    return orn_launch_stage0_bwd(x, wf, z, dxn, nslab, Cp, inv_gs, C, O, H, W, s, slabs, dx, dwf, dbf, (hipStream_t)stream, nullptr);
+}

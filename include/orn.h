@@ -38,7 +38,7 @@ extern "C" {
                                   * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
                                   * orn_loss_ws_bytes_for; + ORN_MAX_BATCH, orn_engine_batch_ws_bytes, orn_engine_set_batch_ws,
                                   * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step);
-                                  * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size) */
+                                  * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size); + orn_stem_bwd_ws_bytes */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -63,7 +63,10 @@ ORN_API int orn_pe_fwd(const float *pos, int B, const float *lbase_pow, int leve
 ORN_API int orn_stem_fwd(const float *embed, const float *w0, const float *b0, const float *w1, const float *b1,
                  int B, int E, int Hd, int Nout, float *pre1, float *h1, float *pre2, float *h2,
                  void *stream);
-/* dh2 [B,Nout] -> dw0,db0,dw1,db1 (overwritten).  ws: B*(Nout + 258*Hd) floats. */
+/* dh2 [B,Nout] -> dw0,db0,dw1,db1 (overwritten).  ws: orn_stem_bwd_ws_bytes(B, Hd, Nout) bytes, 4-byte aligned:
+ * B*(Nout + 2*Hd) floats and max(256, ceil(Nout/16)) rows of B*Hd partial sums (at B == 1 the second layer's kernel leaves one
+ * row per 16 outputs: more than 256 rows from Nout = 4097 on). */
+ORN_API size_t orn_stem_bwd_ws_bytes(int B, int Hd, int Nout);
 ORN_API int orn_stem_bwd(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
                  const float *dh2, int B, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
                  float *db1, float *ws, void *stream);

@@ -1,7 +1,8 @@
 /* orn_debug.h -- test and probe entry points of liborn.so.  NOT part of the drop-in boundary: nothing here has a reference
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
  * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
- * the merge backward's (tests/test_gpu_merge16.py). */
+ * the merge backward's (tests/test_gpu_merge16.py) and the fused first block's and the slab-summing stem backward's
+ * (tests/test_gpu_stage0.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -43,6 +44,35 @@ ORN_API int orn_debug_merge_h16_bwd(int n, const int *co, const float *const *in
 ORN_API size_t orn_debug_decode_out_ws_bytes(void);
 ORN_API int orn_debug_decode_out_f32(const float *img, int H, int W, const float *target, uint8_t *rgb8, float *img_out,
                                      float *stats, void *ws, size_t ws_bytes, void *stream);
+/* The fused fp32 first block of a 16-bit engine (orn_stage0.hip) through the launchers the engine calls, with no rider and no
+ * pack work-groups; tests/test_gpu_stage0.py pins both kernels elementwise through them.  x [C][H][W], wf [O][C][3][3], bf [O]
+ * (fp32, device); Cn = O / s^2 post-shuffle channels.
+ *   supported: 1 when the fused block takes the shape (1 <= C <= 64, O % s^2 == 0, W >= 4, H*W a multiple of 16 and <= 256, LDS);
+ *          every other entry returns ORN_E_ARG ("stage0: unsupported ...") for a shape it declines, and launches nothing.
+ *   slabs: work-groups of the backward = dx partial slabs, s^2 * ceil(Cn / 16) (0 for arguments without a meaning).
+ *   fwd:   z [s^2][H*W][Cn] fp32, element ((i*s + j)*H*W + h*W + w)*Cn + n = pre-activation of conv channel n*s^2 + i*s + j at
+ *          (h, w); every element is written; NULL: not kept (the decode form, same xpad_next bits).  xpad_next: 16-bit
+ *          [H*s + 2][W*s + 2][Cp] channels-last (precision 1: bf16, 2: IEEE half), Cp >= Cn; written: channels [0, Cn) of the
+ *          interior, SiLU of the shuffled pre-activation rounded to nearest even.  NOT written: the one-pixel ring and channels
+ *          [Cn, Cp) (the engine zeroes them once).
+ *   bwd:   z as the forward left it; dxn [nslab][H*s][W*s][Cp] fp32, the next block's dgrad slabs (no ring): their sum times
+ *          inv_gs is the gradient with respect to the block's output; channels [Cn, Cp) are never read.  slabs: scratch and
+ *          output, orn_debug_stage0_slabs(O, s) x [C][H*W] floats, 16-byte aligned, every element overwritten; their sum is dx.
+ *          dx [C][H][W]: that sum (a fixed-order reduction launch); NULL: the slabs are left to the caller, as the engine leaves
+ *          them to the stem backward.  dwf [O][C][3][3], dbf [O]: overwritten, every element. */
+ORN_API int orn_debug_stage0_supported(int C, int O, int H, int W, int s);
+ORN_API int orn_debug_stage0_slabs(int O, int s);
+ORN_API int orn_debug_stage0_fwd(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
+                                 void *xpad_next, int Cp, int precision, void *stream);
+ORN_API int orn_debug_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
+                                 int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream);
+/* The B == 1 stem backward as the 16-bit engine runs it behind the fused first block (two launches, no deferred jobs): dh2_slabs
+ * [nslab][Nout] are partial rows of dL/dh2 that the first kernel sums itself (64 lanes stride over the slabs, fixed order);
+ * other arguments and outputs as orn_stem_bwd at B = 1.  ws: orn_stem_bwd_ws_bytes(1, Hd, Nout) bytes (ORN_E_WS below that);
+ * written: dpre1 [Hd] at float offset Nout and ceil(Nout / 16) rows of Hd partials at Nout + 2*Hd, nothing else. */
+ORN_API int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                                     const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
+                                     float *db1, float *ws, size_t ws_bytes, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
