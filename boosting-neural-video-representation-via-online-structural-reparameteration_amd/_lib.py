@@ -131,7 +131,13 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_stage0_slabs': (c_int, [c_int] * 2),
                'orn_debug_stage0_fwd': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, c_int, P]),
                'orn_debug_stage0_bwd': (c_int, [P, P, P, P, c_int, c_int, c_float] + [c_int] * 5 + [P, P, P, P, P]),
-               'orn_debug_stem_bwd_slabs': (c_int, [P] * 6 + [c_int] * 4 + [P] * 5 + [c_size_t, P])}
+               'orn_debug_stem_bwd_slabs': (c_int, [P] * 6 + [c_int] * 4 + [P] * 5 + [c_size_t, P]),
+               'orn_debug_gauss_taps': (None, [P]),
+               'orn_debug_msssim_level_fwd_tiles': (c_int, [c_int] * 2),
+               'orn_debug_msssim_level_bwd_tiles': (c_int, [c_int] * 2),
+               'orn_debug_msssim_level_fwd': (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
+               'orn_debug_msssim_level_bwd': (c_int, [c_int, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_float, c_float, P, P, P]),
+               'orn_debug_loss_msssim_layout': (c_int, [c_int] * 5 + [POINTER(c_int64)])}
 
 _lib = None
 

@@ -148,11 +148,18 @@ struct OrnMsPyramid {
     float *part;                 // level l at part_off[l]: [F*Ch][nblk[l]][2] = {ssim, cs} tile sums
     size_t part_off[5];
 };
+static inline int orn_msssim_pooled(int n) { return (n + 2 * (n % 2)) / 2; }      // avg_pool2d(2, padding = n % 2)
 static inline void orn_msssim_geom(int H, int W, int Hs[5], int Ws[5])
 {
     Hs[0] = H; Ws[0] = W;
-    for (int l = 1; l < 5; ++l) { Hs[l] = (Hs[l - 1] + 2 * (Hs[l - 1] % 2)) / 2; Ws[l] = (Ws[l - 1] + 2 * (Ws[l - 1] % 2)) / 2; }
+    for (int l = 1; l < 5; ++l) { Hs[l] = orn_msssim_pooled(Hs[l - 1]); Ws[l] = orn_msssim_pooled(Ws[l - 1]); }
 }
+// The same workspace as float offsets from its start (what OrnMsPyramid holds as pointers); total: its size.
+struct OrnMsLayout {
+    int Hs[5], Ws[5], nblk[5]; float nmap[5];
+    size_t pooled[5][2], part, part_off[5], total;       // level l's partials at part + part_off[l]
+};
+void orn_msssim_layout(size_t planes, int H, int W, OrnMsLayout *out);
 size_t orn_msssim_pyramid_floats(size_t planes, int H, int W);
 int orn_launch_msssim_levels(const float *pred, const float *targets, const int32_t *rows, int F, int Ch, int H, int W, float *ws,
                              hipStream_t st, OrnMsPyramid *out);
@@ -161,6 +168,9 @@ int orn_launch_msssim_levels(const float *pred, const float *targets, const int3
 // *ms_val: where the coefficient launch leaves the MS-SSIM value for the finalize stage.
 int orn_loss_msssim_init();
 size_t orn_loss_msssim_ws_floats(size_t planes, int H, int W);
+// float offsets inside ms_ws behind the pyramid: the gradient planes of levels 1..4 (grad[0] unused), the coefficient table
+// [5][planes] (the value follows it)
+void orn_loss_msssim_layout(size_t planes, int H, int W, size_t grad[5], size_t *coef);
 int orn_launch_loss_msssim(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int planes, int H, int W,
                            float g_l1, float g_l2, float w_struct_scaled, float *dpred, float *part_l1, float *ms_ws, hipStream_t st,
                            const float **ms_val);

@@ -816,26 +816,46 @@ __global__ void __launch_bounds__(256) k_msssim_frames_finalize(const float *__r
     }
 }
 
-// floats of one chunk's workspace: pooled pred / target planes of levels 1..4, then every level's per-tile partials
-static size_t msssim_frames_floats(size_t planes, const int Hs[5], const int Ws[5], float *pooled[5][2], float **part, float *base)
+// One level's geometry in the kernel's argument: sizes, the 16x64 tiling of the VALID map, the pooled size and padding (pool: the
+// level writes the next one's planes).  orn_msssim_layout, the level launches and orn_debug_msssim_level_fwd all come through here.
+static OrnMsLevel ms_level_geom(int H, int W, bool pool)
 {
+    OrnMsLevel q = {};
+    q.H = H; q.W = W;
+    q.tiles_w = orn_cdiv(W - 10, SS_TW); q.tiles_h = orn_cdiv(H - 10, SS_TH);
+    if (pool) { q.Ho = orn_msssim_pooled(H); q.Wo = orn_msssim_pooled(W); q.ph = H % 2; q.pw = W % 2; }
+    return q;
+}
+
+// One chunk's workspace in floats: pooled pred / target planes of levels 1..4, then every level's per-tile partials
+void orn_msssim_layout(size_t planes, int H, int W, OrnMsLayout *out)
+{
+    OrnMsLayout &ly = *out;
+    orn_msssim_geom(H, W, ly.Hs, ly.Ws);
     size_t f = 0, nb = 0;
+    ly.pooled[0][0] = ly.pooled[0][1] = 0;
     for (int l = 1; l < 5; ++l)
         for (int k = 0; k < 2; ++k) {
-            if (pooled) pooled[l][k] = base + f;
-            f += orn_align(planes * Hs[l] * Ws[l] * 4) / 4;
+            ly.pooled[l][k] = f;
+            f += orn_align(planes * ly.Hs[l] * ly.Ws[l] * 4) / 4;
         }
-    for (int l = 0; l < 5; ++l) nb += (size_t)orn_cdiv(Ws[l] - 10, SS_TW) * orn_cdiv(Hs[l] - 10, SS_TH);
-    if (part) *part = base + f;
-    return f + orn_align(2 * planes * nb * 4) / 4;
+    ly.part = f;
+    for (int l = 0; l < 5; ++l) {
+        const OrnMsLevel q = ms_level_geom(ly.Hs[l], ly.Ws[l], l < 4);
+        ly.nblk[l] = q.tiles_w * q.tiles_h;
+        ly.nmap[l] = (float)(ly.Hs[l] - 10) * (float)(ly.Ws[l] - 10);
+        ly.part_off[l] = 2 * planes * nb;
+        nb += (size_t)ly.nblk[l];
+    }
+    ly.total = f + orn_align(2 * planes * nb * 4) / 4;
 }
 
 extern "C" size_t orn_msssim_frames_ws_bytes(int n, int Ch, int H, int W)
 {
     if (n <= 0 || Ch <= 0 || Ch > 64 || (H < W ? H : W) <= 160) return 0;
-    int Hs[5], Ws[5];
-    orn_msssim_geom(H, W, Hs, Ws);
-    return msssim_frames_floats((size_t)n * Ch, Hs, Ws, nullptr, nullptr, nullptr) * 4;
+    OrnMsLayout ly;
+    orn_msssim_layout((size_t)n * Ch, H, W, &ly);
+    return ly.total * 4;
 }
 
 // The most frames one chunk may hold in ws_bytes (0: not even one); F * Ch is a grid dimension.
@@ -848,9 +868,9 @@ int orn_msssim_frames_chunk(int n, int Ch, int H, int W, size_t ws_bytes)
 
 size_t orn_msssim_pyramid_floats(size_t planes, int H, int W)
 {
-    int Hs[5], Ws[5];
-    orn_msssim_geom(H, W, Hs, Ws);
-    return msssim_frames_floats(planes, Hs, Ws, nullptr, nullptr, nullptr);
+    OrnMsLayout ly;
+    orn_msssim_layout(planes, H, W, &ly);
+    return ly.total;
 }
 
 // The five level launches of one chunk (F frames whose workspace fits: the callers check); *out describes what they left in ws.
@@ -858,29 +878,23 @@ int orn_launch_msssim_levels(const float *pred, const float *targets, const int3
                              hipStream_t st, OrnMsPyramid *out)
 {
     OrnMsPyramid &py = *out;
-    orn_msssim_geom(H, W, py.Hs, py.Ws);
-    const int *Hs = py.Hs, *Ws = py.Ws;
     const size_t planes = (size_t)F * Ch;
-    for (int k = 0; k < 2; ++k) py.pooled[0][k] = nullptr;
-    py.part = nullptr;
-    msssim_frames_floats(planes, Hs, Ws, py.pooled, &py.part, ws);
-    float *part = py.part;
-    OrnMsLevel q = {};
-    q.x = pred; q.y = targets; q.rows = rows; q.Ch = Ch;
-    size_t poff = 0;
+    OrnMsLayout ly;
+    orn_msssim_layout(planes, H, W, &ly);
     for (int l = 0; l < 5; ++l) {
-        q.H = Hs[l]; q.W = Ws[l];
-        q.tiles_w = orn_cdiv(Ws[l] - 10, SS_TW); q.tiles_h = orn_cdiv(Hs[l] - 10, SS_TH);
-        py.nblk[l] = q.tiles_w * q.tiles_h;
-        py.nmap[l] = (float)(Hs[l] - 10) * (float)(Ws[l] - 10);
-        q.part = part + poff;
-        py.part_off[l] = poff;
-        poff += 2 * planes * py.nblk[l];
-        if (l < 4) { q.nx = py.pooled[l + 1][0]; q.ny = py.pooled[l + 1][1]; q.Ho = Hs[l + 1]; q.Wo = Ws[l + 1]; q.ph = Hs[l] % 2; q.pw = Ws[l] % 2; }
-        else { q.nx = q.ny = nullptr; q.Ho = q.Wo = q.ph = q.pw = 0; }
+        py.Hs[l] = ly.Hs[l]; py.Ws[l] = ly.Ws[l]; py.nblk[l] = ly.nblk[l]; py.nmap[l] = ly.nmap[l]; py.part_off[l] = ly.part_off[l];
+        for (int k = 0; k < 2; ++k) py.pooled[l][k] = l ? ws + ly.pooled[l][k] : nullptr;
+    }
+    py.part = ws + ly.part;
+    const float *x = pred, *y = targets;
+    for (int l = 0; l < 5; ++l) {
+        OrnMsLevel q = ms_level_geom(py.Hs[l], py.Ws[l], l < 4);
+        q.x = x; q.y = y; q.rows = l ? nullptr : rows; q.Ch = Ch;
+        q.part = py.part + py.part_off[l];
+        if (l < 4) { q.nx = py.pooled[l + 1][0]; q.ny = py.pooled[l + 1][1]; }
         hipLaunchKernelGGL(k_msssim_level, dim3(py.nblk[l], (unsigned)planes), dim3(256), 0, st, q);
         ORN_LAUNCH_CHECK("msssim_level");
-        q.x = q.nx; q.y = q.ny; q.rows = nullptr;
+        x = q.nx; y = q.ny;
     }
     return 0;
 }
@@ -935,4 +949,56 @@ extern "C" int orn_msssim(const float *pred, const float *target, int B, int Ch,
     if (ws_bytes < orn_msssim_ws_bytes(B, Ch, H, W)) { orn_set_error("msssim: workspace too small"); return ORN_E_WS; }
     ORN_TRY(ensure_gauss());
     return orn_launch_msssim_frames(pred, target, nullptr, 1, B * Ch, H, W, out, (float *)ws, (hipStream_t)stream);
+}
+
+// ---- test entry points (include/orn_debug.h) ----
+extern "C" void orn_debug_gauss_taps(float *g11) { orn_gauss_taps(g11); }
+
+extern "C" int orn_debug_msssim_level_fwd_tiles(int H, int W)
+{
+    if (H < 11 || W < 11) return 0;
+    const OrnMsLevel q = ms_level_geom(H, W, false);
+    return q.tiles_w * q.tiles_h;
+}
+
+extern "C" int orn_debug_msssim_level_fwd(const float *x, const float *y, int planes, int H, int W, float *part, float *nx, float *ny,
+                                          void *stream)
+{
+    ORN_REQUIRE(x && y && part, "debug_msssim_level_fwd: null pointer");
+    ORN_REQUIRE((nx != nullptr) == (ny != nullptr), "debug_msssim_level_fwd: nx and ny go together");
+    ORN_REQUIRE(planes >= 1 && planes <= 65535, "debug_msssim_level_fwd: bad plane count %d", planes);
+    ORN_REQUIRE(H >= 11 && W >= 11 && (long)H * W <= (1L << 26), "debug_msssim_level_fwd: unsupported size %dx%d", H, W);
+    ORN_TRY(ensure_gauss());
+    OrnMsLevel q = ms_level_geom(H, W, nx != nullptr);
+    q.x = x; q.y = y; q.rows = nullptr; q.Ch = planes;
+    q.part = part; q.nx = nx; q.ny = ny;
+    hipLaunchKernelGGL(k_msssim_level, dim3(q.tiles_w * q.tiles_h, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, q);
+    ORN_LAUNCH_CHECK("msssim_level");
+    return 0;
+}
+
+extern "C" int orn_debug_loss_msssim_layout(int loss_type, int B, int Ch, int H, int W, int64_t *out)
+{
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    ORN_REQUIRE(out, "debug_loss_msssim_layout: null pointer");
+    ORN_REQUIRE(sp && sp->kind == ORN_LOSS_KIND_MSSSIM, "debug_loss_msssim_layout: loss_type %d is not an MS-SSIM loss", loss_type);
+    ORN_REQUIRE(B > 0 && Ch > 0 && (long)B * Ch <= 64 && (H < W ? H : W) > 160, "debug_loss_msssim_layout: unsupported shape");
+    const LossGeom g = loss_geom(B, Ch, H, W);
+    const size_t planes = (size_t)g.planes, ms = g.total;      // orn_launch_loss: ms_ws = ws + g.total
+    OrnMsLayout ly;
+    orn_msssim_layout(planes, H, W, &ly);
+    size_t grad[5], coef;
+    orn_loss_msssim_layout(planes, H, W, grad, &coef);
+    for (int l = 0; l < 5; ++l) {
+        int64_t *o = out + 8 * l;
+        o[0] = ly.Hs[l]; o[1] = ly.Ws[l];
+        o[2] = l ? (int64_t)(ms + ly.pooled[l][0]) : -1; o[3] = l ? (int64_t)(ms + ly.pooled[l][1]) : -1;
+        o[4] = (int64_t)(ms + ly.part + ly.part_off[l]); o[5] = ly.nblk[l];
+        o[6] = l ? (int64_t)(ms + grad[l]) : -1;
+        o[7] = (int64_t)(ms + coef + (size_t)l * planes);
+    }
+    out[40] = (int64_t)(ms + coef + 5 * planes);
+    out[41] = (int64_t)g.off_pl; out[42] = (int64_t)g.tw * g.th;
+    out[43] = (int64_t)(orn_loss_ws_bytes_for(loss_type, B, Ch, H, W) / 4);
+    return 0;
 }

@@ -328,20 +328,57 @@ int orn_loss_msssim_init()
 }
 
 // floats behind the pyramid of the forward: the gradient planes of levels 1..4, then the coefficients [5][planes] and the value
-static size_t ms_loss_floats(size_t planes, int H, int W, float *grad[5], float **kbuf, float *base)
+// (as float offsets from the start of the region)
+static size_t ms_loss_floats(size_t planes, int H, int W, size_t grad[5], size_t *kbuf)
 {
     int Hs[5], Ws[5];
     orn_msssim_geom(H, W, Hs, Ws);
     size_t f = orn_align(orn_msssim_pyramid_floats(planes, H, W) * 4) / 4;
     for (int l = 1; l < 5; ++l) {
-        if (grad) grad[l] = base + f;
+        if (grad) grad[l] = f;
         f += orn_align(planes * Hs[l] * Ws[l] * 4) / 4;
     }
-    if (kbuf) *kbuf = base + f;
+    if (kbuf) *kbuf = f;
     return f + orn_align((5 * planes + 1) * 4) / 4;
 }
 
-size_t orn_loss_msssim_ws_floats(size_t planes, int H, int W) { return ms_loss_floats(planes, H, W, nullptr, nullptr, nullptr); }
+size_t orn_loss_msssim_ws_floats(size_t planes, int H, int W) { return ms_loss_floats(planes, H, W, nullptr, nullptr); }
+
+void orn_loss_msssim_layout(size_t planes, int H, int W, size_t grad[5], size_t *coef)
+{
+    grad[0] = 0;
+    ms_loss_floats(planes, H, W, grad, coef);
+}
+
+// One backward launch's geometry in the kernel's argument: the level's planes and sizes, the 16x64 tiling of the IMAGE (*grid), the
+// float4 load path's condition and, where a level above feeds in (pool), its size and padding.  The caller adds k, gnext, g, the
+// pixel-term scales and part_l1.  orn_launch_loss_msssim and orn_debug_msssim_level_bwd both come through here.
+static MsBwdP ms_bwd_geom(const float *x, const float *y, const int *frame_idx, size_t frame_stride, int H, int W, bool pool, int planes,
+                          dim3 *grid)
+{
+    MsBwdP q = {};
+    q.x = x; q.y = y;
+    q.frame_idx = frame_idx; q.frame_stride = frame_stride;
+    q.H = H; q.W = W; q.Hv = H - 10; q.Wv = W - 10;
+    q.tiles_w = orn_cdiv(W, ML_TW);
+    q.vec4 = (W % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx)) ? 1 : 0;
+    if (pool) { q.Ho = orn_msssim_pooled(H); q.Wo = orn_msssim_pooled(W); q.ph = H % 2; q.pw = W % 2; }
+    *grid = dim3(q.tiles_w * orn_cdiv(H, ML_TH), planes);
+    return q;
+}
+
+// form: 0 SSIM map (level 4), 1 CS map (levels 3..1), 2 CS map at level 0 with the gradient, 3 level 0, the partials alone
+static int ms_bwd_launch(int form, const MsBwdP &q, dim3 gr, hipStream_t st)
+{
+    const dim3 bl(256);
+    const size_t lds = ML_LDS_FLOATS * 4;
+    if (form == 0) hipLaunchKernelGGL((k_msssim_level_bwd<MS_SSIM, false, true>), gr, bl, lds, st, q);
+    else if (form == 1) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, false, true>), gr, bl, lds, st, q);
+    else if (form == 2) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, true, true>), gr, bl, lds, st, q);
+    else hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, true, false>), gr, bl, lds, st, q);
+    ORN_LAUNCH_CHECK("msssim_level_bwd");
+    return 0;
+}
 
 // 5 + 1 + 5 launches (forward only: 5 + 1 + 1).  The callers have checked min(H, W) > 160, planes <= 64 and the workspace.
 int orn_launch_loss_msssim(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int planes, int H, int W,
@@ -352,8 +389,10 @@ int orn_launch_loss_msssim(const float *pred, const float *target, const int *fr
     OrnMsPyramid py;
     // one group of `planes` planes; with a frame index the group's target is row *frame_idx of the frame table
     ORN_TRY(orn_launch_msssim_levels(pred, target, frame_idx, 1, planes, H, W, ms_ws, st, &py));
-    float *grad[5] = {}, *kbuf = nullptr;
-    ms_loss_floats((size_t)planes, H, W, grad, &kbuf, ms_ws);
+    size_t goff[5] = {}, koff = 0;
+    ms_loss_floats((size_t)planes, H, W, goff, &koff);
+    float *grad[5] = {}, *kbuf = ms_ws + koff;
+    for (int l = 1; l < 5; ++l) grad[l] = ms_ws + goff[l];
     MsCoefP c;
     c.part = py.part;
     for (int l = 0; l < 5; ++l) { c.part_off[l] = py.part_off[l]; c.nblk[l] = py.nblk[l]; c.nmap[l] = py.nmap[l]; }
@@ -361,25 +400,42 @@ int orn_launch_loss_msssim(const float *pred, const float *target, const int *fr
     hipLaunchKernelGGL(k_msssim_coef, dim3(1), dim3(64), 0, st, c);
     ORN_LAUNCH_CHECK("msssim_coef");
     *ms_val = c.val;
-    const size_t lds = ML_LDS_FLOATS * 4;
     for (int l = dpred ? 4 : 0; l >= 0; --l) {
-        MsBwdP q = {};
-        q.x = l ? py.pooled[l][0] : pred;
-        q.y = l ? py.pooled[l][1] : target;
-        q.frame_idx = l ? nullptr : frame_idx; q.frame_stride = frame_stride;
-        q.H = py.Hs[l]; q.W = py.Ws[l]; q.Hv = q.H - 10; q.Wv = q.W - 10;
-        q.tiles_w = orn_cdiv(q.W, ML_TW);
-        q.vec4 = (q.W % 4 == 0 && ((uintptr_t)q.x | (uintptr_t)q.y) % 16 == 0 && (frame_stride % 4 == 0 || !q.frame_idx)) ? 1 : 0;
+        dim3 gr;
+        MsBwdP q = ms_bwd_geom(l ? py.pooled[l][0] : pred, l ? py.pooled[l][1] : target, l ? nullptr : frame_idx, frame_stride,
+                               py.Hs[l], py.Ws[l], l < 4, planes, &gr);
         q.k = kbuf + (size_t)l * planes;
-        if (l < 4) { q.gnext = grad[l + 1]; q.Ho = py.Hs[l + 1]; q.Wo = py.Ws[l + 1]; q.ph = q.H % 2; q.pw = q.W % 2; }
+        if (l < 4) q.gnext = grad[l + 1];
         q.g = l ? grad[l] : dpred;
         q.g_l1 = g_l1; q.g_l2 = g_l2; q.part_l1 = part_l1;
-        const dim3 gr(q.tiles_w * orn_cdiv(q.H, ML_TH), planes), bl(256);
-        if (l == 4) hipLaunchKernelGGL((k_msssim_level_bwd<MS_SSIM, false, true>), gr, bl, lds, st, q);
-        else if (l > 0) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, false, true>), gr, bl, lds, st, q);
-        else if (dpred) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, true, true>), gr, bl, lds, st, q);
-        else hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, true, false>), gr, bl, lds, st, q);
-        ORN_LAUNCH_CHECK("msssim_level_bwd");
+        ORN_TRY(ms_bwd_launch(l == 4 ? 0 : (l > 0 ? 1 : (dpred ? 2 : 3)), q, gr, st));
     }
     return 0;
+}
+
+extern "C" int orn_debug_msssim_level_bwd_tiles(int H, int W)
+{
+    if (H < 11 || W < 11) return 0;
+    dim3 gr;
+    ms_bwd_geom(nullptr, nullptr, nullptr, 0, H, W, false, 1, &gr);
+    return (int)gr.x;
+}
+
+extern "C" int orn_debug_msssim_level_bwd(int form, const float *x, const float *y, const float *k, const float *gnext,
+                                          const int *frame_idx, size_t frame_stride, int planes, int H, int W, float g_l1, float g_l2,
+                                          float *g, float *part_l1, void *stream)
+{
+    ORN_REQUIRE(form >= 0 && form <= 3, "debug_msssim_level_bwd: form %d is not one of 0..3", form);
+    ORN_REQUIRE(x && y, "debug_msssim_level_bwd: null pointer");
+    ORN_REQUIRE(planes >= 1 && planes <= 65535, "debug_msssim_level_bwd: bad plane count %d", planes);
+    ORN_REQUIRE(H >= 11 && W >= 11 && (long)H * W <= (1L << 26), "debug_msssim_level_bwd: unsupported size %dx%d", H, W);
+    ORN_REQUIRE(form == 3 || (k && g), "debug_msssim_level_bwd: forms 0..2 need k and g");
+    ORN_REQUIRE(form < 2 || part_l1, "debug_msssim_level_bwd: the level-0 forms need part_l1");
+    ORN_REQUIRE(form >= 2 || !frame_idx, "debug_msssim_level_bwd: only the level-0 forms take a frame index");
+    ORN_TRY(orn_loss_msssim_init());
+    dim3 gr;
+    MsBwdP q = ms_bwd_geom(x, y, frame_idx, frame_stride, H, W, gnext != nullptr, planes, &gr);
+    q.k = k; q.gnext = gnext; q.g = g;
+    q.g_l1 = g_l1; q.g_l2 = g_l2; q.part_l1 = form >= 2 ? part_l1 : nullptr;
+    return ms_bwd_launch(form, q, gr, (hipStream_t)stream);
 }

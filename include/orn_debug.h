@@ -1,8 +1,8 @@
 /* orn_debug.h -- test and probe entry points of liborn.so.  NOT part of the drop-in boundary: nothing here has a reference
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
  * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
- * the merge backward's (tests/test_gpu_merge16.py) and the fused first block's and the slab-summing stem backward's
- * (tests/test_gpu_stage0.py). */
+ * the merge backward's (tests/test_gpu_merge16.py), the fused first block's and the slab-summing stem backward's
+ * (tests/test_gpu_stage0.py) and the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -73,6 +73,43 @@ ORN_API int orn_debug_stage0_bwd(const float *x, const float *wf, const float *z
 ORN_API int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
                                      const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
                                      float *db1, float *ws, size_t ws_bytes, void *stream);
+/* The MS-SSIM losses (Fusion10 / 11 / 12; orn_loss.hip, orn_loss_msssim.hip) one launch at a time, at any plane size H, W >= 11 --
+ * orn_loss_fwd_bwd itself takes nothing below 161 px, so levels 1..4 only ever see what pooling leaves.  The kernel argument of
+ * every launch is built by the function the product launcher builds it with (tile counts, pooled size and padding, the float4
+ * condition, the grid); tests/test_gpu_msssim_levels.py pins the kernels elementwise to fp64 through these.  Every entry returns
+ * ORN_E_ARG with a message for arguments it declines (a null pointer, planes outside 1..65535, H or W below 11, H*W above 2^26, a
+ * form outside 0..3) and launches nothing then.  All pointers are device pointers; planes are fp32 [planes][H][W].
+ *   gauss_taps: the 11 filter taps every SSIM / MS-SSIM kernel uses (host array; no GPU is touched): fp32 exp, fp32 sum in index
+ *          order, fp32 divide.
+ *   level_fwd_tiles / level_bwd_tiles: work-groups per plane of the launch below (16x64 tiles of the valid map (H-10) x (W-10) /
+ *          of the image); 0 for H or W below 11.
+ *   level_fwd: one k_msssim_level launch.  part [planes][tiles][2] = {sum of the SSIM map, sum of the CS map} over the tile's part
+ *          of the valid map; every element is written.  nx, ny (both or neither): the 2x2 average pool of x and y,
+ *          [planes][Ho][Wo], Ho = (H + 2 (H % 2)) / 2 (avg_pool2d(2, padding = size % 2), count_include_pad); every element is
+ *          written, by exactly one work-group.
+ *   level_bwd: one k_msssim_level_bwd launch.  form 0: the SSIM map's derivatives (level 4 of the chain); 1: the CS map's (levels
+ *          3..1); 2: the CS map's at level 0, with the pixel term; 3: level 0 without the gradient.
+ *          g [planes][H][W] = k[plane] * d(sum of the map over the valid region)/dx + the pool's adjoint of gnext
+ *          (0.25 * gnext[(y + H % 2) / 2][(x + W % 2) / 2]; gnext [planes][Ho][Wo], NULL: none) + (form 2) g_l1 * sign(x - y) +
+ *          g_l2 * (x - y); every element is written.  Forms 2 and 3 also write part_l1 [planes][tiles][2] = {sum |x - y|,
+ *          sum (x - y)^2} per image tile; form 3 writes nothing else and reads neither k nor gnext (k, gnext, g may be NULL).
+ *          frame_idx (forms 2 and 3, optional): y is taken at y + *frame_idx * frame_stride floats; the float4 load path needs
+ *          W % 4 == 0, 16-byte aligned x and y and, with a frame index, frame_stride % 4 == 0.
+ *   loss_msssim_layout: where orn_loss_fwd_bwd(loss_type = an MS-SSIM id, B, Ch, H, W) keeps its intermediates, as float offsets
+ *          from the start of its workspace; out[44] (host).  Per level l = 0..4, out[8 l + ..]: 0, 1 the level's H, W; 2, 3 the
+ *          pooled pred / target planes [B*Ch][H_l][W_l] (-1 at level 0: the caller's arrays); 4 the forward's tile partials
+ *          [B*Ch][nblk][2]; 5 nblk; 6 the level's gradient planes (-1 at level 0: dpred); 7 the level's coefficients k[l] [B*Ch].
+ *          out[40]: the MS-SSIM value; out[41], out[42]: the level-0 {|d|, d^2} partials and their tiles per plane; out[43]: the
+ *          workspace in floats (orn_loss_ws_bytes_for / 4). */
+ORN_API void orn_debug_gauss_taps(float *g11);
+ORN_API int orn_debug_msssim_level_fwd_tiles(int H, int W);
+ORN_API int orn_debug_msssim_level_bwd_tiles(int H, int W);
+ORN_API int orn_debug_msssim_level_fwd(const float *x, const float *y, int planes, int H, int W, float *part, float *nx, float *ny,
+                                       void *stream);
+ORN_API int orn_debug_msssim_level_bwd(int form, const float *x, const float *y, const float *k, const float *gnext,
+                                       const int *frame_idx, size_t frame_stride, int planes, int H, int W, float g_l1, float g_l2,
+                                       float *g, float *part_l1, void *stream);
+ORN_API int orn_debug_loss_msssim_layout(int loss_type, int B, int Ch, int H, int W, int64_t *out);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);

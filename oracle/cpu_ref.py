@@ -22,7 +22,7 @@ Parity status
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -258,11 +258,13 @@ def _gaussian_filter(x: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
 
 
 def ssim_maps(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0,
-              K: Tuple[float, float] = (0.01, 0.03)):
-    """ssim_map, cs_map of pytorch_msssim ``_ssim`` (published algorithm; parity unpinned)."""
+              K: Tuple[float, float] = (0.01, 0.03), win: Optional[torch.Tensor] = None):
+    """ssim_map, cs_map of pytorch_msssim ``_ssim`` (published algorithm; parity unpinned).  win: the 11 taps to filter with
+    (default: the Gaussian formed in the dtype of x; the package and liborn form it in fp32 whatever the dtype of x)."""
     c1 = (K[0] * data_range) ** 2
     c2 = (K[1] * data_range) ** 2
-    win = _gauss_1d(dtype=x.dtype)
+    if win is None:
+        win = _gauss_1d(dtype=x.dtype)
     mu1 = _gaussian_filter(x, win)
     mu2 = _gaussian_filter(y, win)
     mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
@@ -284,13 +286,13 @@ def ssim(x, y, data_range: float = 1.0, size_average: bool = True):
 _MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
 
-def ms_ssim(x, y, data_range: float = 1.0, size_average: bool = True):
-    """``pytorch_msssim.ms_ssim`` (5 scales, avg_pool2d(2) with padding = size%2; parity unpinned)."""
+def ms_ssim(x, y, data_range: float = 1.0, size_average: bool = True, win: Optional[torch.Tensor] = None):
+    """``pytorch_msssim.ms_ssim`` (5 scales, avg_pool2d(2) with padding = size%2; parity unpinned).  win: as ssim_maps."""
     weights = torch.tensor(_MS_WEIGHTS, dtype=x.dtype)
     mcs = []
     levels = weights.numel()
     for i in range(levels):
-        ssim_map, cs_map = ssim_maps(x, y, data_range)
+        ssim_map, cs_map = ssim_maps(x, y, data_range, win=win)
         ssim_pc = torch.flatten(ssim_map, 2).mean(-1)
         cs = torch.flatten(cs_map, 2).mean(-1)
         if i < levels - 1:
