@@ -1,20 +1,19 @@
-// A7 + A10  loss_fn (utils.py:139-189: L2, L1, Fusion6 = 0.7*L1 + 0.3*(1-SSIM)) fused with its
-// gradient and with psnr_fn (utils.py:191-199).  HBM-bound on 11 MB planes; two tiled passes:
-//   k_ssim_stats : 11-tap separable Gaussian (sigma 1.5, valid) of p, t, p^2, t^2, pt in LDS ->
-//                  SSIM map value (summed) and dS/dm, dS/dq, dS/dr maps
-//   k_loss_grad  : adjoint (full) filter of the three maps + L1/L2 terms -> dL/dpred, |p-t| and
-//                  (p-t)^2 sums
-// followed by a fixed-order finalize.  SSIM follows pytorch_msssim 0.2.1's published algorithm
-// (the package is not in the reference tree: parity unpinned, see oracle/cpu_ref.py).
-#include "orn_internal.h"
+// A7 + A10  loss_fn (utils.py:139-189) fused with its gradient and with psnr_fn (utils.py:191-199), and N3 msssim_fn.  Every loss id
+// resolves through orn_loss_spec_of to w_l1 * L1 + w_l2 * MSE + w_struct * (1 - s); one 16x64 tiling of the image for all kinds:
+//   k_fusion6   : s = ssim, one pass per tile through the tile machine of orn_ssim_tile.h: SSIM map, its derivative maps, their adjoint
+//                 filter, the pixel term -> dL/dpred and the tile partials {ssim}, {|d|, d^2}.  TC_FILL makes the target's own
+//                 filtered maps once per video, TC_READ reads them in the step
+//   k_loss_grad : no structural term (L1, L2, Fusion7 / 8);  k_loss_ext: the split step, whose loss and gradient the caller computed
+//   k_msssim_level, k_msssim_frames_finalize: MS-SSIM, as a metric and as the forward of the MS-SSIM losses (orn_loss_msssim.hip)
+// each followed by a fixed-order finalize.  SSIM and MS-SSIM follow pytorch_msssim 0.2.1's published algorithm (the package is not in
+// the reference tree: parity unpinned, see oracle/cpu_ref.py).
+#include "orn_ssim_tile.h"
 
-#define SS_TH 16
+#define SS_TH 16             // k_loss_grad, k_loss_ext and k_msssim_level (k_fusion6 too: the static_assert in orn_launch_loss)
 #define SS_TW 64
 #define SS_PH (SS_TH + 10)
 #define SS_PW (SS_TW + 10)
 #define SS_PWP 76            // padded row stride (floats): 16-byte aligned rows for float4 LDS reads
-
-__constant__ float c_gauss[11];
 
 struct LossP {
     const float *pred, *target;
@@ -25,7 +24,7 @@ struct LossP {
     float *part_l1;            // [n_blocks][2]
     float *dpred;              // may be null
     int loss_type;
-    int vec4;                  // W % 4 == 0 and 16-byte aligned planes: the fused Fusion6 kernel loads float4
+    int vec4;                  // orn_loss_vec4: the fused Fusion6 kernel loads float4
     // Fusion6, optional: the TARGET's own filtered maps G*t and G*t^2 on the valid map, [frame][2][planes][Hv][Wv], computed
     // once per video by k_fusion6<.., TC_FILL> with the arithmetic of the in-kernel form (same taps, same fmaf order: the
     // step's results do not change by a bit).  The target never changes during a fit, and 288 GB of HBM hold 2.9 GB of
@@ -36,37 +35,23 @@ struct LossP {
     int tiles_w, tiles_h;
 };
 
-// Fusion6 in ONE pass per image tile (round 3; rounds 1-2 ran k_ssim_stats + k_loss_grad with the three dS maps making a
-// round trip through HBM).  A work-group owns a 16x64 tile of dL/dpred.  It needs the dS maps on the tile + a 10-pixel apron
-// (adjoint of the valid 11x11 filter), hence p and t on the tile + a 20-pixel apron: the five filtered maps and the three dS
-// maps are RECOMPUTED on the apron (2.9x / 1.9x the arithmetic of the tile alone: the separable filters are cheap VALU work)
-// and never leave LDS.  HBM traffic: p, t read (aprons from L2), dL/dpred written.  Register-blocked separable filtering:
-// every thread produces 4 adjacent outputs from a 14-wide window (3x fewer LDS reads than one output per thread).
-//   LDS (80 KB, two work-groups per CU):  X [2][36][88] p, t patch | Hm [5][36][76] row-filtered p, t, p^2, t^2, pt
-//                                         D [3][26][76] dS/dm, dS/dq, dS/dr (over X) | Hh [3][26][64] row-adjoint of D (over Hm)
-#define F6_TH 16
-#define F6_TW 64
-#define F6_PH (F6_TH + 20)
-#define F6_PWP 88            // 84 columns used
-#define F6_DH (F6_TH + 10)
-#define F6_DWP 76            // 74 columns used
-#define F6_LDS_FLOATS (2 * F6_PH * F6_PWP + 5 * F6_PH * F6_DWP + 16)
-
+// Fusion6 in ONE pass per image tile (round 3; rounds 1-2 ran k_ssim_stats + k_loss_grad with the three dS maps making a round trip
+// through HBM): the tile machine of orn_ssim_tile.h with the SSIM map.  HBM traffic: p, t read (aprons from L2), dL/dpred written.
 enum { TC_NONE = 0, TC_READ = 1, TC_FILL = 2 };
 // L2T: the pixel term of the gradient is g_l2 * d (Fusion1 / 3 / 5: MSE + SSIM) instead of g_l1 * sign(d)
 template <bool GRAD, int TC, bool L2T = false>
 __global__ void __launch_bounds__(256) k_fusion6(LossP q)
 {
     extern __shared__ __attribute__((aligned(16))) float f6s[];
-    float *Xp = f6s, *Xt = f6s + F6_PH * F6_PWP;
-    float *Hm = f6s + 2 * F6_PH * F6_PWP;
+    float *Xp = f6s, *Xt = f6s + ST_PH * ST_PWP;
+    float *Hm = f6s + 2 * ST_PH * ST_PWP;
     float *Dm = f6s;                       // written after the last read of Xp / Xt
     float *Hh = Hm;                        // written after the last read of Hm
-    float *sred = f6s + 2 * F6_PH * F6_PWP + 5 * F6_PH * F6_DWP;
+    float *sred = f6s + 2 * ST_PH * ST_PWP + 5 * ST_PH * ST_DWP;
     const int t = threadIdx.x;
     const int plane = blockIdx.y;
     const int tw = blockIdx.x % q.tiles_w, th = blockIdx.x / q.tiles_w;
-    const int y0 = th * F6_TH, x0 = tw * F6_TW;
+    const int y0 = th * ST_TH, x0 = tw * ST_TW;
     const size_t HW = (size_t)q.H * q.W;
     const size_t fr = TC == TC_FILL ? (size_t)blockIdx.z : (q.frame_idx ? (size_t)(*q.frame_idx) : 0);
     const float *tp = q.target + fr * q.frame_stride + (size_t)plane * HW;
@@ -79,155 +64,51 @@ __global__ void __launch_bounds__(256) k_fusion6(LossP q)
     // the cached target statistics of this thread's nine map positions (column filter mapping below) are requested first: two
     // barriers lie between here and their use.  (Loaded where they are used, they cost more than the two filters they save:
     // with two work-groups per CU nothing covers a round trip to HBM in the middle of a phase.)
-    constexpr int RPT = 9;
-    const int vrg = t / F6_DWP, vj = t - vrg * F6_DWP, vr4 = vrg == 2 ? 17 : vrg * RPT;
-    float c_mu[RPT], c_tt[RPT];
-    if (TC == TC_READ && t < 3 * F6_DWP) {
+    constexpr bool P_MAPS = TC != TC_FILL, T_MAPS = TC != TC_READ;       // which of the five maps this mode forms
+    const int vrg = t / ST_DWP, vj = t - vrg * ST_DWP, vr4 = vrg == 2 ? 17 : vrg * ST_RPT;
+    float c_mu[ST_RPT], c_tt[ST_RPT];
+    if (TC == TC_READ && t < 3 * ST_DWP) {
 #pragma unroll
-        for (int o = 0; o < RPT; ++o) {
+        for (int o = 0; o < ST_RPT; ++o) {
             const int vy = min(max(y0 - 10 + vr4 + o, 0), q.Hv - 1), vx = min(max(x0 - 10 + vj, 0), q.Wv - 1);
             c_mu[o] = ts_mu[(size_t)vy * q.Wv + vx];
             c_tt[o] = ts_tt[(size_t)vy * q.Wv + vx];
         }
     }
-    // ---- patch rows y0-10 .. y0+25, columns x0-10 .. x0+73 (LDS column c <-> image column x0 - 10 + c); zero outside the image
-    if (q.vec4) {           // rows are 16-byte aligned: float4 units from image column x0 - 12
-        constexpr int NU = 22, NIT = (F6_PH * NU + 255) / 256;
-        float4 ra[NIT], rb[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int idx = t + it * 256;
-            const int r = idx / NU, u = idx - r * NU;
-            const int gy = y0 - 10 + r, gx = x0 - 12 + 4 * u;
-            ra[it] = make_float4(0.f, 0.f, 0.f, 0.f); rb[it] = ra[it];
-            if (idx < F6_PH * NU && gy >= 0 && gy < q.H && gx >= 0 && gx < q.W) {
-                ra[it] = *reinterpret_cast<const float4 *>(pp + (size_t)gy * q.W + gx);
-                rb[it] = *reinterpret_cast<const float4 *>(tp + (size_t)gy * q.W + gx);
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int idx = t + it * 256;
-            const int r = idx / NU, u = idx - r * NU;
-            if (idx < F6_PH * NU) {
-                const int c = 4 * u - 2;
-                if (u > 0) {
-                    *reinterpret_cast<float2 *>(Xp + r * F6_PWP + c) = make_float2(ra[it].x, ra[it].y);
-                    *reinterpret_cast<float2 *>(Xt + r * F6_PWP + c) = make_float2(rb[it].x, rb[it].y);
-                }
-                *reinterpret_cast<float2 *>(Xp + r * F6_PWP + c + 2) = make_float2(ra[it].z, ra[it].w);
-                *reinterpret_cast<float2 *>(Xt + r * F6_PWP + c + 2) = make_float2(rb[it].z, rb[it].w);
-            }
-        }
-    } else {
-        constexpr int NL = (F6_PH * F6_PWP + 255) / 256;
-#pragma unroll 1
-        for (int it = 0; it < NL; ++it) {
-            const int idx = t + it * 256;
-            const int r = idx / F6_PWP, c = idx - r * F6_PWP;
-            const int gy = y0 - 10 + r, gx = x0 - 10 + c;
-            float a = 0.f, b = 0.f;
-            if (idx < F6_PH * F6_PWP && gy >= 0 && gy < q.H && gx >= 0 && gx < q.W) { a = pp[(size_t)gy * q.W + gx]; b = tp[(size_t)gy * q.W + gx]; }
-            if (idx < F6_PH * F6_PWP) { Xp[idx] = a; Xt[idx] = b; }
-        }
-    }
+    st_load_patch(Xp, Xt, pp, tp, y0, x0, q.H, q.W, q.vec4, t);
     __syncthreads();
-    // ---- row filter: Hm[m][r][j] = sum_k g[k] X[r][j + k], j < 76 (74 used); item = (row r, 4 columns)
-    for (int idx = t; idx < F6_PH * (F6_DWP / 4); idx += 256) {
-        const int r = idx / (F6_DWP / 4), c4 = (idx - r * (F6_DWP / 4)) * 4;
-        float a[16], b[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 va = *reinterpret_cast<const float4 *>(Xp + r * F6_PWP + c4 + 4 * k);
-            const float4 vb = *reinterpret_cast<const float4 *>(Xt + r * F6_PWP + c4 + 4 * k);
-            a[4 * k] = va.x; a[4 * k + 1] = va.y; a[4 * k + 2] = va.z; a[4 * k + 3] = va.w;
-            b[4 * k] = vb.x; b[4 * k + 1] = vb.y; b[4 * k + 2] = vb.z; b[4 * k + 3] = vb.w;
-        }
-        float sp[4] = {0, 0, 0, 0}, st[4] = {0, 0, 0, 0}, spp[4] = {0, 0, 0, 0}, stt[4] = {0, 0, 0, 0}, spt[4] = {0, 0, 0, 0};
-        constexpr bool P_MAPS = TC != TC_FILL, T_MAPS = TC != TC_READ;       // which of the five maps this mode forms
-#pragma unroll
-        for (int k = 0; k < 14; ++k) {
-            const float aa = a[k] * a[k], bb = b[k] * b[k], ab = a[k] * b[k];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const int tap = k - o;
-                if (tap >= 0 && tap < 11) {
-                    const float g = c_gauss[tap];
-                    if (P_MAPS) { sp[o] = fmaf(g, a[k], sp[o]); spp[o] = fmaf(g, aa, spp[o]); spt[o] = fmaf(g, ab, spt[o]); }
-                    if (T_MAPS) { st[o] = fmaf(g, b[k], st[o]); stt[o] = fmaf(g, bb, stt[o]); }
-                }
-            }
-        }
-        float *h = Hm + r * F6_DWP + c4;
-        if (P_MAPS) {
-            *reinterpret_cast<float4 *>(h) = make_float4(sp[0], sp[1], sp[2], sp[3]);
-            *reinterpret_cast<float4 *>(h + 2 * F6_PH * F6_DWP) = make_float4(spp[0], spp[1], spp[2], spp[3]);
-            *reinterpret_cast<float4 *>(h + 4 * F6_PH * F6_DWP) = make_float4(spt[0], spt[1], spt[2], spt[3]);
-        }
-        if (T_MAPS) {
-            *reinterpret_cast<float4 *>(h + F6_PH * F6_DWP) = make_float4(st[0], st[1], st[2], st[3]);
-            *reinterpret_cast<float4 *>(h + 3 * F6_PH * F6_DWP) = make_float4(stt[0], stt[1], stt[2], stt[3]);
-        }
-    }
+    st_row_filter<P_MAPS, T_MAPS>(Xp, Xt, Hm, t);
     __syncthreads();
-    // ---- column filter + SSIM map + dS maps on valid-map rows y0-10+i (i < 26), columns x0-10+j (j < 74).
-    // item = (column j, 9 rows); the third row group restarts at row 17 (rows 17..25: row 17 is computed twice, same value)
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    // ---- column filter + SSIM map + dS maps; item = (column j, 9 rows from r4) as for the prefetch above
     float ssum = 0.f;
-    if (t < 3 * F6_DWP) {
+    if (t < 3 * ST_DWP) {
         const int rg = vrg, j = vj, r4 = vr4;
-        float v[5][RPT];
+        float v[5][ST_RPT];
 #pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            if ((TC == TC_READ && (m == 1 || m == 3)) || (TC == TC_FILL && !(m == 1 || m == 3))) continue;
-            float col[RPT + 10];
+        for (int m = 0; m < 5; ++m)
+            if ((m == 1 || m == 3) ? T_MAPS : P_MAPS) st_col_filter(Hm, m, r4, j, v[m]);
 #pragma unroll
-            for (int k = 0; k < RPT + 10; ++k) col[k] = Hm[(m * F6_PH + r4 + k) * F6_DWP + j];
-#pragma unroll
-            for (int o = 0; o < RPT; ++o) {
-                float acc = 0.f;
-#pragma unroll
-                for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss[k], col[o + k], acc);
-                v[m][o] = acc;
-            }
-        }
-#pragma unroll
-        for (int o = 0; o < RPT; ++o) {
+        for (int o = 0; o < ST_RPT; ++o) {
             const int i = r4 + o;
             const int vy = y0 - 10 + i, vx = x0 - 10 + j;
             float dm = 0.f, dq = 0.f, dr = 0.f;
             if (TC == TC_FILL) {                        // the owned part of the two target maps, once
-                if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && i >= 10 && j >= 10 && j < F6_TW + 10 && (rg < 2 || o > 0)) {
+                if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && i >= 10 && j >= 10 && j < ST_TW + 10 && (rg < 2 || o > 0)) {
                     ts_mu[(size_t)vy * q.Wv + vx] = v[1][o];
                     ts_tt[(size_t)vy * q.Wv + vx] = v[3][o];
                 }
                 continue;
             }
-            if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && j < F6_TW + 10) {
-                const float m = v[0][o], qq = v[2][o], rr = v[4][o];
-                const float mu = TC == TC_READ ? c_mu[o] : v[1][o];
-                const float tt = TC == TC_READ ? c_tt[o] : v[3][o];
-                const float sp = qq - m * m, st = tt - mu * mu, spt = rr - m * mu;
-                const float A1 = 2.f * m * mu + C1, A2 = 2.f * spt + C2;
-                const float B1 = m * m + mu * mu + C1, B2 = sp + st + C2;
-                // two reciprocals (v_rcp_f32 + one Newton step: < 1 ulp) instead of four IEEE divisions (~10 instructions each)
-                float i1 = __builtin_amdgcn_rcpf(B1), i2 = __builtin_amdgcn_rcpf(B2);
-                i1 = i1 * (2.0f - B1 * i1);
-                i2 = i2 * (2.0f - B2 * i2);
-                const float inv = i1 * i2;
-                const float S = A1 * A2 * inv;
+            if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && j < ST_TW + 10) {
+                const float S = st_deriv<true>(v[0][o], TC == TC_READ ? c_mu[o] : v[1][o], v[2][o], TC == TC_READ ? c_tt[o] : v[3][o], v[4][o], dm, dq, dr);
                 if (i >= 10 && j >= 10 && (rg < 2 || o > 0)) ssum += S;      // this tile's own part of the map, once
-                dm = 2.f * mu * (A2 - A1) * inv - 2.f * m * S * i1 + 2.f * m * S * i2;
-                dq = -S * i2;
-                dr = 2.f * A1 * inv;
             }
-            float *d = Dm + i * F6_DWP + j;
-            d[0] = dm; d[F6_DH * F6_DWP] = dq; d[2 * F6_DH * F6_DWP] = dr;      // X is dead since the barrier above
+            st_store_deriv(Dm, i, j, dm, dq, dr);
         }
     }
     if (TC == TC_FILL) return;
     // this thread's four output pixels (last phase) are requested before the two adjoint passes
-    const int fc = t & (F6_TW - 1), fr4 = (t >> 6) * 4;
+    const int fc = t & (ST_TW - 1), fr4 = (t >> 6) * 4;
     float fp[4], ft[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
@@ -236,50 +117,15 @@ __global__ void __launch_bounds__(256) k_fusion6(LossP q)
     }
     __syncthreads();
     float sabs = 0.f, ssq = 0.f;
-    // ---- adjoint row filter: Hh[m][i][c] = sum_k g[k] D[m][i][c + 10 - k]; item = (row i, 4 columns, map m)
     if (GRAD) {
-        for (int idx = t; idx < F6_DH * (F6_TW / 4); idx += 256) {
-            const int r = idx / (F6_TW / 4), c4 = (idx - r * (F6_TW / 4)) * 4;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                float w[16];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float4 vv = *reinterpret_cast<const float4 *>(Dm + (m * F6_DH + r) * F6_DWP + c4 + 4 * k);
-                    w[4 * k] = vv.x; w[4 * k + 1] = vv.y; w[4 * k + 2] = vv.z; w[4 * k + 3] = vv.w;
-                }
-                float hv[4];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss[k], w[o + 10 - k], acc);
-                    hv[o] = acc;
-                }
-                *reinterpret_cast<float4 *>(Hh + (m * F6_DH + r) * F6_TW + c4) = make_float4(hv[0], hv[1], hv[2], hv[3]);
-            }
-        }
+        st_adj_row(Dm, Hh, t);
         __syncthreads();
     }
-    // ---- adjoint column filter + L1 term: thread = (column c, 4 rows)
+    // ---- adjoint column filter + pixel term: thread = (column c, 4 rows)
     {
         const int c = fc, r4 = fr4;
         float am[4] = {0, 0, 0, 0}, aq[4] = {0, 0, 0, 0}, ar[4] = {0, 0, 0, 0};
-        if (GRAD) {
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                float col[14];
-#pragma unroll
-                for (int k = 0; k < 14; ++k) col[k] = Hh[(m * F6_DH + r4 + k) * F6_TW + c];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss[k], col[o + 10 - k], acc);
-                    if (m == 0) am[o] = acc; else if (m == 1) aq[o] = acc; else ar[o] = acc;
-                }
-            }
-        }
+        if (GRAD) st_adj_col(Hh, r4, c, am, aq, ar);
         const int gx = x0 + c;
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
@@ -454,8 +300,6 @@ __global__ void __launch_bounds__(256) k_loss_ext_finalize(LossExtFinal j)
     }
 }
 
-static bool g_gauss_ready = false;
-
 // pytorch_msssim _fspecial_gauss_1d(11, 1.5): fp32 exp, fp32 normalise
 void orn_gauss_taps(float g[11])
 {
@@ -466,20 +310,6 @@ void orn_gauss_taps(float g[11])
         s += g[i];
     }
     for (int i = 0; i < 11; ++i) g[i] /= s;
-}
-
-static int ensure_gauss()
-{
-    if (g_gauss_ready) return 0;
-    float g[11];
-    orn_gauss_taps(g);
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g));
-    if (e != hipSuccess) {
-        orn_set_error("loss: hipMemcpyToSymbol failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    g_gauss_ready = true;
-    return 0;
 }
 
 struct LossGeom { int planes, Hv, Wv, tw, th; size_t nmap, off_pl, total; };
@@ -522,23 +352,14 @@ extern "C" size_t orn_loss_ws_bytes_for(int loss_type, int B, int Ch, int H, int
     return f * 4;
 }
 
-static int ensure_fusion6_lds()
+// Must be called once outside any graph capture (orn_ssim_tile_init).
+int orn_loss_init()
 {
-    static bool done = false;
-    if (done) return 0;
-    hipError_t e = hipSuccess;
-    const void *kerns[] = {(const void *)k_fusion6<true, TC_NONE>, (const void *)k_fusion6<false, TC_NONE>, (const void *)k_fusion6<true, TC_READ>,
-                           (const void *)k_fusion6<false, TC_READ>, (const void *)k_fusion6<false, TC_FILL>,
-                           (const void *)k_fusion6<true, TC_NONE, true>, (const void *)k_fusion6<true, TC_READ, true>};
-    for (const void *k : kerns)
-        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, F6_LDS_FLOATS * 4);
-    if (e != hipSuccess) { orn_set_error("loss: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    done = true;
-    return 0;
+    ORN_TRY(orn_ssim_tile_init({(const void *)k_fusion6<true, TC_NONE>, (const void *)k_fusion6<false, TC_NONE>, (const void *)k_fusion6<true, TC_READ>,
+                                (const void *)k_fusion6<false, TC_READ>, (const void *)k_fusion6<false, TC_FILL>,
+                                (const void *)k_fusion6<true, TC_NONE, true>, (const void *)k_fusion6<true, TC_READ, true>}));
+    return orn_loss_msssim_init();
 }
-
-// Must be called once outside any graph capture (hipMemcpyToSymbol is synchronous).
-int orn_loss_init() { ORN_TRY(ensure_gauss()); ORN_TRY(ensure_fusion6_lds()); return orn_loss_msssim_init(); }
 
 int orn_launch_loss(const float *pred, const float *target, const int *frame_idx, size_t frame_stride, int B, int Ch,
                     int H, int W, int loss_type, float loss_scale, float *stats, float *dpred, float *ws,
@@ -547,7 +368,7 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
     const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
     ORN_REQUIRE(sp, "loss: unsupported loss_type %d", loss_type);
     ORN_TRY(orn_loss_init());
-    static_assert(SS_TH == F6_TH && SS_TW == F6_TW, "one tiling for all loss kernels");
+    static_assert(SS_TH == ST_TH && SS_TW == ST_TW, "one tiling for all loss kernels");
     const LossGeom g = loss_geom(B, Ch, H, W);
     const bool ssim = sp->kind == ORN_LOSS_KIND_SSIM, msssim = sp->kind == ORN_LOSS_KIND_MSSSIM;
     if (ssim) ORN_REQUIRE(g.Hv > 0 && g.Wv > 0, "loss: SSIM needs H,W > 10 (got %dx%d)", H, W);
@@ -562,7 +383,7 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
     q.part_ssim = ws; q.part_l1 = ws + g.off_pl;
     q.dpred = dpred; q.loss_type = loss_type;
     q.tstats = const_cast<float *>(tstats); q.tstats_stride = 2 * g.nmap;
-    q.vec4 = (W % 4 == 0 && ((uintptr_t)pred | (uintptr_t)target) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx)) ? 1 : 0;
+    q.vec4 = orn_loss_vec4(W, (uintptr_t)pred | (uintptr_t)target, frame_stride, frame_idx) ? 1 : 0;
     const double n = (double)g.planes * H * W;
     // (ids 0..2: the values they have always had -- 0.7 * loss_scale / n, 2.0 * loss_scale / n, 0.3 * loss_scale / nmap)
     q.g_l1 = (float)(sp->w_l1 * loss_scale / n);
@@ -580,13 +401,13 @@ int orn_launch_loss(const float *pred, const float *target, const int *frame_idx
         const bool l2t = sp->w_l2 != 0.0;      // SSIM kinds: an L2 pixel term in place of the L1 one (no loss has both)
         if (ssim) {
             if (tstats) {
-                if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q);
-                else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_READ, true>), gr, bl, F6_LDS_FLOATS * 4, st, q);
-                else hipLaunchKernelGGL((k_fusion6<true, TC_READ>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+                if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_READ>), gr, bl, ST_LDS_FLOATS * 4, st, q);
+                else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_READ, true>), gr, bl, ST_LDS_FLOATS * 4, st, q);
+                else hipLaunchKernelGGL((k_fusion6<true, TC_READ>), gr, bl, ST_LDS_FLOATS * 4, st, q);
             }
-            else if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q);
-            else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_NONE, true>), gr, bl, F6_LDS_FLOATS * 4, st, q);
-            else hipLaunchKernelGGL((k_fusion6<true, TC_NONE>), gr, bl, F6_LDS_FLOATS * 4, st, q);
+            else if (!gd) hipLaunchKernelGGL((k_fusion6<false, TC_NONE>), gr, bl, ST_LDS_FLOATS * 4, st, q);
+            else if (l2t) hipLaunchKernelGGL((k_fusion6<true, TC_NONE, true>), gr, bl, ST_LDS_FLOATS * 4, st, q);
+            else hipLaunchKernelGGL((k_fusion6<true, TC_NONE>), gr, bl, ST_LDS_FLOATS * 4, st, q);
         }
         else if (loss_type == ORN_LOSS_L2) { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L2, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L2, false>), gr, bl, 0, st, q); }
         else if (loss_type == ORN_LOSS_L1) { if (gd) hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, true>), gr, bl, 0, st, q); else hipLaunchKernelGGL((k_loss_grad<ORN_LOSS_L1, false>), gr, bl, 0, st, q); }
@@ -614,7 +435,7 @@ int orn_launch_loss_ext(const float *pred, const float *target, const int *frame
     q.H = H; q.W = W; q.tiles_w = g.tw;
     q.part_l1 = ws + g.off_pl;
     q.sc = sc;
-    const bool vec4 = W % 4 == 0 && ((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx);
+    const bool vec4 = orn_loss_vec4(W, (uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred, frame_stride, frame_idx);
     const dim3 gr(g.tw * g.th, g.planes), bl(256);
     if (vec4) hipLaunchKernelGGL(k_loss_ext<true>, gr, bl, 0, st, q);
     else hipLaunchKernelGGL(k_loss_ext<false>, gr, bl, 0, st, q);
@@ -642,9 +463,9 @@ extern "C" int orn_loss_target_stats(const float *frames, int n, int Ch, int H, 
     q.planes = g.planes; q.H = H; q.W = W; q.Hv = g.Hv; q.Wv = g.Wv;
     q.tstats = out; q.tstats_stride = 2 * g.nmap;
     q.loss_type = ORN_LOSS_FUSION6;
-    q.vec4 = (W % 4 == 0 && (uintptr_t)frames % 16 == 0) ? 1 : 0;
+    q.vec4 = orn_loss_vec4(W, (uintptr_t)frames, q.frame_stride, nullptr) ? 1 : 0;      // (frames of Ch * H * W floats: W % 4 == 0 covers the stride)
     q.tiles_w = g.tw; q.tiles_h = g.th;
-    hipLaunchKernelGGL((k_fusion6<false, TC_FILL>), dim3(g.tw * g.th, g.planes, n), dim3(256), F6_LDS_FLOATS * 4, (hipStream_t)stream, q);
+    hipLaunchKernelGGL((k_fusion6<false, TC_FILL>), dim3(g.tw * g.th, g.planes, n), dim3(256), ST_LDS_FLOATS * 4, (hipStream_t)stream, q);
     ORN_LAUNCH_CHECK("loss_target_stats");
     return 0;
 }
@@ -786,7 +607,6 @@ __global__ void __launch_bounds__(256) k_msssim_level(OrnMsLevel q)
 __global__ void __launch_bounds__(256) k_msssim_frames_finalize(const float *__restrict__ part, OrnMsGeom g, int F, int Ch, float *__restrict__ out)
 {
     __shared__ double acc[256];
-    const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
     const int fpb = 256 / Ch, fl = threadIdx.x / Ch, pc = threadIdx.x - fl * Ch;
     const int frame = blockIdx.x * fpb + fl, planes = F * Ch;
     const bool live = fl < fpb && frame < F;
@@ -796,14 +616,9 @@ __global__ void __launch_bounds__(256) k_msssim_frames_finalize(const float *__r
         size_t off = 0;
         double prod = 1.0;
         for (int lv = 0; lv < 5; ++lv) {
-            double ss = 0.0, cs = 0.0;
-            for (int b = 0; b < g.nblk[lv]; ++b) {
-                ss += (double)part[off + 2 * (pl * g.nblk[lv] + b)];
-                cs += (double)part[off + 2 * (pl * g.nblk[lv] + b) + 1];
-            }
+            const double v = orn_msssim_level_mean(part + off, pl, g.nblk[lv], g.nmap[lv], lv);
             off += (size_t)2 * planes * g.nblk[lv];
-            const double v = (lv < 4 ? cs : ss) / (double)g.nmap[lv];
-            prod *= pow(v > 0.0 ? v : 0.0, (double)wts[lv]);
+            prod *= pow(v > 0.0 ? v : 0.0, (double)c_ms_weights[lv]);
         }
         val = prod;
     }
@@ -923,7 +738,7 @@ extern "C" int orn_msssim_frames(const float *pred, const float *targets, const 
     ORN_REQUIRE(pred && targets && out && ws, "msssim_frames: null pointer");
     const int chunk = orn_msssim_frames_chunk(n, Ch, H, W, ws_bytes);
     if (chunk < 1) { orn_set_error("msssim_frames: workspace too small"); return ORN_E_WS; }
-    ORN_TRY(ensure_gauss());
+    ORN_TRY(orn_loss_init());
     for (int k = 0; k < n; k += chunk) {
         const int F = n - k < chunk ? n - k : chunk;
         const size_t at = (size_t)k * Ch * H * W;
@@ -947,7 +762,7 @@ extern "C" int orn_msssim(const float *pred, const float *target, int B, int Ch,
     ORN_REQUIRE(B > 0 && Ch > 0 && B * Ch <= 64, "msssim: bad plane count");
     ORN_REQUIRE((H < W ? H : W) > 160, "msssim: image side must exceed 160 (got %dx%d)", H, W);
     if (ws_bytes < orn_msssim_ws_bytes(B, Ch, H, W)) { orn_set_error("msssim: workspace too small"); return ORN_E_WS; }
-    ORN_TRY(ensure_gauss());
+    ORN_TRY(orn_loss_init());
     return orn_launch_msssim_frames(pred, target, nullptr, 1, B * Ch, H, W, out, (float *)ws, (hipStream_t)stream);
 }
 
@@ -968,7 +783,7 @@ extern "C" int orn_debug_msssim_level_fwd(const float *x, const float *y, int pl
     ORN_REQUIRE((nx != nullptr) == (ny != nullptr), "debug_msssim_level_fwd: nx and ny go together");
     ORN_REQUIRE(planes >= 1 && planes <= 65535, "debug_msssim_level_fwd: bad plane count %d", planes);
     ORN_REQUIRE(H >= 11 && W >= 11 && (long)H * W <= (1L << 26), "debug_msssim_level_fwd: unsupported size %dx%d", H, W);
-    ORN_TRY(ensure_gauss());
+    ORN_TRY(orn_loss_init());
     OrnMsLevel q = ms_level_geom(H, W, nx != nullptr);
     q.x = x; q.y = y; q.rows = nullptr; q.Ch = planes;
     q.part = part; q.nx = nx; q.ny = ny;

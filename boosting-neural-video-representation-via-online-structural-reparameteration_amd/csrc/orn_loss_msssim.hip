@@ -1,35 +1,24 @@
 // The MS-SSIM losses of loss_fn (utils.py:167-172: Fusion10 / 11 / 12 = a * L1 + b * (1 - ms_ssim)) with their gradient.
 //   forward : the five k_msssim_level launches of orn_loss.hip on the step's planes (one group of B*Ch planes); the pooled pred /
 //             target planes of levels 1..4 and the per-tile {ssim, cs} partials stay in the workspace
-//   k_msssim_coef      : per plane the five level means v_l (cs at levels 0..3, ssim at level 4; sums in double, in the tile order of
-//                        k_msssim_frames_finalize, so the value equals orn_msssim's on the same pair), P = prod relu(v_l)^w_l, the
-//                        MS-SSIM value, and k[l][plane] = -w_struct * loss_scale * w_l * P / v_l / planes / nmap_l (0 where v_l <= 0)
+//   k_msssim_coef      : per plane the five level means v_l (orn_msssim_level_mean, which k_msssim_frames_finalize calls too: the
+//                        value equals orn_msssim's on the same pair), P = prod relu(v_l)^w_l, the MS-SSIM value, and
+//                        k[l][plane] = -w_struct * loss_scale * w_l * P / v_l / planes / nmap_l (0 where v_l <= 0)
 //   k_msssim_level_bwd : levels 4, 3, 2, 1, 0.  g_l = k[l] * (G^T dm + 2 x G^T dq + y G^T dr) + avg-pool adjoint of g_{l+1}, where
 //                        dm / dq / dr are the derivatives of level l's map (CS at 0..3, SSIM at 4) with respect to the filtered
 //                        G*x, G*x^2, G*xy.  A work-group owns a 16x64 tile of g_l and recomputes the five filtered maps on the tile
-//                        plus a 20-pixel apron in LDS: the layout, the register blocking and the fmaf order of k_fusion6
-//                        (orn_loss.hip), which is the same computation for one level with the SSIM map.  Level 0 adds the L1 / L2
-//                        term, writes dpred and the {|d|, d^2} tile partials of the loss finalize.
+//                        plus a 20-pixel apron in LDS through the functions of orn_ssim_tile.h, as k_fusion6 (orn_loss.hip) does for
+//                        one level with the SSIM map.  Level 0 adds the L1 / L2 term, writes dpred and the {|d|, d^2} tile partials.
 // No atomics, fixed-order sums: run-to-run bit-identical.  Levels shrink to 45x80 at 720p and 11x12 at the smallest legal size:
 // every load is bounds-checked against the level's own H x W and everything outside is zero, as the valid filter's adjoint needs.
-#include "orn_internal.h"
-
-#define ML_TH 16
-#define ML_TW 64
-#define ML_PH (ML_TH + 20)
-#define ML_PWP 88            // 84 columns used
-#define ML_DH (ML_TH + 10)
-#define ML_DWP 76            // 74 columns used
-#define ML_LDS_FLOATS (2 * ML_PH * ML_PWP + 5 * ML_PH * ML_DWP + 16)
-
-__constant__ float c_gauss_ms[11];
+#include "orn_ssim_tile.h"
 
 struct MsBwdP {
     const float *x, *y;            // this level's pred / target planes [planes][H][W]
     const int *frame_idx;          // level 0, optional: the target is y + *frame_idx * frame_stride
     size_t frame_stride;
     int H, W, Hv, Wv, tiles_w;
-    int vec4;                      // W % 4 == 0 and 16-byte aligned planes
+    int vec4;                      // orn_loss_vec4
     const float *k;                // [planes] this level's coefficients
     const float *gnext;            // level l+1's gradient [planes][Ho][Wo]; null at level 4
     int Ho, Wo, ph, pw;
@@ -44,149 +33,42 @@ template <int KIND, bool LAST, bool GRAD>
 __global__ void __launch_bounds__(256) k_msssim_level_bwd(MsBwdP q)
 {
     extern __shared__ __attribute__((aligned(16))) float mls[];
-    float *Xp = mls, *Xt = mls + ML_PH * ML_PWP;
-    float *Hm = mls + 2 * ML_PH * ML_PWP;
+    float *Xp = mls, *Xt = mls + ST_PH * ST_PWP;
+    float *Hm = mls + 2 * ST_PH * ST_PWP;
     float *Dm = mls;                       // written after the last read of Xp / Xt
     float *Hh = Hm;                        // written after the last read of Hm
-    float *sred = mls + 2 * ML_PH * ML_PWP + 5 * ML_PH * ML_DWP;
+    float *sred = mls + 2 * ST_PH * ST_PWP + 5 * ST_PH * ST_DWP;
     const int t = threadIdx.x;
     const int plane = blockIdx.y;
     const int tw = blockIdx.x % q.tiles_w, th = blockIdx.x / q.tiles_w;
-    const int y0 = th * ML_TH, x0 = tw * ML_TW;
+    const int y0 = th * ST_TH, x0 = tw * ST_TW;
     const size_t HW = (size_t)q.H * q.W;
     const float *tp = q.y + (q.frame_idx ? (size_t)(*q.frame_idx) * q.frame_stride : 0) + (size_t)plane * HW;
     const float *pp = q.x + (size_t)plane * HW;
     if (GRAD) {
-        // ---- patch rows y0-10 .. y0+25, columns x0-10 .. x0+73 (LDS column c <-> image column x0 - 10 + c); zero outside the image
-        if (q.vec4) {           // rows are 16-byte aligned: float4 units from image column x0 - 12
-            constexpr int NU = 22, NIT = (ML_PH * NU + 255) / 256;
-            float4 ra[NIT], rb[NIT];
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int idx = t + it * 256;
-                const int r = idx / NU, u = idx - r * NU;
-                const int gy = y0 - 10 + r, gx = x0 - 12 + 4 * u;
-                ra[it] = make_float4(0.f, 0.f, 0.f, 0.f); rb[it] = ra[it];
-                if (idx < ML_PH * NU && gy >= 0 && gy < q.H && gx >= 0 && gx < q.W) {
-                    ra[it] = *reinterpret_cast<const float4 *>(pp + (size_t)gy * q.W + gx);
-                    rb[it] = *reinterpret_cast<const float4 *>(tp + (size_t)gy * q.W + gx);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int idx = t + it * 256;
-                const int r = idx / NU, u = idx - r * NU;
-                if (idx < ML_PH * NU) {
-                    const int c = 4 * u - 2;
-                    if (u > 0) {
-                        *reinterpret_cast<float2 *>(Xp + r * ML_PWP + c) = make_float2(ra[it].x, ra[it].y);
-                        *reinterpret_cast<float2 *>(Xt + r * ML_PWP + c) = make_float2(rb[it].x, rb[it].y);
-                    }
-                    *reinterpret_cast<float2 *>(Xp + r * ML_PWP + c + 2) = make_float2(ra[it].z, ra[it].w);
-                    *reinterpret_cast<float2 *>(Xt + r * ML_PWP + c + 2) = make_float2(rb[it].z, rb[it].w);
-                }
-            }
-        } else {
-            constexpr int NL = (ML_PH * ML_PWP + 255) / 256;
-#pragma unroll 1
-            for (int it = 0; it < NL; ++it) {
-                const int idx = t + it * 256;
-                const int r = idx / ML_PWP, c = idx - r * ML_PWP;
-                const int gy = y0 - 10 + r, gx = x0 - 10 + c;
-                float a = 0.f, b = 0.f;
-                if (idx < ML_PH * ML_PWP && gy >= 0 && gy < q.H && gx >= 0 && gx < q.W) { a = pp[(size_t)gy * q.W + gx]; b = tp[(size_t)gy * q.W + gx]; }
-                if (idx < ML_PH * ML_PWP) { Xp[idx] = a; Xt[idx] = b; }
-            }
-        }
+        st_load_patch(Xp, Xt, pp, tp, y0, x0, q.H, q.W, q.vec4, t);
         __syncthreads();
-        // ---- row filter: Hm[m][r][j] = sum_k g[k] X[r][j + k], j < 76 (74 used); item = (row r, 4 columns)
-        for (int idx = t; idx < ML_PH * (ML_DWP / 4); idx += 256) {
-            const int r = idx / (ML_DWP / 4), c4 = (idx - r * (ML_DWP / 4)) * 4;
-            float a[16], b[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float4 va = *reinterpret_cast<const float4 *>(Xp + r * ML_PWP + c4 + 4 * k);
-                const float4 vb = *reinterpret_cast<const float4 *>(Xt + r * ML_PWP + c4 + 4 * k);
-                a[4 * k] = va.x; a[4 * k + 1] = va.y; a[4 * k + 2] = va.z; a[4 * k + 3] = va.w;
-                b[4 * k] = vb.x; b[4 * k + 1] = vb.y; b[4 * k + 2] = vb.z; b[4 * k + 3] = vb.w;
-            }
-            float sp[4] = {0, 0, 0, 0}, st[4] = {0, 0, 0, 0}, spp[4] = {0, 0, 0, 0}, stt[4] = {0, 0, 0, 0}, spt[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int k = 0; k < 14; ++k) {
-                const float aa = a[k] * a[k], bb = b[k] * b[k], ab = a[k] * b[k];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    const int tap = k - o;
-                    if (tap >= 0 && tap < 11) {
-                        const float g = c_gauss_ms[tap];
-                        sp[o] = fmaf(g, a[k], sp[o]); spp[o] = fmaf(g, aa, spp[o]); spt[o] = fmaf(g, ab, spt[o]);
-                        st[o] = fmaf(g, b[k], st[o]); stt[o] = fmaf(g, bb, stt[o]);
-                    }
-                }
-            }
-            float *h = Hm + r * ML_DWP + c4;
-            *reinterpret_cast<float4 *>(h) = make_float4(sp[0], sp[1], sp[2], sp[3]);
-            *reinterpret_cast<float4 *>(h + ML_PH * ML_DWP) = make_float4(st[0], st[1], st[2], st[3]);
-            *reinterpret_cast<float4 *>(h + 2 * ML_PH * ML_DWP) = make_float4(spp[0], spp[1], spp[2], spp[3]);
-            *reinterpret_cast<float4 *>(h + 3 * ML_PH * ML_DWP) = make_float4(stt[0], stt[1], stt[2], stt[3]);
-            *reinterpret_cast<float4 *>(h + 4 * ML_PH * ML_DWP) = make_float4(spt[0], spt[1], spt[2], spt[3]);
-        }
+        st_row_filter<true, true>(Xp, Xt, Hm, t);
         __syncthreads();
-        // ---- column filter + derivative maps on valid-map rows y0-10+i (i < 26), columns x0-10+j (j < 74).
-        // item = (column j, 9 rows); the third row group restarts at row 17 (rows 17..25: row 17 is computed twice, same value)
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        constexpr int RPT = 9;
-        if (t < 3 * ML_DWP) {
-            const int rg = t / ML_DWP, j = t - rg * ML_DWP, r4 = rg == 2 ? 17 : rg * RPT;
-            float v[5][RPT];
+        // ---- column filter + derivative maps; item = (column j, 9 rows from r4)
+        if (t < 3 * ST_DWP) {
+            const int rg = t / ST_DWP, j = t - rg * ST_DWP, r4 = rg == 2 ? 17 : rg * ST_RPT;
+            float v[5][ST_RPT];
 #pragma unroll
-            for (int m = 0; m < 5; ++m) {
-                float col[RPT + 10];
+            for (int m = 0; m < 5; ++m) st_col_filter(Hm, m, r4, j, v[m]);
 #pragma unroll
-                for (int k = 0; k < RPT + 10; ++k) col[k] = Hm[(m * ML_PH + r4 + k) * ML_DWP + j];
-#pragma unroll
-                for (int o = 0; o < RPT; ++o) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss_ms[k], col[o + k], acc);
-                    v[m][o] = acc;
-                }
-            }
-#pragma unroll
-            for (int o = 0; o < RPT; ++o) {
+            for (int o = 0; o < ST_RPT; ++o) {
                 const int i = r4 + o;
                 const int vy = y0 - 10 + i, vx = x0 - 10 + j;
                 float dm = 0.f, dq = 0.f, dr = 0.f;
-                if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && j < ML_TW + 10) {
-                    const float m = v[0][o], mu = v[1][o], qq = v[2][o], tt = v[3][o], rr = v[4][o];
-                    const float sp = qq - m * m, st = tt - mu * mu, spt = rr - m * mu;
-                    const float A2 = 2.f * spt + C2, B2 = sp + st + C2;
-                    // reciprocals as v_rcp_f32 + one Newton step (< 1 ulp), as k_fusion6 forms them
-                    float i2 = __builtin_amdgcn_rcpf(B2);
-                    i2 = i2 * (2.0f - B2 * i2);
-                    if (KIND == MS_SSIM) {
-                        const float A1 = 2.f * m * mu + C1, B1 = m * m + mu * mu + C1;
-                        float i1 = __builtin_amdgcn_rcpf(B1);
-                        i1 = i1 * (2.0f - B1 * i1);
-                        const float inv = i1 * i2;
-                        const float S = A1 * A2 * inv;
-                        dm = 2.f * mu * (A2 - A1) * inv - 2.f * m * S * i1 + 2.f * m * S * i2;
-                        dq = -S * i2;
-                        dr = 2.f * A1 * inv;
-                    } else {
-                        const float cs = A2 * i2;
-                        dm = (2.f * m * cs - 2.f * mu) * i2;
-                        dq = -cs * i2;
-                        dr = 2.f * i2;
-                    }
-                }
-                float *d = Dm + i * ML_DWP + j;
-                d[0] = dm; d[ML_DH * ML_DWP] = dq; d[2 * ML_DH * ML_DWP] = dr;      // X is dead since the barrier above
+                if (vy >= 0 && vy < q.Hv && vx >= 0 && vx < q.Wv && j < ST_TW + 10)
+                    st_deriv<KIND == MS_SSIM>(v[0][o], v[1][o], v[2][o], v[3][o], v[4][o], dm, dq, dr);
+                st_store_deriv(Dm, i, j, dm, dq, dr);
             }
         }
     }
     // this thread's four output pixels (last phase) are requested before the two adjoint passes
-    const int fc = t & (ML_TW - 1), fr4 = (t >> 6) * 4;
+    const int fc = t & (ST_TW - 1), fr4 = (t >> 6) * 4;
     float fp[4], ft[4], gn[4];
     const float kl = GRAD ? q.k[plane] : 0.f;
 #pragma unroll
@@ -200,43 +82,9 @@ __global__ void __launch_bounds__(256) k_msssim_level_bwd(MsBwdP q)
     float am[4] = {0, 0, 0, 0}, aq[4] = {0, 0, 0, 0}, ar[4] = {0, 0, 0, 0};
     if (GRAD) {
         __syncthreads();
-        // ---- adjoint row filter: Hh[m][i][c] = sum_k g[k] D[m][i][c + 10 - k]; item = (row i, 4 columns, map m)
-        for (int idx = t; idx < ML_DH * (ML_TW / 4); idx += 256) {
-            const int r = idx / (ML_TW / 4), c4 = (idx - r * (ML_TW / 4)) * 4;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                float w[16];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float4 vv = *reinterpret_cast<const float4 *>(Dm + (m * ML_DH + r) * ML_DWP + c4 + 4 * k);
-                    w[4 * k] = vv.x; w[4 * k + 1] = vv.y; w[4 * k + 2] = vv.z; w[4 * k + 3] = vv.w;
-                }
-                float hv[4];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss_ms[k], w[o + 10 - k], acc);
-                    hv[o] = acc;
-                }
-                *reinterpret_cast<float4 *>(Hh + (m * ML_DH + r) * ML_TW + c4) = make_float4(hv[0], hv[1], hv[2], hv[3]);
-            }
-        }
+        st_adj_row(Dm, Hh, t);
         __syncthreads();
-        // ---- adjoint column filter: thread = (column fc, 4 rows)
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            float col[14];
-#pragma unroll
-            for (int k = 0; k < 14; ++k) col[k] = Hh[(m * ML_DH + fr4 + k) * ML_TW + fc];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                float acc = 0.f;
-#pragma unroll
-                for (int k = 0; k < 11; ++k) acc = fmaf(c_gauss_ms[k], col[o + 10 - k], acc);
-                if (m == 0) am[o] = acc; else if (m == 1) aq[o] = acc; else ar[o] = acc;
-            }
-        }
+        st_adj_col(Hh, fr4, fc, am, aq, ar);
     }
     float sabs = 0.f, ssq = 0.f;
     const int gx = x0 + fc;
@@ -264,8 +112,8 @@ __global__ void __launch_bounds__(256) k_msssim_level_bwd(MsBwdP q)
     }
 }
 
-// One work-group, one thread per plane (planes <= 64).  The level means and their product exactly as k_msssim_frames_finalize forms
-// them (orn_loss.hip): the tile partials walked in tile order in double, pow in double, the planes summed in plane order.
+// One work-group, one thread per plane (planes <= 64).  The level means and their product as k_msssim_frames_finalize forms them
+// (orn_loss.hip): orn_msssim_level_mean, pow in double, the planes summed in plane order.
 struct MsCoefP {
     const float *part; size_t part_off[5]; int nblk[5]; float nmap[5];
     int planes; float w_scaled;      // w_struct * loss_scale
@@ -275,21 +123,14 @@ struct MsCoefP {
 __global__ void __launch_bounds__(64) k_msssim_coef(MsCoefP q)
 {
     __shared__ double acc[64];
-    const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
     const int pl = threadIdx.x;
     const bool live = pl < q.planes;
     double prod = 1.0, v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0;
     if (live) {
 #pragma unroll
         for (int lv = 0; lv < 5; ++lv) {
-            const float *part = q.part + q.part_off[lv];
-            double ss = 0.0, cs = 0.0;
-            for (int b = 0; b < q.nblk[lv]; ++b) {
-                ss += (double)part[2 * ((size_t)pl * q.nblk[lv] + b)];
-                cs += (double)part[2 * ((size_t)pl * q.nblk[lv] + b) + 1];
-            }
-            const double v = (lv < 4 ? cs : ss) / (double)q.nmap[lv];
-            prod *= pow(v > 0.0 ? v : 0.0, (double)wts[lv]);
+            const double v = orn_msssim_level_mean(q.part + q.part_off[lv], (size_t)pl, q.nblk[lv], q.nmap[lv], lv);
+            prod *= pow(v > 0.0 ? v : 0.0, (double)c_ms_weights[lv]);
             if (lv == 0) v0 = v; else if (lv == 1) v1 = v; else if (lv == 2) v2 = v; else if (lv == 3) v3 = v; else v4 = v;
         }
     }
@@ -304,27 +145,17 @@ __global__ void __launch_bounds__(64) k_msssim_coef(MsCoefP q)
 #pragma unroll
         for (int lv = 0; lv < 5; ++lv) {
             const double v = lv == 0 ? v0 : (lv == 1 ? v1 : (lv == 2 ? v2 : (lv == 3 ? v3 : v4)));
-            const double c = -(double)q.w_scaled * (double)wts[lv] * prod / v / (double)q.planes / (double)q.nmap[lv];
+            const double c = -(double)q.w_scaled * (double)c_ms_weights[lv] * prod / v / (double)q.planes / (double)q.nmap[lv];
             q.k[(size_t)lv * q.planes + pl] = v > 0.0 ? (float)c : 0.f;
         }
     }
 }
 
-// Must be called once outside any graph capture (hipMemcpyToSymbol is synchronous; the kernels use 80 KB of dynamic LDS).
+// Must be called once outside any graph capture (orn_ssim_tile_init).
 int orn_loss_msssim_init()
 {
-    static bool done = false;
-    if (done) return 0;
-    float g[11];
-    orn_gauss_taps(g);
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_gauss_ms), g, sizeof(g));
-    const void *kerns[] = {(const void *)k_msssim_level_bwd<MS_SSIM, false, true>, (const void *)k_msssim_level_bwd<MS_CS, false, true>,
-                           (const void *)k_msssim_level_bwd<MS_CS, true, true>, (const void *)k_msssim_level_bwd<MS_CS, true, false>};
-    for (const void *k : kerns)
-        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, ML_LDS_FLOATS * 4);
-    if (e != hipSuccess) { orn_set_error("loss_msssim: init failed: %s", hipGetErrorString(e)); return (int)e; }
-    done = true;
-    return 0;
+    return orn_ssim_tile_init({(const void *)k_msssim_level_bwd<MS_SSIM, false, true>, (const void *)k_msssim_level_bwd<MS_CS, false, true>,
+                               (const void *)k_msssim_level_bwd<MS_CS, true, true>, (const void *)k_msssim_level_bwd<MS_CS, true, false>});
 }
 
 // floats behind the pyramid of the forward: the gradient planes of levels 1..4, then the coefficients [5][planes] and the value
@@ -360,10 +191,10 @@ static MsBwdP ms_bwd_geom(const float *x, const float *y, const int *frame_idx, 
     q.x = x; q.y = y;
     q.frame_idx = frame_idx; q.frame_stride = frame_stride;
     q.H = H; q.W = W; q.Hv = H - 10; q.Wv = W - 10;
-    q.tiles_w = orn_cdiv(W, ML_TW);
-    q.vec4 = (W % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (frame_stride % 4 == 0 || !frame_idx)) ? 1 : 0;
+    q.tiles_w = orn_cdiv(W, ST_TW);
+    q.vec4 = orn_loss_vec4(W, (uintptr_t)x | (uintptr_t)y, frame_stride, frame_idx) ? 1 : 0;
     if (pool) { q.Ho = orn_msssim_pooled(H); q.Wo = orn_msssim_pooled(W); q.ph = H % 2; q.pw = W % 2; }
-    *grid = dim3(q.tiles_w * orn_cdiv(H, ML_TH), planes);
+    *grid = dim3(q.tiles_w * orn_cdiv(H, ST_TH), planes);
     return q;
 }
 
@@ -371,7 +202,7 @@ static MsBwdP ms_bwd_geom(const float *x, const float *y, const int *frame_idx, 
 static int ms_bwd_launch(int form, const MsBwdP &q, dim3 gr, hipStream_t st)
 {
     const dim3 bl(256);
-    const size_t lds = ML_LDS_FLOATS * 4;
+    const size_t lds = ST_LDS_FLOATS * 4;
     if (form == 0) hipLaunchKernelGGL((k_msssim_level_bwd<MS_SSIM, false, true>), gr, bl, lds, st, q);
     else if (form == 1) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, false, true>), gr, bl, lds, st, q);
     else if (form == 2) hipLaunchKernelGGL((k_msssim_level_bwd<MS_CS, true, true>), gr, bl, lds, st, q);
