@@ -17,8 +17,9 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # operands), which issue slower than the scalar-per-lane instructions they replace on gfx950 (MI355X_MICROARCH.md: 'an anti-lever');
 # measured per kernel in round 3: Fusion6 88 -> 71 us, head backward 85 -> see DESIGN 4.3
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function', '-fvisibility=hidden', '-fno-slp-vectorize']
-# Per-file flags (none at present)
-FILE_FLAGS = {}
+# Per-file flags.  orn_merge_lin.hip: its forward is pinned bit for bit to a tensor expression of separate multiplies and adds, so
+# nothing there may be contracted to an fma (the chains that ARE fma chains call fmaf)
+FILE_FLAGS = {'orn_merge_lin.hip': ['-ffp-contract=off']}
 # the 16-bit fast path is built for bf16 and, with -DORN_FP16, for IEEE half
 BUILT_TWICE = ('orn_conv_bf16.hip', 'orn_conv_fwd_bf16.hip', 'orn_conv2_bf16.hip', 'orn_wgrad_bf16.hip', 'orn_ops_bf16.hip',
                'orn_decode_out.hip')

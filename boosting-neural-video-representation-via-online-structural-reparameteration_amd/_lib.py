@@ -43,6 +43,29 @@ class LayerDesc(ctypes.Structure):
                 ('w1x3', c_int64), ('b1x3', c_int64), ('w1', c_int64), ('w2', c_int64), ('w3', c_int64)]
 
 
+# ORN_BRANCH_* of include/orn.h: the blocks trained through the online merge of orn_merge_lin.hip (ERB has its own path, `erb`)
+BRANCH_KINDS = {'ACB': 2, 'RepVGG': 3, 'ECB': 4}
+ECB_SEQ = ('sbx', 'sby', 'lpl')          # orn_branch_ptrs.sb[t] / orn_branch_desc.sb[t]: rbr_conv1x1_<t>_branch
+SEQ_FIELDS = ('k0', 'b0', 'scale', 'bias', 'mask')
+
+
+class SeqDesc(ctypes.Structure):
+    _fields_ = [(f, c_int64) for f in SEQ_FIELDS]
+
+
+class BranchDesc(ctypes.Structure):
+    _fields_ = [('w1x1', c_int64), ('b1x1', c_int64), ('sb', SeqDesc * 3)]
+
+
+class SeqPtrs(ctypes.Structure):
+    _fields_ = [(f, c_void_p) for f in SEQ_FIELDS]
+
+
+class BranchPtrs(ctypes.Structure):
+    """orn_branch_ptrs: device pointers of a block's parameters, or of where their gradients go."""
+    _fields_ = [(f, c_void_p) for f in ('w3x3', 'b3x3', 'w3x1', 'b3x1', 'w1x3', 'b1x3', 'w1x1', 'b1x1', 'wA', 'wB')] + [('sb', SeqPtrs * 3)]
+
+
 class EngineDesc(ctypes.Structure):
     _fields_ = [('n_layers', c_int32), ('erb', c_int32), ('embed_len', c_int32), ('stem_dim', c_int32),
                 ('fc_h', c_int32), ('fc_w', c_int32), ('fc_dim', c_int32), ('sigmoid', c_int32),
@@ -50,7 +73,9 @@ class EngineDesc(ctypes.Structure):
                 ('beta1', c_double), ('beta2', c_double), ('eps', c_double),
                 ('stem_w0', c_int64), ('stem_b0', c_int64), ('stem_w1', c_int64), ('stem_b1', c_int64),
                 ('head_w', c_int64), ('head_b', c_int64), ('n_params', c_int64),
-                ('layer', LayerDesc * ORN_MAX_LAYERS)]
+                ('layer', LayerDesc * ORN_MAX_LAYERS),
+                # appended (all zero: the engine `erb` describes)
+                ('branch_kind', c_int32), ('reserved_', c_int32), ('branch', BranchDesc * ORN_MAX_LAYERS)]
 
 
 P = c_void_p
@@ -64,6 +89,9 @@ _SIGS = {
     'orn_erb_merge_fwd': (c_int, [P] * 9 + [c_int, c_int, P, P, P, P]),
     'orn_erb_merge_bwd_ws_bytes': (c_size_t, [c_int, c_int]),
     'orn_erb_merge_bwd': (c_int, [P] * 6 + [c_int, c_int] + [P] * 9 + [P, c_size_t, P]),
+    'orn_branch_merge_fwd': (c_int, [c_int, POINTER(BranchPtrs), c_int, c_int, P, P, P]),
+    'orn_branch_merge_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'orn_branch_merge_bwd': (c_int, [c_int, POINTER(BranchPtrs), P, P, c_int, c_int, POINTER(BranchPtrs), P, c_size_t, P]),
     'orn_conv3x3_ps_silu_fwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     'orn_conv3x3_ps_silu_bwd_ws_bytes': (c_size_t, [c_int] * 5),
     'orn_conv3x3_ps_silu_bwd': (c_int, [P, P, P, P] + [c_int] * 6 + [P, P, P, P, c_size_t, P]),

@@ -15,11 +15,22 @@ TRAIN_ERB_SUFFIXES = ('rbr_3x3_branch.weight', 'rbr_3x3_branch.bias', 'rbr_3x1_b
 
 
 def state_dict_kind(sd: Dict[str, torch.Tensor]) -> str:
-    """'deploy' | 'ERB' | 'NeRV_vanilla' from the key layout (read_pth.py documents the same three)."""
+    """'deploy' | 'ERB' | 'ACB' | 'RepVGG' | 'ECB' | 'NeRV_vanilla' from the key layout (read_pth.py documents the first two and the
+    last; the multi-branch kinds all carry rbr_3x3_branch and differ in the tensors beside it, model.py:324-393)."""
     keys = list(sd.keys())
     if any(k.endswith('rbr_reparam.weight') for k in keys):
         return 'deploy'
     if any(k.endswith('rbr_3x3_branch.weight') for k in keys):
+        if any(k.endswith('rbr_1x1_3x3_1x1_branch_3x3.weight') for k in keys):
+            return 'ERB'
+        if any(k.endswith('rbr_conv1x1_sbx_branch.k0') for k in keys):
+            return 'ECB'
+        if any(k.endswith('rbr_1x1_avg_branch_1x1.weight') for k in keys):
+            raise ValueError('a DBB state dict: that block is not built')
+        if any(k.endswith('rbr_1x1_branch.weight') for k in keys):
+            return 'RepVGG'
+        if any(k.endswith('rbr_3x1_branch.weight') for k in keys):
+            return 'ACB'
         return 'ERB'
     if any(k.endswith('.branch.weight') for k in keys):
         return 'NeRV_vanilla'
@@ -46,7 +57,7 @@ def deploy_state_dict(model) -> Dict[str, torch.Tensor]:
         blk = model.layers[i]
         if getattr(blk, 'deploy', False):
             w, b = blk.rbr_reparam.weight, blk.rbr_reparam.bias
-        elif blk.branch_type == 'ERB':
+        elif blk.branch_type != 'NeRV_vanilla':         # ERB, ACB, RepVGG, ECB: the online merge
             with torch.no_grad():
                 w, b = blk.get_equivalent_kernel_bias()
         else:

@@ -12,6 +12,7 @@ struct LayerBuf {
     float *T, *wf, *bf;   // merge products (ERB) -- wf/bf alias the params for vanilla/deploy
     float *w2t;           // tap-major copy of W2 (ERB): the T products read contiguous rows
     float *dT, *dw1p;     // merge backward scratch (ERB)
+    float *dwap;          // merge backward scratch of an ECB block: the slabs of dwA (orn_merge_lin.hip)
     float *wd32;          // fp32 layers: flipped / transposed merged kernel for the dgrad (made for all layers in one launch)
     void *mh16;           // half operand copies of the merge backward (16-bit modes, orn_merge_h16.hip)
     float *dw2t;          // dW2 tap-major [9][O][2C] (16-bit modes)
@@ -55,6 +56,10 @@ struct orn_engine {
         int tiles[4];                   // work-groups of each table's launch, as orn_merge_groups_build counted them
         void *mh_tables, *mh_host;      // 16-bit modes: tables of the packed-operand merge backward (device / host)
     } mset[3];
+    // (ACB / RepVGG / ECB, d.branch_kind) the blocks as the launchers of orn_merge_lin.hip see them: such a block is a single-conv block
+    // whose (wf, bf) live in the workspace, merged by one launch in front of the forward and sent back by one behind the weight gradients
+    int nbr;                         // 0: not such an engine
+    OrnBranchLayer bl[ORN_MAX_LAYERS];
     int ff;                          // first layer on the bf16 fast path (== n_layers: none)
     float *dxn;                      // fp32 NHWC dgrad output of layer ff (converted to NCHW for the fp32 part)
     size_t stem_ws;                  // floats of `scratch` the stem backward uses (the fused first block's dx slabs sit behind them)
@@ -157,6 +162,8 @@ static int check_desc(const orn_engine_desc *d)
     ORN_REQUIRE(d, "engine: null desc");
     ORN_REQUIRE(d->n_layers >= 1 && d->n_layers <= ORN_MAX_LAYERS, "engine: n_layers=%d out of range", d->n_layers);
     ORN_REQUIRE(d->precision >= 0 && d->precision <= 2, "engine: precision %d not built", d->precision);
+    ORN_REQUIRE(d->branch_kind == 0 || ((d->branch_kind == ORN_BRANCH_ACB || d->branch_kind == ORN_BRANCH_REPVGG || d->branch_kind == ORN_BRANCH_ECB) && !d->erb),
+                "engine: branch_kind %d (with erb = %d) is not 0 or ORN_BRANCH_ACB / _REPVGG / _ECB with erb = 0", d->branch_kind, d->erb);
     ORN_REQUIRE(d->embed_len > 0 && d->stem_dim > 0 && d->fc_h > 0 && d->fc_w > 0 && d->fc_dim > 0, "engine: bad stem geometry");
     int C = d->fc_dim, H = d->fc_h, W = d->fc_w;
     for (int i = 0; i < d->n_layers; ++i) {
@@ -168,6 +175,17 @@ static int check_desc(const orn_engine_desc *d)
         if (d->erb)
             ORN_REQUIRE(l.w3x1 >= 0 && l.b3x1 >= 0 && l.w1x3 >= 0 && l.b1x3 >= 0 && l.w1 >= 0 && l.w2 >= 0 && l.w3 >= 0,
                         "engine: layer %d: missing ERB branch tensors", i);
+        const orn_branch_desc &x = d->branch[i];
+        if (d->branch_kind == ORN_BRANCH_ACB)
+            ORN_REQUIRE(l.w3x1 >= 0 && l.b3x1 >= 0 && l.w1x3 >= 0 && l.b1x3 >= 0, "engine: layer %d: missing ACB branch tensors", i);
+        if (d->branch_kind == ORN_BRANCH_REPVGG)
+            ORN_REQUIRE(x.w1x1 >= 0 && x.b1x1 >= 0, "engine: layer %d: missing RepVGG branch tensors", i);
+        if (d->branch_kind == ORN_BRANCH_ECB) {
+            ORN_REQUIRE(l.w1 >= 0 && l.w2 >= 0, "engine: layer %d: missing ECB branch tensors (w1 = wA, w2 = wB)", i);
+            for (int t = 0; t < 3; ++t)
+                ORN_REQUIRE(x.sb[t].k0 >= 0 && x.sb[t].b0 >= 0 && x.sb[t].scale >= 0 && x.sb[t].bias >= 0 && x.sb[t].mask >= 0,
+                            "engine: layer %d: missing ECB branch tensors (1x1 -> mask branch %d)", i, t);
+        }
         C = l.O / (l.s * l.s); H *= l.s; W *= l.s;
     }
     ORN_REQUIRE(d->n_params > 0 && d->n_params % 4 == 0, "engine: n_params must be a positive multiple of 4");
@@ -227,6 +245,10 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
                 L[i].mh16 = take((orn_merge_h16_layer_halfs(l.C, l.O) + 1) / 2);
                 L[i].dw2t = take((size_t)9 * l.O * 2 * l.C);
             }
+        }
+        if (d->branch_kind) {
+            L[i].wf = take(wsz); L[i].bf = take(l.O);
+            L[i].dwap = take(orn_branch_merge_bwd_ws_floats(d->branch_kind, l.C, l.O));
         }
         Cn = l.O / (l.s * l.s); H = l.H * l.s; W = l.W * l.s;
         const size_t asz = (size_t)Cn * H * W;
@@ -328,6 +350,7 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     e->side = nullptr;
     for (auto ev : SIDE_EVENTS) e->*ev = nullptr;
     e->pipe_ok = false; e->side_busy = false; e->side_lo = 0;
+    e->nbr = 0;
     for (int i = 0; i < 4 * ORN_MAX_LAYERS + 4; ++i) e->prof_ev[i] = nullptr;
     e->ops = (d->precision == 2) ? orn_half_ops_f16() : orn_half_ops_bf16();
     e->gs = (d->precision == 2) ? 1048576.0f : 1.0f;
@@ -368,7 +391,7 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     {
         const int nl = d->n_layers;
         const orn_layer_desc &ll = d->layer[nl - 1];
-        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v;
+        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v && !d->branch_kind;     // (no pipelined form of the ACB / RepVGG / ECB merge)
         if (ok) {
             const int64_t lo_all[9] = {ll.w3x3, ll.b3x3, ll.w3x1, ll.b3x1, ll.w1x3, ll.b1x3, ll.w1, ll.w2, ll.w3};
             int64_t lo = d->n_params;
@@ -409,7 +432,39 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
         e->side_below = ok && nl - 2 > e->ff;
         e->fork_behind_dgrad = e->side_below;
     }
-    if (!d->erb)
+    if (d->branch_kind) {
+        // the arena offsets of a block as pointers into `base`: the parameters, or (grads) where their gradients go
+        auto ptrs = [&](int i, float *base) {
+            const orn_layer_desc &l = d->layer[i];
+            const orn_branch_desc &x = d->branch[i];
+            orn_branch_ptrs p = {};
+            p.w3x3 = base + l.w3x3; p.b3x3 = base + l.b3x3;
+            if (d->branch_kind == ORN_BRANCH_ACB) { p.w3x1 = base + l.w3x1; p.b3x1 = base + l.b3x1; p.w1x3 = base + l.w1x3; p.b1x3 = base + l.b1x3; }
+            if (d->branch_kind == ORN_BRANCH_REPVGG) { p.w1x1 = base + x.w1x1; p.b1x1 = base + x.b1x1; }
+            if (d->branch_kind == ORN_BRANCH_ECB) {
+                p.wA = base + l.w1; p.wB = base + l.w2;
+                for (int t = 0; t < 3; ++t) {
+                    p.sb[t].k0 = base + x.sb[t].k0; p.sb[t].b0 = base + x.sb[t].b0; p.sb[t].scale = base + x.sb[t].scale;
+                    p.sb[t].bias = base + x.sb[t].bias; p.sb[t].mask = base + x.sb[t].mask;
+                }
+            }
+            return p;
+        };
+        for (int i = 0; i < d->n_layers; ++i) {
+            OrnBranchLayer &b = e->bl[i];
+            b = OrnBranchLayer{};
+            b.kind = d->branch_kind; b.C = d->layer[i].C; b.O = d->layer[i].O;
+            b.p = ptrs(i, params);
+            b.wf = e->L[i].wf; b.bf = e->L[i].bf;
+            if (grads) {        // dWf / dbf land in the 3x3 branch's gradient slots: d3x3 = g, db3x3 = dbf without a copy
+                b.d = ptrs(i, grads);
+                b.g = b.d.w3x3; b.dbf = b.d.b3x3;
+            }
+            b.dwAp = e->L[i].dwap;
+            e->L[i].T = nullptr;
+        }
+        e->nbr = d->n_layers;
+    } else if (!d->erb)
         for (int i = 0; i < d->n_layers; ++i) {
             e->L[i].T = nullptr;
             e->L[i].wf = params + d->layer[i].w3x3;
@@ -699,6 +754,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
         ORN_TRY(orn_launch_linear_silu(lin1.x, lin1.row_idx, lin1.row_stride, lin1.w, lin1.bias, 1, lin1.K, lin1.N, lin1.pre, lin1.y, st));
         ORN_TRY(orn_launch_linear_silu(lin2.x, nullptr, 0, lin2.w, lin2.bias, 1, lin2.K, lin2.N, lin2.pre, lin2.y, st));
     }
+    if (e->nbr && merge) ORN_TRY(orn_launch_branch_merge_fwd(e->nbr, e->bl, st));      // ACB / RepVGG / ECB: (wf, bf) of every block, one launch
     if (ff < nl && !d.erb && merge) {      // 16-bit operand copies of every fast layer's kernel, one launch (ERB: written by the merge's S launch)
         OrnPrepLayer pl[ORN_MAX_LAYERS];
         const int np = (set == 1 ? nl - 1 : nl) - ff;       // (pipelined step: the side branch prepares the last block's)
@@ -1074,6 +1130,7 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
         if (stats_out) ORN_TRY(orn_launch_batch_stats(e->b_stats, o.batch, cur, stats_out, st));
     }
     if (d.erb) ORN_TRY(merge_backward(e, e->mset[pipe ? 1 : 0], st, sc));
+    if (e->nbr) ORN_TRY(orn_launch_branch_merge_bwd(e->nbr, e->bl, st));     // ACB / RepVGG / ECB: dWf / dbf (3x3 slots) -> the other branches' slots
     if (pipe) {
         // this stream's Adam launch covers everything below the last block; its skip decision is mirrored for the side branch's launch
         // (into sc_side->mirrored: a word of its own, apart from the flag the side branch's detectors raise meanwhile)

@@ -97,6 +97,19 @@ struct OrnMergeMisc {
 };
 int orn_launch_merge_bwd_tail_all(int n, const OrnMergeMisc *L, hipStream_t st);
 
+// orn_merge_lin.hip: online merge of the ACB / RepVGG / ECB blocks (include/orn.h, N7), all blocks of an engine per launch
+struct OrnBranchLayer {
+    int kind, C, O;                   // ORN_BRANCH_*
+    orn_branch_ptrs p;                // parameters (read only)
+    float *wf, *bf;                   // forward: the merged kernel and bias
+    const float *g, *dbf;             // backward: dL/dwf, dL/dbf ...
+    orn_branch_ptrs d;                // ... and where each gradient goes (d.w3x3 == g, d.b3x3 == dbf: no copy)
+    float *dwAp;                      // ECB: orn_branch_merge_bwd_ws_floats floats, the slabs of dwA
+};
+size_t orn_branch_merge_bwd_ws_floats(int kind, int C, int O);
+int orn_launch_branch_merge_fwd(int n, const OrnBranchLayer *L, hipStream_t st);
+int orn_launch_branch_merge_bwd(int n, const OrnBranchLayer *L, hipStream_t st);    // ECB: two launches (the slabs of dwA are summed by the second)
+
 // orn_conv_f32.hip
 int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, int B, int C, int O, int H, int W,
                            int s, int epi, float *z, float *out, hipStream_t st, float *split_ws);

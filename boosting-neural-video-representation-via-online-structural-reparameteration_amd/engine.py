@@ -28,6 +28,15 @@ _ERB_FIELDS = {
     'rbr_1x1_3x3_1x1_branch_1x1_1.weight': 'w1', 'rbr_1x1_3x3_1x1_branch_3x3.weight': 'w2',
     'rbr_1x1_3x3_1x1_branch_1x1_2.weight': 'w3',
 }
+# ACB / RepVGG / ECB (orn_engine_desc.branch_kind): fields of orn_layer_desc where it has one (ACB's as ERB's; ECB's wA / wB in
+# w1 / w2), else of orn_branch_desc ('x.' prefix)
+_BRANCH_FIELDS = {
+    'ACB': {k: f for k, f in _ERB_FIELDS.items() if f in ('w3x3', 'b3x3', 'w3x1', 'b3x1', 'w1x3', 'b1x3')},
+    'RepVGG': {'rbr_3x3_branch.weight': 'w3x3', 'rbr_3x3_branch.bias': 'b3x3', 'rbr_1x1_branch.weight': 'x.w1x1', 'rbr_1x1_branch.bias': 'x.b1x1'},
+    'ECB': {'rbr_3x3_branch.weight': 'w3x3', 'rbr_3x3_branch.bias': 'b3x3',
+            'rbr_1x1_3x3_branch_1x1.weight': 'w1', 'rbr_1x1_3x3_branch_3x3.weight': 'w2',
+            **{f'rbr_conv1x1_{seq}_branch.{f}': f'x.sb.{t}.{f}' for t, seq in enumerate(_lib.ECB_SEQ) for f in _lib.SEQ_FIELDS}},
+}
 _SINGLE_FIELDS = {'branch.weight': 'w3x3', 'branch.bias': 'b3x3', 'rbr_reparam.weight': 'w3x3', 'rbr_reparam.bias': 'b3x3'}
 
 
@@ -50,7 +59,8 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
         raise OrnError(f'{n_layers} layers > ORN_MAX_LAYERS')
     blk0 = model.layers[0]
     erb = (not blk0.deploy) and blk0.branch_type == 'ERB'
-    d.n_layers, d.erb = n_layers, int(erb)
+    kind = None if blk0.deploy else _lib.BRANCH_KINDS.get(blk0.branch_type)
+    d.n_layers, d.erb, d.branch_kind = n_layers, int(erb), kind or 0
     d.embed_len, d.stem_dim = model.stem[0].in_features, model.stem[0].out_features
     d.fc_h, d.fc_w, d.fc_dim = model.fc_h, model.fc_w, model.fc_dim
     d.sigmoid = int(bool(model.sigmoid))
@@ -67,10 +77,22 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
         L.C, L.O, L.s, L.H, L.W = blk.ngf, blk.out_channels, blk.stride, H, W
         for f in ('w3x3', 'b3x3', 'w3x1', 'b3x1', 'w1x3', 'b1x3', 'w1', 'w2', 'w3'):
             setattr(L, f, -1)
-        fields = _ERB_FIELDS if erb else _SINGLE_FIELDS
+        X = d.branch[i]
+        if kind:                                            # (another kind's descriptor leaves these zero and unread)
+            X.w1x1 = X.b1x1 = -1
+            for t in range(3):
+                for f in _lib.SEQ_FIELDS:
+                    setattr(X.sb[t], f, -1)
+        fields = _ERB_FIELDS if erb else _BRANCH_FIELDS[blk0.branch_type] if kind else _SINGLE_FIELDS
         for key, f in fields.items():
             name = f'layers.{i}.{key}'
-            if name in layout:
+            if name not in layout:
+                continue
+            if f.startswith('x.sb.'):
+                setattr(X.sb[int(f.split('.')[2])], f.split('.')[3], layout[name][0])
+            elif f.startswith('x.'):
+                setattr(X, f[2:], layout[name][0])
+            else:
                 setattr(L, f, layout[name][0])
         H, W = H * blk.stride, W * blk.stride
     return d
@@ -523,7 +545,7 @@ class TrainEngine(_Decoding):
         return self.stats_ring[:n].cpu()
 
     def engine_fused_kernel(self, layer: int):
-        """(Wf, bf) of block `layer` exactly as the ENGINE's last merge left them in its workspace (copies; ERB only)."""
+        """(Wf, bf) of block `layer` exactly as the ENGINE's last merge left them in its workspace (copies; ERB, ACB, RepVGG, ECB)."""
         wf, bf = c_void_p(), c_void_p()
         check(lib().orn_engine_fused_kernel(self._h, layer, byref(wf), byref(bf)), 'orn_engine_fused_kernel')
         shape = tuple(dict(self.model.named_parameters())[f'layers.{layer}.rbr_3x3_branch.weight'].shape)
@@ -540,7 +562,7 @@ class TrainEngine(_Decoding):
     def fused_kernel(self, layer: int):
         """(Wf, bf) of block `layer` as produced by the last merge (model.py:450-478), as tensors."""
         blk = self.model.layers[layer]
-        if self.desc.erb:
+        if self.desc.erb or self.desc.branch_kind:
             with torch.no_grad():
                 return blk.get_equivalent_kernel_bias()
         conv = blk.rbr_reparam if blk.deploy else blk.branch

@@ -150,7 +150,11 @@ def main(argv=None):
     deploy_file = os.path.join(outf, 'model_latest_deploy.pth')
     train_file = os.path.join(outf, 'model_latest.pth')
     finetune = args.finetune and args.prune_ratio < 1
-    path = deploy_file if (args.branch_type == 'ERB' and os.path.exists(deploy_file) and not finetune) else train_file
+    from .main_train import MERGED_BRANCHES
+    if args.finetune and args.branch_type in MERGED_BRANCHES and args.branch_type != 'ERB':
+        # the reference's fine-tune prunes nothing of these blocks (main_eval.py:244-340 knows `branch` and ERB's attributes only)
+        raise ValueError(f'--finetune with --branch_type {args.branch_type}: the prune fine-tune is built for NeRV_vanilla and ERB only')
+    path = deploy_file if (args.branch_type in MERGED_BRANCHES and os.path.exists(deploy_file) and not finetune) else train_file
     if not os.path.exists(path):
         raise FileNotFoundError(path)
     sd = checkpoint.load_state_dict_file(path)
@@ -167,7 +171,7 @@ def main(argv=None):
         masks, originals = _prune_finetune(model, args, PE, path, vid_index) if vid_index else _prune_finetune(model, args, PE, path)
     if kind != 'deploy':
         for blk in model.layers:
-            blk.switch_to_deploy() if blk.branch_type == 'ERB' else None
+            blk.switch_to_deploy() if blk.branch_type in MERGED_BRANCHES else None
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     n_param = sum(v.numel() for v in sd.values())
     if args.prune_ratio < 1 and not finetune:

@@ -162,8 +162,12 @@ class Best:
         self.val_msssim = torch.tensor(0.0)
 
 
+# the blocks trained through an online merge: their checkpoints get a `_deploy` copy with every block merged to one conv
+MERGED_BRANCHES = ('ERB', 'ACB', 'RepVGG', 'ECB')
+
+
 def save_checkpoint(args, model, eng, epoch, best, name='model_latest.pth', deploy_too=None, applied=None):
-    """main_train.py:293-301,327 layout; ERB also writes the deploy copy (main_train.py:325-351).  `best`: a Best, or a
+    """main_train.py:293-301,327 layout; the merged kinds (ERB, ACB, RepVGG, ECB) also write the deploy copy (main_train.py:325-351).  `best`: a Best, or a
     number (train PSNR; kept for callers that only track that)."""
     from . import checkpoint
     if not isinstance(best, Best):
@@ -174,7 +178,7 @@ def save_checkpoint(args, model, eng, epoch, best, name='model_latest.pth', depl
     kw = dict(train_best_psnr=best.train_psnr, val_best_psnr=best.val_psnr, train_best_msssim=best.train_msssim,
               val_best_msssim=best.val_msssim)
     checkpoint.save(os.path.join(args.outf, name), model, epoch + 1, opt, **kw)
-    if args.branch_type == 'ERB' if deploy_too is None else deploy_too:
+    if args.branch_type in MERGED_BRANCHES if deploy_too is None else deploy_too:
         checkpoint.save(os.path.join(args.outf, name.replace('.pth', '_deploy.pth')), model, epoch + 1, opt, deploy=True, **kw)
 
 
@@ -473,7 +477,7 @@ def fit_video(args, name, vid_index, rank, _inject=None):
                 best_dirty = False
         epoch += 1
     torch.cuda.synchronize()
-    if args.branch_type == 'ERB':                                        # main_train.py:361-367
+    if args.branch_type in MERGED_BRANCHES:                              # main_train.py:361-367
         from . import checkpoint
         say(f'Deploy Rep-Model Params: {checkpoint.deploy_param_count(model) / 1e6:.3f}M')
     sc = eng.scale_state()

@@ -113,6 +113,85 @@ class ErbMergeFn(torch.autograd.Function):
         return d3x3, db3x3, d3x1, db3x1, d1x3, db1x3, dw1, dw2, dw3
 
 
+# ---- N7 ------------------------------------------------------------------------------------
+# Tensor order of a block of each kind, as BranchMergeFn / branch_merge_fwd / branch_merge_bwd take and return them: the fields
+# of orn_branch_ptrs (include/orn.h), ECB's three 1x1 -> mask branches in the order sbx, sby, lpl.
+BRANCH_TENSORS = {
+    'ACB': ('w3x3', 'b3x3', 'w3x1', 'b3x1', 'w1x3', 'b1x3'),
+    'RepVGG': ('w3x3', 'b3x3', 'w1x1', 'b1x1'),
+    'ECB': ('w3x3', 'b3x3', 'wA', 'wB') + tuple(f'{t}.{f}' for t in _lib.ECB_SEQ for f in _lib.SEQ_FIELDS),
+}
+
+
+def branch_shapes(kind: str, C: int, O: int):
+    """Shapes of BRANCH_TENSORS[kind] for a block C -> O (model.py:345-393)."""
+    sh = {'w3x3': (O, C, 3, 3), 'b3x3': (O,), 'w3x1': (O, C, 3, 1), 'b3x1': (O,), 'w1x3': (O, C, 1, 3), 'b1x3': (O,),
+          'w1x1': (O, C, 1, 1), 'b1x1': (O,), 'wA': (2 * C, C, 1, 1), 'wB': (O, 2 * C, 3, 3),
+          'k0': (O, C, 1, 1), 'b0': (O,), 'scale': (O, 1, 1, 1), 'bias': (O,), 'mask': (O, 1, 3, 3)}
+    return [sh[n.split('.')[-1]] for n in BRANCH_TENSORS[kind]]
+
+
+def _branch_ptrs(kind: str, tensors) -> '_lib.BranchPtrs':
+    names = BRANCH_TENSORS[kind]
+    if len(tensors) != len(names):
+        raise _lib.OrnError(f'{kind}: {len(tensors)} tensors for {names}')
+    p = _lib.BranchPtrs()
+    for n, t in zip(names, tensors):
+        if '.' in n:
+            seq, f = n.split('.')
+            setattr(p.sb[_lib.ECB_SEQ.index(seq)], f, t.data_ptr())
+        else:
+            setattr(p, n, t.data_ptr())
+    return p
+
+
+def branch_merge_fwd(kind: str, tensors, out=None):
+    """(Wf [O,C,3,3], bf [O]) of an ACB / RepVGG / ECB block (orn_branch_merge_fwd).  tensors: BRANCH_TENSORS[kind], fp32 on the
+    GPU.  out: (wf, bf) to fill in place of new tensors."""
+    ts = [_f32c(t) for t in tensors]
+    O, C = ts[0].shape[0], ts[0].shape[1]
+    wf, bf = out if out is not None else (torch.empty(O, C, 3, 3, device=ts[0].device), torch.empty(O, device=ts[0].device))
+    p = _branch_ptrs(kind, ts)
+    check(lib().orn_branch_merge_fwd(_lib.BRANCH_KINDS[kind], p, C, O, ptr(wf), ptr(bf), stream()), 'orn_branch_merge_fwd')
+    return wf, bf
+
+
+def branch_merge_bwd(kind: str, tensors, g, dbf, grads=None):
+    """Gradients of BRANCH_TENSORS[kind] from g = dL/dWf and dbf = dL/dbf (orn_branch_merge_bwd), in that order; ECB's b0 and mask
+    get zeros.  grads: preallocated outputs (grads[0] may be g and grads[1] dbf: no copy then)."""
+    ts = [_f32c(t) for t in tensors]
+    g, dbf = _f32c(g), _f32c(dbf)
+    O, C = ts[0].shape[0], ts[0].shape[1]
+    if grads is None:
+        grads = [torch.empty_like(t) for t in ts]
+    nb = lib().orn_branch_merge_bwd_ws_bytes(_lib.BRANCH_KINDS[kind], C, O)
+    ws = _ws(nb, g.device)
+    p, d = _branch_ptrs(kind, ts), _branch_ptrs(kind, grads)
+    check(lib().orn_branch_merge_bwd(_lib.BRANCH_KINDS[kind], p, ptr(g), ptr(dbf), C, O, d, ptr(ws), c_size_t(ws.numel()), stream()),
+          'orn_branch_merge_bwd')
+    return grads
+
+
+class BranchMergeFn(torch.autograd.Function):
+    """get_equivalent_kernel_bias of an ACB / RepVGG / ECB block: BranchMergeFn.apply(kind, *BRANCH_TENSORS[kind]) -> (Wf, bf).
+    The reference has no merge for these kinds (its switch_to_deploy knows ERB's attributes only); include/orn.h, N7, defines it."""
+
+    @staticmethod
+    def forward(ctx, kind, *tensors):
+        ts = [_f32c(t) for t in tensors]
+        ctx.kind = kind
+        ctx.save_for_backward(*ts)
+        return branch_merge_fwd(kind, ts)
+
+    @staticmethod
+    def backward(ctx, g, dbf):
+        ts = ctx.saved_tensors
+        O, C = ts[0].shape[0], ts[0].shape[1]
+        g = g if g is not None else torch.zeros(O, C, 3, 3, device=ts[0].device)
+        dbf = dbf if dbf is not None else torch.zeros(O, device=ts[0].device)
+        return (None, *branch_merge_bwd(ctx.kind, ts, g, dbf))
+
+
 # ---- A4 ------------------------------------------------------------------------------------
 class ConvPsSiluFn(torch.autograd.Function):
     """conv3x3(pad 1) + bias -> PixelShuffle(s) -> SiLU (model.py:539,567)."""

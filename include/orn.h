@@ -38,7 +38,9 @@ extern "C" {
                                   * + orn_msssim_frames*, orn_engine_eval_frames*; + ORN_LOSS_SSIM .. ORN_LOSS_FUSION12, orn_loss_spec,
                                   * orn_loss_ws_bytes_for; + ORN_MAX_BATCH, orn_engine_batch_ws_bytes, orn_engine_set_batch_ws,
                                   * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step);
-                                  * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size); + orn_stem_bwd_ws_bytes */
+                                  * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size); + orn_stem_bwd_ws_bytes;
+                                  * + ORN_BRANCH_ACB / _REPVGG / _ECB, orn_branch_ptrs, orn_branch_merge_fwd / _bwd_ws_bytes / _bwd, and, appended
+                                  * to orn_engine_desc, branch_kind + branch[] (N7: the paper's comparison blocks through an online merge) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -83,6 +85,40 @@ ORN_API int orn_erb_merge_bwd(const float *g, const float *dbf, const float *w1,
                       const float *T, int C, int O, float *d3x3, float *db3x3, float *d3x1, float *db3x1,
                       float *d1x3, float *db1x3, float *dw1, float *dw2, float *dw3, void *ws,
                       size_t ws_bytes, void *stream);
+
+/* ---- N7  ACB / RepVGG / ECB blocks trained through an online merge    model.py:345-393, 541-565 ----
+ * The reference trains these blocks as three to five convolutions summed on the activations.  Each is linear in its weights, so it
+ * is trained here the way ERB is: merged to one 3x3 kernel every step (wf [O,C,3,3], bf [O]), which feeds the one conv of the block,
+ * and dL/dwf is sent back through the merge.  Taps are (kh, kw) in 0..2, k = 3*kh + kw, centre k = 4.  All arithmetic is fp32.
+ *   ACB     wf = (w3x3 + pad_h(w1x3)) + pad_w(w3x1);  bf = (b3x3 + b1x3) + b3x1
+ *   RepVGG  wf = w3x3, plus w1x1 at the centre tap;   bf = b3x3 + b1x1
+ *   ECB     wf = w3x3 + T + sum_t (scale_t * mask_t) * k0_t, terms added in the order written, t = sbx, sby, lpl;
+ *           T[o,c,k] = sum_m wB[o,m,k] * wA[m,c], one m-ordered fmaf chain from 0;  bf = ((b3x3 + bias_sbx) + bias_sby) + bias_lpl.
+ *           b0_t enters bf with the factor sum_k scale_t * mask_t[k], which is exactly 0 in fp32 for the Sobel and Laplacian masks: it
+ *           is left out.  mask_t is read from memory like any other tensor (a state-dict tensor that is never trained).
+ * Backward, g = dL/dwf, dbf = dL/dbf (fixed-order sums, no atomics, run-to-run bit-identical):
+ *   d3x3 = g, every branch bias gets dbf;  ACB: d3x1[o,c,kh] = g[o,c,kh,1], d1x3[o,c,kw] = g[o,c,1,kw];  RepVGG: d1x1[o,c] = g[o,c,1,1];
+ *   ECB: dwB[o,m,k] = sum_c g[o,c,k] * wA[m,c];  dwA[m,c] = sum_{o,k} wB[o,m,k] * g[o,c,k] (partial sums over slabs of 32 output
+ *        channels, then the slabs in order);  with q_t[o,c] = sum_k mask_t[o,k] * g[o,c,k]:  dk0_t = scale_t * q_t,
+ *        dscale_t[o] = sum_c k0_t[o,c] * q_t[o,c], dbias_t = dbf;  db0_t = 0 and dmask_t = 0 are WRITTEN, so that an optimiser over
+ *        the whole arena never reads a stale value.
+ * orn_branch_ptrs holds device pointers: the parameters (forward; backward reads wA, wB, k0, scale, mask) or, as the `grads`
+ * argument of the backward, where each gradient goes (tensors of the same shapes).  Only the members of the given kind are read.
+ * grads->w3x3 == g and grads->b3x3 == dbf are allowed (no copy then: the engine's dwf already lies in the 3x3 branch's slot). */
+#define ORN_BRANCH_ACB 2
+#define ORN_BRANCH_REPVGG 3
+#define ORN_BRANCH_ECB 4
+typedef struct orn_branch_ptrs {
+    float *w3x3, *b3x3;                 /* [O,C,3,3], [O]: every kind */
+    float *w3x1, *b3x1, *w1x3, *b1x3;   /* ACB: [O,C,3,1], [O], [O,C,1,3], [O] */
+    float *w1x1, *b1x1;                 /* RepVGG: [O,C,1,1], [O] */
+    float *wA, *wB;                     /* ECB: rbr_1x1_3x3_branch_1x1 [2C,C,1,1], rbr_1x1_3x3_branch_3x3 [O,2C,3,3] */
+    struct { float *k0, *b0, *scale, *bias, *mask; } sb[3];   /* ECB: rbr_conv1x1_{sbx,sby,lpl}_branch: [O,C,1,1], [O], [O,1,1,1], [O], [O,1,3,3] */
+} orn_branch_ptrs;
+ORN_API int orn_branch_merge_fwd(int kind, const orn_branch_ptrs *p, int C, int O, float *wf, float *bf, void *stream);
+ORN_API size_t orn_branch_merge_bwd_ws_bytes(int kind, int C, int O);       /* 0 on bad arguments (and 256 for the kinds that need none) */
+ORN_API int orn_branch_merge_bwd(int kind, const orn_branch_ptrs *p, const float *g, const float *dbf, int C, int O,
+                                 const orn_branch_ptrs *grads, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- A4  NeRVBlock.forward: conv3x3(pad 1)+bias -> PixelShuffle(s) -> SiLU   model.py:539,567 --
  * x [B,C,H,W]; wf [O,C,3,3]; bf [O]; O = Cn*s*s.  z (pre-activation, post-shuffle) and
@@ -256,6 +292,13 @@ typedef struct orn_layer_desc {
     int64_t w1, w2, w3;             /* ERB only: 1x1 -> 3x3 -> 1x1 */
 } orn_layer_desc;
 
+/* The offsets of a block of a kind of N7 that orn_layer_desc has no field for (same units; read only for that kind).  ACB uses
+ * w3x1 / b3x1 / w1x3 / b1x3 of orn_layer_desc; ECB uses w1 / w2 for wA / wB, with w3 = -1. */
+typedef struct orn_branch_desc {
+    int64_t w1x1, b1x1;             /* RepVGG */
+    struct { int64_t k0, b0, scale, bias, mask; } sb[3];    /* ECB: sbx, sby, lpl */
+} orn_branch_desc;
+
 typedef struct orn_engine_desc {
     int32_t n_layers;
     int32_t erb;                    /* 1: ERB online merge; 0: single 3x3 conv per block */
@@ -267,6 +310,12 @@ typedef struct orn_engine_desc {
     int64_t stem_w0, stem_b0, stem_w1, stem_b1, head_w, head_b;
     int64_t n_params;               /* arena length in floats */
     orn_layer_desc layer[ORN_MAX_LAYERS];
+    /* appended (N7); all zero = the engine that `erb` describes */
+    int32_t branch_kind;            /* 0: as `erb` says; ORN_BRANCH_ACB / _REPVGG / _ECB (with erb = 0): every block is of that kind -- a
+                                     * single-conv block whose (wf, bf) are merged into the workspace every step, as ERB's are.  Serial
+                                     * step, graph replay, batched and split step, decode; no pipelined form */
+    int32_t reserved_;
+    orn_branch_desc branch[ORN_MAX_LAYERS];
 } orn_engine_desc;
 
 /* One entry of the per-step schedule (device array, uploaded per epoch by the caller). */
@@ -430,7 +479,7 @@ ORN_API int orn_engine_train_steps_batch(orn_engine *e, const float *frames, con
 ORN_API int orn_engine_scale_state(orn_engine *e, float *out8);
 /* Overrides the live scale (>= 1) and, if gs_max > 0, its ceiling: tests inject an overflowing step this way. */
 ORN_API int orn_engine_set_grad_scale(orn_engine *e, float gs, float gs_max);
-/* Merged (deploy) kernel/bias of layer i, valid after a decode / train step (model.py:395-448). */
+/* Merged (deploy) kernel/bias of layer i, valid after a decode / train step (model.py:395-448; ERB and the kinds of N7). */
 ORN_API int orn_engine_fused_kernel(orn_engine *e, int layer, const float **wf, const float **bf);
 
 #ifdef __cplusplus
