@@ -22,7 +22,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-u
 FILE_FLAGS = {'orn_merge_lin.hip': ['-ffp-contract=off']}
 # the 16-bit fast path is built for bf16 and, with -DORN_FP16, for IEEE half
 BUILT_TWICE = ('orn_conv_bf16.hip', 'orn_conv_fwd_bf16.hip', 'orn_conv2_bf16.hip', 'orn_wgrad_bf16.hip', 'orn_ops_bf16.hip',
-               'orn_decode_out.hip')
+               'orn_decode_out.hip', 'orn_side_head.hip')
 
 
 def _sources():

@@ -75,7 +75,9 @@ class EngineDesc(ctypes.Structure):
                 ('head_w', c_int64), ('head_b', c_int64), ('n_params', c_int64),
                 ('layer', LayerDesc * ORN_MAX_LAYERS),
                 # appended (all zero: the engine `erb` describes)
-                ('branch_kind', c_int32), ('reserved_', c_int32), ('branch', BranchDesc * ORN_MAX_LAYERS)]
+                ('branch_kind', c_int32), ('reserved_', c_int32), ('branch', BranchDesc * ORN_MAX_LAYERS),
+                # appended (multi-resolution heads; all zero: a single-resolution engine)
+                ('multi_res', c_int32), ('lw', c_float), ('side_head_w', c_int64 * ORN_MAX_LAYERS), ('side_head_b', c_int64 * ORN_MAX_LAYERS)]
 
 
 P = c_void_p
@@ -141,6 +143,9 @@ _SIGS = {
     'orn_engine_profile_step': (c_int, [P, P, P, P, P, P, c_int32, P, P]),
     'orn_engine_set_grad_mask': (c_int, [P, P]),
     'orn_engine_set_target_stats': (c_int, [P, P]),
+    'orn_engine_set_stage_targets': (c_int, [P, c_int32, P]),
+    'orn_engine_set_stage_target_stats': (c_int, [P, c_int32, P]),
+    'orn_engine_set_stage_stats': (c_int, [P, P, c_int32]),
     'orn_engine_fused_kernel': (c_int, [P, c_int, POINTER(c_void_p), POINTER(c_void_p)]),
     'orn_engine_scale_state': (c_int, [P, P]),
     'orn_engine_set_grad_scale': (c_int, [P, c_float, c_float]),
@@ -165,7 +170,14 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_msssim_level_bwd_tiles': (c_int, [c_int] * 2),
                'orn_debug_msssim_level_fwd': (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
                'orn_debug_msssim_level_bwd': (c_int, [c_int, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_float, c_float, P, P, P]),
-               'orn_debug_loss_msssim_layout': (c_int, [c_int] * 5 + [POINTER(c_int64)])}
+               'orn_debug_loss_msssim_layout': (c_int, [c_int] * 5 + [POINTER(c_int64)]),
+               'orn_debug_side_head_bwd_ws_bytes': (c_size_t, [c_int] * 3),
+               'orn_debug_side_head_fwd_bf16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
+               'orn_debug_side_head_fwd_f16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
+               'orn_debug_side_head_fwd_f32': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
+               'orn_debug_side_head_bwd_bf16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, c_float, P, P, P, P, c_size_t, P]),
+               'orn_debug_side_head_bwd_f16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, c_float, P, P, P, P, c_size_t, P]),
+               'orn_debug_side_head_bwd_f32': (c_int, [P] * 4 + [c_int] * 4 + [c_float, P, P, P, P, c_size_t, P])}
 
 _lib = None
 

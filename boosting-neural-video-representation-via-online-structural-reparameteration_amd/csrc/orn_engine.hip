@@ -112,6 +112,16 @@ struct orn_engine {
     // for the backward half; every other entry that would overwrite them is refused meanwhile (ORN_E_STATE)
     bool open;
     hipStream_t open_st;
+    // Multi-resolution heads (d.multi_res; include/orn.h, N8): what stage i < n_layers - 1 keeps -- its image, dLoss_i/dout_i, the
+    // loss's stats and workspace, the head backward's partials (workspace carve), and the caller's target tables
+    struct SideStage {
+        int C, H, W;                 // the stage's output: channels of block i's output, image size
+        float *img, *dimg, *stats, *loss_ws, *head_ws;
+        const float *targets, *tstats;
+    } stage[ORN_MAX_LAYERS];
+    float *stage_ring;               // optional [stage_slots][n_layers][2] = {loss_i, psnr_i} (orn_engine_set_stage_stats)
+    int stage_slots;
+    OrnAccumTable side_tab;          // batched step: the side heads' gradient slots (a second accumulate launch)
     // orn_engine_profile_step: HIP events around every forward conv launch of an eager step
     bool prof;
     hipEvent_t prof_ev[4 * ORN_MAX_LAYERS + 4];      // pairs: forward conv of layer i, dgrad launch of layer i, wgrad batch, its reduction
@@ -193,6 +203,24 @@ static int check_desc(const orn_engine_desc *d)
     ORN_REQUIRE(sp, "engine: bad loss_type %d", d->loss_type);
     if (sp->kind == ORN_LOSS_KIND_MSSSIM)       // pytorch_msssim's own limit (H, W: the decoder's output by now)
         ORN_REQUIRE((H < W ? H : W) > 160, "engine: the MS-SSIM losses need an output side above 160 (got %dx%d)", H, W);
+    ORN_REQUIRE(d->multi_res == 0 || d->multi_res == 1, "engine: multi_res = %d is not 0 or 1", d->multi_res);
+    if (d->multi_res) {
+        // a head and a loss of this type on every stage: the loss must take every stage's size, as the reference's does
+        ORN_REQUIRE(fabsf(d->lw) <= 3.0e38f, "engine: lw is not finite");
+        H = d->fc_h; W = d->fc_w;
+        for (int i = 0; i + 1 < d->n_layers; ++i) {
+            H *= d->layer[i].s; W *= d->layer[i].s;
+            ORN_REQUIRE(d->side_head_w[i] >= 0 && d->side_head_b[i] >= 0, "engine: stage %d: missing head tensors (side_head_w / side_head_b)", i);
+            const int64_t Ci = d->layer[i].O / (d->layer[i].s * d->layer[i].s);
+            ORN_REQUIRE(d->side_head_w[i] + 3 * Ci <= d->n_params && d->side_head_b[i] + 3 <= d->n_params,
+                        "engine: stage %d: head tensors lie outside the arena of %lld floats", i, (long long)d->n_params);
+            ORN_REQUIRE(Ci <= 512, "engine: stage %d: a side head takes at most 512 channels (got %lld)", i, (long long)Ci);
+            if (sp->kind == ORN_LOSS_KIND_SSIM)
+                ORN_REQUIRE(H > 10 && W > 10, "engine: stage %d (%dx%d): the SSIM losses need an 11x11 window to fit (H, W > 10)", i, H, W);
+            if (sp->kind == ORN_LOSS_KIND_MSSSIM)
+                ORN_REQUIRE((H < W ? H : W) > 160, "engine: stage %d (%dx%d): the MS-SSIM losses need a side above 160", i, H, W);
+        }
+    }
     return 0;
 }
 
@@ -298,7 +326,26 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
     float *cur_side = take((sizeof(OrnStepCur) + 3) / 4 + 16);
     float *sc_side = take(sizeof(OrnScaleState) / 4 + 16);
     float *dec_ws = take(ORN_DECODE_WS_FLOATS);
+    // multi-resolution heads: behind everything else, so that a single-resolution engine's carve is the one it has always had
+    orn_engine::SideStage stg[ORN_MAX_LAYERS] = {};
+    if (d->multi_res) {
+        int Hi = d->fc_h, Wi = d->fc_w;
+        for (int i = 0; i + 1 < d->n_layers; ++i) {
+            const orn_layer_desc &l = d->layer[i];
+            Hi *= l.s; Wi *= l.s;
+            orn_engine::SideStage &s = stg[i];
+            s.C = l.O / (l.s * l.s); s.H = Hi; s.W = Wi;
+            const size_t isz_i = (size_t)3 * Hi * Wi;
+            s.img = take(isz_i); s.dimg = take(isz_i); s.stats = take(8);
+            s.loss_ws = take(orn_loss_ws_bytes_for(d->loss_type, 1, 3, Hi, Wi) / 4);
+            s.head_ws = take(orn_side_head_bwd_ws_floats(s.C, Hi, Wi));
+        }
+    }
     if (e) {
+        for (int i = 0; i < ORN_MAX_LAYERS; ++i) {       // (the target tables are the caller's: kept)
+            stg[i].targets = e->stage[i].targets; stg[i].tstats = e->stage[i].tstats;
+            e->stage[i] = stg[i];
+        }
         e->pre1 = pre1; e->h1 = h1; e->pre2 = pre2; e->h2 = h2; e->dh2 = dh2;
         e->img = img; e->dimg = dimg; e->stats = stats; e->loss_ws = loss_ws; e->scratch = scr; e->head_ws = head_ws;
         e->cur = (OrnStepCur *)cur;
@@ -308,7 +355,9 @@ static size_t layout(const orn_engine_desc *d, orn_engine *e)
         e->ff = ff; e->dxn = dxn;
         e->stem_ws = al(orn_stem_bwd_ws_floats(1, d->stem_dim, Nout));
         const orn_layer_desc &l0 = d->layer[0];
-        e->stage0 = d->precision != 0 && ff == 1 && d->n_layers > 1 && orn_stage0_supported(l0.C, l0.O, l0.H, l0.W, l0.s);
+        // (multi-resolution heads: stage 0's head reads the block's fp32 activation and adds to its fp32 gradient, which the fused
+        // pair never materialises -- the two blocks stay apart there)
+        e->stage0 = d->precision != 0 && ff == 1 && d->n_layers > 1 && orn_stage0_supported(l0.C, l0.O, l0.H, l0.W, l0.s) && !d->multi_res;
         for (int k = 0; k < 3; ++k) { e->mset[k].tables = mtab[k]; e->mset[k].mh_tables = mhtab[k]; }
         e->cur_side = (OrnStepCur *)cur_side;
         e->sc_side = (OrnScaleState *)sc_side;
@@ -374,6 +423,18 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
         add(d->stem_w0, (int64_t)d->stem_dim * d->embed_len); add(d->stem_b0, d->stem_dim);
         add(d->stem_w1, Nout * d->stem_dim); add(d->stem_b1, Nout);
         e->b_acc = nullptr; e->b_cur = nullptr; e->b_stats = nullptr; e->b_max = 0;
+        // (multi-resolution heads) the side heads' slots: a table of their own, so that the first keeps the launch it has always had
+        OrnAccumTable &s = e->side_tab;
+        s.n = 0;
+        blocks = 0;
+        for (int i = 0; d->multi_res && i + 1 < d->n_layers; ++i) {
+            const int64_t off[2] = {d->side_head_w[i], d->side_head_b[i]}, len[2] = {(int64_t)3 * e->stage[i].C, 3};
+            for (int k = 0; k < 2; ++k) {
+                s.off[s.n] = off[k]; s.len[s.n] = len[k];
+                blocks += orn_cdiv((long)len[k], ORN_ACCUM_CHUNK);
+                s.blk_end[s.n++] = blocks;
+            }
+        }
     }
     {   // the one-pixel borders of the channels-last buffers must be (and stay) zero
         hipError_t rc = hipMemset(ws, 0, need);
@@ -391,7 +452,8 @@ extern "C" int orn_engine_create(const orn_engine_desc *d, float *params, float 
     {
         const int nl = d->n_layers;
         const orn_layer_desc &ll = d->layer[nl - 1];
-        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v && !d->branch_kind;     // (no pipelined form of the ACB / RepVGG / ECB merge)
+        bool ok = d->precision != 0 && e->ff < nl - 1 && grads && adam_m && adam_v && !d->branch_kind     // (no pipelined form of the ACB / RepVGG / ECB merge,
+                  && !d->multi_res;                                                                      //  nor of the multi-resolution heads)
         if (ok) {
             const int64_t lo_all[9] = {ll.w3x3, ll.b3x3, ll.w3x1, ll.b3x1, ll.w1x3, ll.b1x3, ll.w1, ll.w2, ll.w3};
             int64_t lo = d->n_params;
@@ -544,6 +606,57 @@ extern "C" int orn_engine_set_target_stats(orn_engine *e, const float *stats)
     ORN_REQUIRE((uintptr_t)stats % 16 == 0, "engine_set_target_stats: stats must be 16-byte aligned");
     e->tstats = stats;
     drop_graphs(e);
+    return 0;
+}
+
+// ---- multi-resolution heads: the side stages' tables and the per-stage ring (include/orn.h, N8).  Each changes what a captured step
+// reads or writes, so the graph cache is dropped.
+static int side_stage_arg(orn_engine *e, int32_t stage, const void *p, const char *name)
+{
+    if (!e) { orn_set_error("%s: null engine", name); return ORN_E_ARG; }
+    if (!e->d.multi_res) { orn_set_error("%s: the engine was created with multi_res = 0", name); return ORN_E_STATE; }
+    ORN_REQUIRE(stage >= 0 && stage + 1 < e->d.n_layers, "%s: stage %d outside [0, %d) (the last stage's table is `frames`)", name, stage, e->d.n_layers - 1);
+    ORN_REQUIRE((uintptr_t)p % 16 == 0, "%s: the table must be 16-byte aligned", name);
+    return 0;
+}
+
+extern "C" int orn_engine_set_stage_targets(orn_engine *e, int32_t stage, const float *frames)
+{
+    ORN_TRY(side_stage_arg(e, stage, frames, "engine_set_stage_targets"));
+    e->stage[stage].targets = frames;
+    drop_graphs(e);
+    return 0;
+}
+
+extern "C" int orn_engine_set_stage_target_stats(orn_engine *e, int32_t stage, const float *stats)
+{
+    ORN_TRY(side_stage_arg(e, stage, stats, "engine_set_stage_target_stats"));
+    e->stage[stage].tstats = stats;
+    drop_graphs(e);
+    return 0;
+}
+
+extern "C" int orn_engine_set_stage_stats(orn_engine *e, float *out, int32_t n_slots)
+{
+    ORN_REQUIRE(e, "engine_set_stage_stats: null engine");
+    if (!e->d.multi_res) { orn_set_error("engine_set_stage_stats: the engine was created with multi_res = 0"); return ORN_E_STATE; }
+    ORN_REQUIRE(!out || n_slots >= 1, "engine_set_stage_stats: n_slots = %d", n_slots);
+    e->stage_ring = out;
+    e->stage_slots = out ? n_slots : 0;
+    drop_graphs(e);
+    return 0;
+}
+
+// Every side stage has its target table, and the per-stage ring (if any) has the slots this call's records go to
+static int side_ready(const orn_engine *e, int32_t slots_needed, const char *name)
+{
+    if (!e->d.multi_res) return 0;
+    for (int i = 0; i + 1 < e->d.n_layers; ++i)
+        if (!e->stage[i].targets) {
+            orn_set_error("%s: stage %d has no target table (orn_engine_set_stage_targets)", name, i);
+            return ORN_E_STATE;
+        }
+    ORN_REQUIRE(!e->stage_ring || e->stage_slots >= slots_needed, "%s: the per-stage ring has %d slots, %d needed", name, e->stage_slots, slots_needed);
     return 0;
 }
 
@@ -719,13 +832,49 @@ static OrnWgradReduce wgrad_reduce(const orn_engine *e, int i, OrnScaleState *sc
     return OrnWgradReduce{e->L[i].wslab, l.H, l.W, l.C, l.O, l.s, 1.0f / e->gs, e->grads + l.w3x3, e->grads + l.b3x3, sc, slab_cap(e, i)};
 }
 
+// Multi-resolution heads, stage i < n_layers - 1, forward: the image of the block's output (16-bit layers: from the channels-last
+// pre-activation; fp32 layers: from the NCHW activation), then the engine's loss on (image, the stage's target of the step's
+// frame) with its own finalize launch: stats {loss_i, .., psnr_i}, dLoss_i/dout_i un-weighted and un-scaled (lw and the loss scale
+// enter in the head's backward), a non-finite loss raises the step's flag.
+static int side_forward(orn_engine *e, int i, const int *frame_idx, hipStream_t st, OrnScaleState *sc)
+{
+    const orn_engine_desc &d = e->d;
+    const orn_engine::SideStage &s = e->stage[i];
+    const float *w = e->params + d.side_head_w[i], *b = e->params + d.side_head_b[i];
+    const size_t HW = (size_t)s.H * s.W;
+    if (i >= e->ff)
+        ORN_TRY((d.precision == 2 ? orn_launch_side_head_fwd_f16 : orn_launch_side_head_fwd_bf16)(e->L[i].zb, w, b, s.C, HW, d.sigmoid, s.img, st, sc));
+    else
+        ORN_TRY(orn_launch_side_head_fwd_f32(e->L[i].a, w, b, s.C, HW, d.sigmoid, s.img, st, sc));
+    return orn_launch_loss(s.img, s.targets, frame_idx, 3 * HW, 1, 3, s.H, s.W, d.loss_type, 1.0f, s.stats, s.dimg, s.loss_ws, st, nullptr, nullptr, sc,
+                           orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? s.tstats : nullptr, nullptr);
+}
+
+// Backward of the same stage, to run behind block i + 1's dgrad and in front of block i's own backward: adds W_i^T du_i to the
+// gradient block i + 1 left for block i's output and writes the head's own gradients (un-scaled) into the arena.
+static int side_backward(orn_engine *e, int i, hipStream_t st, OrnScaleState *sc)
+{
+    const orn_engine_desc &d = e->d;
+    const orn_engine::SideStage &s = e->stage[i];
+    const float *w = e->params + d.side_head_w[i];
+    float *dw = e->grads + d.side_head_w[i], *db = e->grads + d.side_head_b[i];
+    if (i >= e->ff)
+        return (d.precision == 2 ? orn_launch_side_head_bwd_f16 : orn_launch_side_head_bwd_bf16)(e->L[i].zb, w, s.img, s.dimg, s.C, s.H, s.W, d.sigmoid,
+                                                                                                d.layer[i].s, d.lw, e->gs, e->L[i].dypad, dw, db,
+                                                                                                s.head_ws, st, sc);
+    return orn_launch_side_head_bwd_f32(e->L[i].a, w, s.img, s.dimg, s.C, s.H, s.W, d.sigmoid, d.lw, e->L[i].da, dw, db, s.head_ws, st, sc);
+}
+
 // set: which layers this forward merges (0 all; 1: all but the last block, whose merged kernel the side branch of the previous
 // pipelined step leaves behind -- the forward then waits for that branch where it touches the last block's buffers;
 // MERGE_NONE: nothing -- the parameters have not changed since the previous forward (frames 1.. of orn_engine_decode_frames), so
 // every wf / bf / wb / biasp is used as that forward left it: no W2 transpose, no merge launch, no operand copies, no riders)
 // head: false leaves the A5 head of a 16-bit engine to the caller (the decode output kernel reads the last block's z)
+// side_sc (training forward of a multi-resolution engine): the step's scale-state entry -- behind every block below the last, its
+// stage's head and loss run (side_forward)
 enum { MERGE_NONE = -1 };
-static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set = 0, bool head = true)
+static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set = 0, bool head = true,
+                   OrnScaleState *side_sc = nullptr)
 {
     const bool merge = set != MERGE_NONE;
     const orn_engine_desc &d = e->d;
@@ -796,6 +945,7 @@ static int forward(orn_engine *e, const float *embeds, const int *row_idx, bool 
             ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
         }
+        if (side_sc && i + 1 < nl) ORN_TRY(side_forward(e, i, row_idx, st, side_sc));
     }
     if (ff < nl) {
         if (head)
@@ -1048,7 +1198,33 @@ static int step_front(orn_engine *e, const float *embeds, const orn_step_sched *
         ORN_LAUNCH_CHECK("advance");
     }
     const int *fidx = &step_cur(e, o)->frame;
-    return forward(e, embeds, fidx, true, st, (o.batch > 0 && o.bframe > 0) ? (int)MERGE_NONE : (o.pipe && e->side_busy) ? 1 : 0);
+    return forward(e, embeds, fidx, true, st, (o.batch > 0 && o.bframe > 0) ? (int)MERGE_NONE : (o.pipe && e->side_busy) ? 1 : 0, true,
+                   d.multi_res ? e->sc + o.cur : nullptr);
+}
+
+// Multi-resolution heads, end of a step (one thread): the per-stage ring's entry {loss_i, psnr_i} of every stage, and the weighted
+// sum in the loss entry of the step's record, ((lw l_0 + lw l_1) + ..) + l_last as Python's sum() forms it (main_train.py:243-244).
+// ring: where the last stage's finalize left the record {l_last, L1, MSE, s, PSNR, ..} at cur->slot (null: none kept).
+struct StageRecord {
+    int n_side;
+    const float *stats[ORN_MAX_LAYERS];     // the side stages' loss stats
+    float lw;
+    const OrnStepCur *cur;
+    float *ring, *stage_ring;
+};
+__global__ void k_stage_record(StageRecord r)
+{
+    if (threadIdx.x != 0 || !r.ring) return;
+    float *rec = r.ring + (size_t)r.cur->slot * 8;
+    const float last = rec[0];
+    float sum = 0.f;
+    for (int i = 0; i < r.n_side; ++i) sum = __fadd_rn(sum, __fmul_rn(r.lw, r.stats[i][0]));      // (two roundings, as torch: never an fma)
+    rec[0] = sum + last;
+    if (r.stage_ring) {
+        float *s = r.stage_ring + (size_t)r.cur->slot * (r.n_side + 1) * 2;
+        for (int i = 0; i < r.n_side; ++i) { s[2 * i] = r.stats[i][0]; s[2 * i + 1] = r.stats[i][4]; }
+        s[2 * r.n_side] = last; s[2 * r.n_side + 1] = rec[4];
+    }
 }
 
 // dimg: dLoss/d(e->img), fp32 planar (the engine's own buffer, or the caller's in a split step); fin: the loss's finalize stage for a
@@ -1110,6 +1286,8 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
                                         (i == nl - 1 && head_fused32) ? &hfuse : nullptr, ff >= nl ? b.wd32 : nullptr));
         if (e->prof) (void)hipEventRecord(e->prof_ev[2 * ORN_MAX_LAYERS + 2 * i + 1], st);
         if (pipe && e->fork_behind_dgrad && i == nl - 1) ORN_TRY(side_branch_backward(e, st));     // fork: behind the last block's dgrad
+        // multi-resolution heads: block i - 1's gradient buffer holds what this block sent down; its stage's head adds its own term
+        if (d.multi_res && i >= 1) ORN_TRY(side_backward(e, i - 1, st, sc));
     }
     // stem backward; with a wgrad batch behind it, its last kernel (needed by Adam only) rides along that launch
     OrnStemW0Job w0job;
@@ -1121,10 +1299,20 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
                                 e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr));
     if (ff < nl) ORN_TRY(fast_weight_grads(e, st, pipe, sc, &l2job, &w0job));
     if (pipe && !e->fork_behind_dgrad) ORN_TRY(side_branch_backward(e, st));     // fork: behind the lower blocks' slab reduction
+    if (d.multi_res) {      // (behind the head's backward, which carries a 16-bit engine's loss finalize: the step's -- or, batched, the frame's -- record exists)
+        StageRecord r = {};
+        r.n_side = nl - 1;
+        for (int i = 0; i < nl - 1; ++i) r.stats[i] = e->stage[i].stats;
+        r.lw = d.lw; r.cur = cur; r.ring = batched ? e->b_stats : stats_out; r.stage_ring = e->stage_ring;
+        hipLaunchKernelGGL(k_stage_record, dim3(1), dim3(64), 0, st, r);
+        ORN_LAUNCH_CHECK("stage_record");
+    }
     if (batched) {
         // every directly written gradient slot holds this frame's gradient: fold it into the batch's sum (B == 1: it is the sum)
         if (o.batch > 1)
             ORN_TRY(orn_launch_grad_accum(e->acc_tab, G, e->b_acc, o.bframe == 0 ? 0 : (o.bframe + 1 < o.batch ? 1 : 2), 1.0f / (float)o.batch, st));
+        if (o.batch > 1 && e->side_tab.n)
+            ORN_TRY(orn_launch_grad_accum(e->side_tab, G, e->b_acc, o.bframe == 0 ? 0 : (o.bframe + 1 < o.batch ? 1 : 2), 1.0f / (float)o.batch, st));
         if (o.bframe + 1 < o.batch) return 0;
         cur = e->cur;                                   // the optimiser step's own state (k_advance_batch)
         if (stats_out) ORN_TRY(orn_launch_batch_stats(e->b_stats, o.batch, cur, stats_out, st));
@@ -1164,6 +1352,7 @@ extern "C" int orn_engine_train_step(orn_engine *e, const float *frames, const f
     ORN_REQUIRE(e && frames && embeds && sched && cursor, "engine_train_step: null pointer");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_step: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_train_step");
+    ORN_TRY(side_ready(e, n_slots > 0 ? n_slots : 1, "engine_train_step"));
     return train_step(e, frames, embeds, sched, cursor, stats_out, n_slots, (hipStream_t)stream);
 }
 
@@ -1174,6 +1363,7 @@ extern "C" int orn_engine_step_forward(orn_engine *e, const float *frames, const
     ORN_REQUIRE(e && frames && embeds && sched && cursor && pred, "engine_step_forward: null pointer");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_step_forward: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_step_forward");
+    ORN_REQUIRE(!e->d.multi_res, "engine_step_forward: a multi-resolution engine has no split step (a caller's objective takes one image)");
     assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
     ORN_TRY(step_front(e, embeds, sched, cursor, n_slots, (hipStream_t)stream, StepOpts()));
     *pred = e->img;
@@ -1215,6 +1405,7 @@ extern "C" int orn_engine_train_steps(orn_engine *e, const float *frames, const 
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_train_steps");
+    ORN_TRY(side_ready(e, n_slots > 0 ? n_slots : 1, "engine_train_steps"));
     hipStream_t st = (hipStream_t)stream;
     int rc = 0;
     StepOpts o;
@@ -1256,10 +1447,12 @@ extern "C" int orn_engine_set_batch_ws(orn_engine *e, void *ws, size_t bytes, in
     if (!ws) { e->b_acc = nullptr; e->b_cur = nullptr; e->b_stats = nullptr; e->b_max = 0; return 0; }
     ORN_REQUIRE(max_batch >= 1 && max_batch <= ORN_MAX_BATCH, "engine_set_batch_ws: max_batch=%d outside [1, %d]", max_batch, ORN_MAX_BATCH);
     ORN_REQUIRE((uintptr_t)ws % 256 == 0, "engine_set_batch_ws: workspace must be 256-byte aligned");
-    const OrnAccumTable &t = e->acc_tab;
-    for (int r = 0; r < t.n; ++r)       // (the accumulate launch writes exactly these ranges of both arenas)
-        ORN_REQUIRE(t.off[r] >= 0 && t.len[r] > 0 && t.off[r] + t.len[r] <= e->d.n_params,
-                    "engine_set_batch_ws: gradient range %d [%lld, +%lld) lies outside the arena", r, (long long)t.off[r], (long long)t.len[r]);
+    for (const OrnAccumTable *tp : {&e->acc_tab, &e->side_tab}) {
+        const OrnAccumTable &t = *tp;
+        for (int r = 0; r < t.n; ++r)       // (the accumulate launches write exactly these ranges of both arenas)
+            ORN_REQUIRE(t.off[r] >= 0 && t.len[r] > 0 && t.off[r] + t.len[r] <= e->d.n_params,
+                        "engine_set_batch_ws: gradient range %d [%lld, +%lld) lies outside the arena", r, (long long)t.off[r], (long long)t.len[r]);
+    }
     size_t cur_off, stats_off;
     const size_t need = batch_ws_layout(&e->d, max_batch, &cur_off, &stats_off);
     if (bytes < need) { orn_set_error("engine_set_batch_ws: workspace %zu < %zu", bytes, need); return ORN_E_WS; }
@@ -1278,6 +1471,7 @@ extern "C" int orn_engine_train_steps_batch(orn_engine *e, const float *frames, 
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps_batch: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps_batch: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_train_steps_batch");
+    ORN_TRY(side_ready(e, batch, "engine_train_steps_batch"));
     ORN_REQUIRE(e->b_acc, "engine_train_steps_batch: no batch workspace (orn_engine_set_batch_ws)");
     ORN_REQUIRE(batch >= 1 && batch <= e->b_max, "engine_train_steps_batch: batch=%d outside [1, %d] (max_batch of the workspace)", batch, e->b_max);
     assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
@@ -1303,6 +1497,7 @@ extern "C" int orn_engine_profile_step(orn_engine *e, const float *frames, const
     ORN_REQUIRE(e && frames && embeds && sched && cursor && ms_out, "engine_profile_step: null pointer");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_profile_step: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_profile_step");
+    ORN_TRY(side_ready(e, n_slots > 0 ? n_slots : 1, "engine_profile_step"));
     hipStream_t st = (hipStream_t)stream;
     const int nl = e->d.n_layers;
     for (int i = 0; i < 4 * ORN_MAX_LAYERS + 4; ++i)
@@ -1343,6 +1538,7 @@ extern "C" int orn_engine_train_steps_graph(orn_engine *e, const float *frames, 
     ORN_REQUIRE(e && frames && embeds && sched && cursor && n_steps >= 0, "engine_train_steps_graph: bad arguments");
     ORN_REQUIRE(e->grads && e->m && e->v, "engine_train_steps_graph: engine was created without grads / Adam arenas");
     ORN_REQUIRE_CLOSED(e, "engine_train_steps_graph");
+    ORN_TRY(side_ready(e, n_slots > 0 ? n_slots : 1, "engine_train_steps_graph"));
     hipStream_t st = (hipStream_t)stream;
     const bool same = e->graph_exec && e->g_frames == frames && e->g_embeds == embeds && e->g_sched == sched &&
                       e->g_cursor == cursor && e->g_stats == stats_out && e->g_slots == n_slots && e->g_stream == st;

@@ -51,8 +51,15 @@ def arena_layout(named_shapes: Sequence[Tuple[str, Tuple[int, ...]]]):
     return out, off
 
 
-def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999, eps=1e-8, precision=0) -> EngineDesc:
-    """Describe `model` (our Generator mirror) to the native engine."""
+def is_multi_res(model) -> bool:
+    """A head on every stage (Generator(sin_res=False), model.py:597-625), not on the last alone."""
+    return len(model.head_layers) > 1 and all(h is not None for h in model.head_layers)
+
+
+def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999, eps=1e-8, precision=0, lw=1.0,
+               multi_res=None) -> EngineDesc:
+    """Describe `model` (our Generator mirror) to the native engine.  A multi-resolution model (is_multi_res) gives a multi-resolution
+    engine with the side stages' weight lw (--lw); multi_res=False describes its last stage alone (decode-only engines)."""
     d = EngineDesc()
     n_layers = len(model.layers)
     if n_layers > _lib.ORN_MAX_LAYERS:
@@ -71,6 +78,10 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
     d.stem_w1, d.stem_b1 = layout['stem.2.weight'][0], layout['stem.2.bias'][0]
     d.head_w, d.head_b = layout[f'head_layers.{n_layers - 1}.weight'][0], layout[f'head_layers.{n_layers - 1}.bias'][0]
     d.n_params = total
+    if is_multi_res(model) if multi_res is None else multi_res:
+        d.multi_res, d.lw = 1, lw
+        for i in range(n_layers - 1):
+            d.side_head_w[i], d.side_head_b[i] = layout[f'head_layers.{i}.weight'][0], layout[f'head_layers.{i}.bias'][0]
     H, W = model.fc_h, model.fc_w
     for i, blk in enumerate(model.layers):
         L = d.layer[i]
@@ -240,7 +251,8 @@ class Decoder(_Decoding):
                 view.copy_(p.detach().to(self.device))
                 p.data = view                                   # the module and the engine share the arena
         self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
-        self.desc = build_desc(model, self.layout, self.n_params, 'L2', 0.5, 0.999, 1e-8, self.precision)
+        # (a multi-resolution model decodes its last stage: the single-resolution engine on the tensors the two share)
+        self.desc = build_desc(model, self.layout, self.n_params, 'L2', 0.5, 0.999, 1e-8, self.precision, multi_res=False)
         nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
         if nbytes == 0:
             raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
@@ -255,7 +267,7 @@ class TrainEngine(_Decoding):
     """Native training engine for one video (one process / one GPU per video)."""
 
     def __init__(self, model, loss_type: str = 'Fusion6', beta: float = 0.5, precision: str = 'fp32',
-                 device: Optional[torch.device] = None, n_slots: int = 4096, target_cache: bool = True):
+                 device: Optional[torch.device] = None, n_slots: int = 4096, target_cache: bool = True, lw: float = 1.0):
         if not torch.cuda.is_available():
             raise OrnError('TrainEngine needs a GPU: there is no CPU path')
         self.device = torch.device(device or f'cuda:{torch.cuda.current_device()}')
@@ -275,7 +287,9 @@ class TrainEngine(_Decoding):
                 p.data = view                                   # parameters now live in the arena
                 p.grad = self.grads[off:off + n].view(p.shape)  # and their grads in the grad arena
         self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
-        self.desc = build_desc(model, self.layout, self.n_params, loss_type, beta, 0.999, 1e-8, self.precision)
+        # a model with a head on every stage (Generator(sin_res=False)) trains them all: sum_{i < n-1} lw * loss_i + loss_{n-1}
+        self.desc = build_desc(model, self.layout, self.n_params, loss_type, beta, 0.999, 1e-8, self.precision, lw)
+        self.multi_res = bool(self.desc.multi_res)
         nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
         if nbytes == 0:
             raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
@@ -288,6 +302,11 @@ class TrainEngine(_Decoding):
         self.tstats = None
         self.n_slots = n_slots
         self.stats_ring = torch.zeros(n_slots, 8, device=dev)
+        self.stage_ring = None
+        self.stage_frames, self.stage_tstats = [], []
+        if self.multi_res:                                 # {loss_i, psnr_i} of every stage, beside each step's record
+            self.stage_ring = torch.zeros(n_slots, self.desc.n_layers, 2, device=dev)
+            check(lib().orn_engine_set_stage_stats(self._h, _lib.ptr(self.stage_ring), c_int32(n_slots)), 'orn_engine_set_stage_stats')
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sched = None
         self.frames = None
@@ -304,10 +323,14 @@ class TrainEngine(_Decoding):
         self.stream = torch.cuda.Stream(device=dev)
 
     # ---- data ---------------------------------------------------------------------------------
-    def set_video(self, frames: torch.Tensor, embeds: torch.Tensor):
+    def set_video(self, frames: torch.Tensor, embeds: torch.Tensor, stage_frames: Optional[Sequence[torch.Tensor]] = None):
         """frames [N,3,H,W] fp32 in [0,1] (resident in HBM), embeds [N,E] (PE of k/N).  Frames of another size than the decoder's
         output, or uint8 [N,H,W,3], are pooled to it once, on the device (_target_frames): the target-statistics cache, the
-        schedule, every step form and the evaluation see the pooled table only."""
+        schedule, every step form and the evaluation see the pooled table only.
+        A multi-resolution engine also needs every lower stage's target, adaptive_avg_pool2d of the SOURCE frames to that stage's size
+        (main_train.py:239): pooled here from `frames` as given, or taken from stage_frames (one fp32 [N,3,H_i,W_i] table per stage
+        below the last) when the caller has pooled a source it does not keep resident (a frame directory read piece by piece)."""
+        source = frames
         frames = self._target_frames(frames)
         if embeds.shape != (frames.shape[0], self.desc.embed_len):
             raise OrnError(f'embeds {tuple(embeds.shape)} vs ({frames.shape[0]}, {self.desc.embed_len})')
@@ -328,6 +351,41 @@ class TrainEngine(_Decoding):
                 check(lib().orn_loss_target_stats(_lib.ptr(self.frames), n, 3, H, W, _lib.ptr(self.tstats), c_void_p(cur.cuda_stream)),
                       'orn_loss_target_stats')
                 check(lib().orn_engine_set_target_stats(self._h, _lib.ptr(self.tstats)), 'orn_engine_set_target_stats')
+        if self.multi_res:
+            self._set_stage_tables(source, stage_frames)
+
+    def stage_hw(self) -> List[Tuple[int, int]]:
+        """Image size of every stage, the last included."""
+        H, W, out = self.model.fc_h, self.model.fc_w, []
+        for blk in self.model.layers:
+            H, W = H * blk.stride, W * blk.stride
+            out.append((H, W))
+        return out
+
+    def _set_stage_tables(self, source: torch.Tensor, given=None):
+        """The target table of every stage below the last: F.adaptive_avg_pool2d(data, out_i.shape[-2:]) of main_train.py:239, pooled
+        from the SOURCE pixels (not from the last stage's table) by ops.ingest_frames, as the last stage's table is; and, for the
+        SSIM kinds, the target side of its SSIM statistics."""
+        src = source.to(self.device)
+        src = src.contiguous() if src.dtype == torch.uint8 else src.to(torch.float32).contiguous()
+        self.stage_frames, self.stage_tstats = [], []
+        cur = c_void_p(torch.cuda.current_stream().cuda_stream)
+        for i, (h, w) in enumerate(self.stage_hw()[:-1]):
+            if given is not None:
+                tab = given[i].to(self.device, torch.float32).contiguous()
+                if tuple(tab.shape) != (self.frames.shape[0], 3, h, w):
+                    raise OrnError(f'set_video: stage_frames[{i}] {tuple(tab.shape)} vs {(self.frames.shape[0], 3, h, w)}')
+            else:
+                tab = ops.ingest_frames(src, (h, w))
+            self.stage_frames.append(tab)
+            check(lib().orn_engine_set_stage_targets(self._h, i, _lib.ptr(tab)), 'orn_engine_set_stage_targets')
+            ts = None
+            nbytes = lib().orn_loss_target_stats_bytes(tab.shape[0], 3, h, w) if self.target_cache else 0
+            if 0 < nbytes < torch.cuda.mem_get_info(self.device)[0] // 2:
+                ts = torch.empty(nbytes // 4, device=self.device)
+                check(lib().orn_loss_target_stats(_lib.ptr(tab), tab.shape[0], 3, h, w, _lib.ptr(ts), cur), 'orn_loss_target_stats')
+            self.stage_tstats.append(ts)
+            check(lib().orn_engine_set_stage_target_stats(self._h, i, _lib.ptr(ts)), 'orn_engine_set_stage_target_stats')
 
     def set_schedule(self, entries: Sequence[Tuple[int, int, float]]):
         """Upload the next run's per-step (frame, global step, lr) entries and rewind the cursor."""
@@ -411,6 +469,9 @@ class TrainEngine(_Decoding):
         Returns the engine's output as a [1,3,H,W] fp32 VIEW into its workspace (no copy), ordered before the caller's current
         stream.  The step is now open: until backward_step() every other stepping or decoding call of this engine raises OrnError.
         `open_frame` holds the index of the step's frame (its target is frames[open_frame]), from the host copy of the schedule."""
+        if self.multi_res:
+            raise OrnError('forward_step: a multi-resolution engine has no split step (a caller-supplied objective takes one image; '
+                           'build the model with sin_res=True)')
         if self.frames is None or self.sched is None:
             raise OrnError('set_video() and set_schedule() first')
         if self._cursor_host >= self._sched_len:
@@ -543,6 +604,13 @@ class TrainEngine(_Decoding):
     def stats(self, n: int) -> torch.Tensor:
         """[n,8] host tensor of the last run's first n steps: loss, L1, MSE, SSIM, PSNR, lr, frame, step."""
         return self.stats_ring[:n].cpu()
+
+    def stage_stats(self, n: int) -> torch.Tensor:
+        """[n, n_stages, 2] host tensor of the last run's first n steps (multi-resolution engine): the un-weighted loss and the PSNR of
+        every stage, the last stage in the last row.  After a batched run: the frames of the last optimiser step, in batch order."""
+        if self.stage_ring is None:
+            raise OrnError('stage_stats: not a multi-resolution engine')
+        return self.stage_ring[:n].cpu()
 
     def engine_fused_kernel(self, layer: int):
         """(Wf, bf) of block `layer` exactly as the ENGINE's last merge left them in its workspace (copies; ERB, ACB, RepVGG, ECB)."""

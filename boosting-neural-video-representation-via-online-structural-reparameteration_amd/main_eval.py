@@ -130,6 +130,9 @@ def main(argv=None):
         # the fine-tune's loop takes one frame per optimiser step; a -b it ignored would silently be another recipe
         raise ValueError(f'--finetune with -b/--batchSize {args.batchSize}: the prune fine-tune steps one frame at a time; use -b 1 '
                          '(batched steps are built for main_train only)')
+    if args.finetune and not args.single_res:
+        raise ValueError('--finetune needs --single_res: the prune fine-tune of a multi-resolution generator (a head on every stage) is '
+                         'not built')
     args.warmup = int(args.warmup * args.epochs)          # main_eval.py:106 (as main_train.parse_args): warm-up in epochs
     outf = os.path.join('result', args.outf, f'{args.suffix}')
     # a job that fitted several videos wrote one sub-directory per video (main_train.video_outf)
@@ -205,7 +208,7 @@ def main(argv=None):
     dumped = []
     with torch.no_grad():
         for k in range(n):
-            img = model(embeds[k:k + 1])[0]
+            img = model(embeds[k:k + 1])[-1]                 # the last stage (main_eval.py:467-472: a multi-resolution model returns one image per stage)
             st, _ = ops.loss_stats(img, frames[k:k + 1], 'L2', want_grad=False)
             psnrs.append(st[4])
             if args.dump_images:                      # main_eval.py:795-803 (written after the timed loop)
@@ -222,7 +225,7 @@ def main(argv=None):
             arr = im.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to('cpu', torch.uint8).numpy()
             Image.fromarray(arr).save(os.path.join(visual_dir, f'pred_{k}.png'))
     with torch.no_grad():                                            # untimed, as the FPS above is the decoder's
-        ms = [utils.msssim_fn([model(embeds[k:k + 1])[0]], [frames[k:k + 1]])[0, 0] for k in range(n)]
+        ms = [utils.msssim_fn([model(embeds[k:k + 1])[-1]], [frames[k:k + 1]])[0, 0] for k in range(n)]
     msg = f'Eval: PSNR {psnr:.2f} dB, MS-SSIM {float(torch.stack(ms).mean()):.4f}, decode {fps:.1f} FPS, params {n_param / 1e6:.3f} M'
     if bits is not None:
         msg += f', bpp {bits / (n * hw[0] * hw[1]):.4f}'

@@ -305,6 +305,9 @@ def custom_loss_of(args):
     fn = load_custom_loss(spec)
     if args.batchSize != 1:
         raise ValueError(f'--custom_loss trains one frame per optimiser step: -b/--batchSize {args.batchSize} is not supported with it (use -b 1)')
+    if not args.single_res:
+        raise ValueError('--custom_loss takes one image: it needs --single_res (without it the generator has a head on every stage and '
+                         'the objective is the --lw-weighted sum of the built-in loss over the stages)')
     return fn
 
 
@@ -377,11 +380,16 @@ def fit_video(args, name, vid_index, rank, _inject=None):
                              deploy=args.deploy, branch_type=args.branch_type)
     total_params = sum(p.numel() for p in model.parameters()) / 1e6
     precision = args.precision
-    eng = oeng.TrainEngine(model, loss_type=args.loss_type, beta=args.beta, precision=precision)
+    eng = oeng.TrainEngine(model, loss_type=args.loss_type, beta=args.beta, precision=precision, lw=args.lw)
     frames, pos = load_frames(args, eng.out_hw, eng.device, name, vid_index, args.frame_gap)
     n = frames.shape[0]
     embeds = PE(pos)
-    eng.set_video(frames, embeds)                                   # pos: model.py:37,68
+    # without --single_res every lower stage has a target of its own, pooled from the source pixels like the last stage's
+    # (main_train.py:239); synthetic frames ARE the source, at the decoder's size: the engine pools them
+    stage_frames = None
+    if eng.multi_res and not args.synthetic:
+        stage_frames = [load_frames(args, hw, eng.device, name, vid_index, args.frame_gap)[0] for hw in eng.stage_hw()[:-1]]
+    eng.set_video(frames, embeds, stage_frames)                     # pos: model.py:37,68
     val = None
     if args.frame_gap != 1:                                         # the validation samples are not a subset of the training ones
         vf, vp = load_frames(args, eng.out_hw, eng.device, name, vid_index, args.test_gap)
@@ -432,11 +440,11 @@ def fit_video(args, name, vid_index, rank, _inject=None):
             carry = step0 - epoch_start.applied                          # steps skipped before the restored epoch began, by any engine
             m0, v0 = eng.adam_m.clone(), eng.adam_v.clone()
             del eng
-            eng = oeng.TrainEngine(model, loss_type=args.loss_type, beta=args.beta, precision=wider)
+            eng = oeng.TrainEngine(model, loss_type=args.loss_type, beta=args.beta, precision=wider, lw=args.lw)
             eng.adam_m.copy_(m0); eng.adam_v.copy_(v0)
             eng.global_step = step0
             eng.skipped_carry = carry                                   # the new engine's own counter starts at 0
-            eng.set_video(frames, embeds)
+            eng.set_video(frames, embeds, stage_frames)
             precision, skipped_before = wider, 0
             best_snap = None if best_snap is None else best_snap       # (arena-sized tensors: still valid for the new engine)
             continue
@@ -448,8 +456,14 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         if is_train_best:
             best.train_psnr = train_psnr
             best_snap, best_dirty = Snapshot(eng, epoch), True
+        psnr_log = f'{train_psnr:.2f}'
+        if eng.multi_res:
+            # one column per stage, as the reference logs them (main_train.py:256-263); best values follow the last stage.  -b > 1: the
+            # per-stage ring holds the frames of the epoch's last optimiser step
+            ss = eng.stage_stats(steps_per_epoch if B == 1 else B)
+            psnr_log = '[' + ', '.join(f'{float(v):.2f}' for v in ss[:, :, 1].mean(dim=0)) + ']'
         line = (f'[{time.strftime("%Y/%m/%d %H:%M:%S")}] Rank:{rank}, Video:{name}, Epoch[{epoch + 1}/{args.epochs}], lr:{st[-1, 5]:.2e} '
-                f'PSNR: {train_psnr:.2f}, best: {float(best.train_psnr):.2f}, loss: {st[:, 0].mean():.5f}, steps: {steps_per_epoch}, '
+                f'PSNR: {psnr_log}, best: {float(best.train_psnr):.2f}, loss: {st[:, 0].mean():.5f}, steps: {steps_per_epoch}, '
                 f'{(time.time() - start) / (epoch + 1):.3f} s/epoch')
         say(line, console=epoch % max(1, args.print_freq // 10) == 0 or epoch == args.epochs - 1)
         is_eval = (epoch + 1) % args.eval_freq == 0 or epoch > args.epochs - 10     # main_train.py:303

@@ -187,12 +187,10 @@ class Generator(nn.Module):
                                          act=kargs['act'], deploy=kargs['deploy'], conv_type=kargs.get('conv_type', 'conv'),
                                          branch_type=kargs['branch_type']))
             ngf = new_ngf
+            # model.py:597-608: one head on the last stage (sin_res), else one on every stage, drawn right behind its block
             head_layer = None
-            if kargs['sin_res']:
-                if i == len(self.stride_list) - 1:
-                    head_layer = nn.Conv2d(ngf, 3, 1, 1, bias=kargs['bias'])
-            else:
-                raise NotImplementedError('multi-resolution heads (no --single_res) are outside the hot path')
+            if not kargs['sin_res'] or i == len(self.stride_list) - 1:
+                head_layer = nn.Conv2d(ngf, 3, 1, 1, bias=kargs['bias'])
             self.head_layers.append(head_layer)
         self.sigmoid = kargs['sigmoid']
 

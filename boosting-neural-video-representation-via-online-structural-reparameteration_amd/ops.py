@@ -261,6 +261,54 @@ class HeadFn(torch.autograd.Function):
         return da, dw, db, None
 
 
+# ---- side heads of the multi-resolution generator (orn_side_head.hip, include/orn_debug.h) -------
+_H16 = {torch.bfloat16: 'bf16', torch.float16: 'f16'}
+
+
+def _side_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise _lib.OrnError(f'{name} is not in this build of liborn.so')
+    return fn
+
+
+def side_head_fwd(x, w, b, sigmoid: bool = False) -> torch.Tensor:
+    """The head of one stage, model.py:621-622, -> out [3,H,W] fp32.  x: the block's stored output in the layout the engine keeps it
+    in -- bf16 / fp16 [H,W,C] channels-last PRE-activation (the head forms SiLU itself), or fp32 [C,H,W] activation."""
+    w, b = _f32c(w).reshape(3, -1), _f32c(b)
+    (C, H, W) = x.shape if x.dtype == torch.float32 else (x.shape[2], x.shape[0], x.shape[1])
+    out = torch.empty(3, H, W, device=x.device)
+    name = f'orn_debug_side_head_fwd_{_H16.get(x.dtype, "f32")}'
+    check(_side_fn(name)(ptr(x), ptr(w), ptr(b), C, H, W, int(bool(sigmoid)), ptr(out), stream()), name)
+    return out
+
+
+def side_head_bwd_(x, w, out, dout, grad, sigmoid: bool = False, lw: float = 1.0, sp: int = 1, gs: float = 1.0):
+    """The accumulating backward of a side head: ADDS this head's term to `grad`, in place, and returns (dW [3,C], db [3]).
+    du = dout * lw * act'(out).  16-bit x [H,W,C] (pre-activation z): grad is the block's padded un-shuffled gradient buffer
+    [H/sp + 2, W/sp + 2, C sp^2] of x's dtype, carrying the scale gs; every interior element becomes
+    round(fp32(grad) + gs * (W^T du) * SiLU'(z)), the ring stays as it is; dW, db come back un-scaled.  fp32 x [C,H,W] (activation):
+    grad [C,H,W] += W^T du (sp, gs unused)."""
+    w, out, dout = _f32c(w).reshape(3, -1), _f32c(out), _f32c(dout)
+    f32 = x.dtype == torch.float32
+    (C, H, W) = x.shape if f32 else (x.shape[2], x.shape[0], x.shape[1])
+    want = (C, H, W) if f32 else (H // sp + 2, W // sp + 2, C * sp * sp)
+    if grad.dtype != x.dtype or tuple(grad.shape) != want or not grad.is_contiguous():
+        raise _lib.OrnError(f'side_head_bwd_: grad {grad.dtype} {tuple(grad.shape)} vs contiguous {x.dtype} {want}')
+    dw = torch.empty(3, C, device=x.device)
+    db = torch.empty(3, device=x.device)
+    ws = _ws(_side_fn('orn_debug_side_head_bwd_ws_bytes')(C, H, W), x.device)
+    if f32:
+        check(_side_fn('orn_debug_side_head_bwd_f32')(ptr(x), ptr(w), ptr(out), ptr(dout), C, H, W, int(bool(sigmoid)), c_float(lw),
+                                                      ptr(grad), ptr(dw), ptr(db), ptr(ws), c_size_t(ws.numel()), stream()),
+              'orn_debug_side_head_bwd_f32')
+    else:
+        name = f'orn_debug_side_head_bwd_{_H16[x.dtype]}'
+        check(_side_fn(name)(ptr(x), ptr(w), ptr(out), ptr(dout), C, H, W, int(bool(sigmoid)), sp, c_float(lw), c_float(gs),
+                             ptr(grad), ptr(dw), ptr(db), ptr(ws), c_size_t(ws.numel()), stream()), name)
+    return dw, db
+
+
 # ---- A7 / A10 ------------------------------------------------------------------------------
 def loss_stats(pred, target, loss_type: str = 'Fusion6', want_grad: bool = True, loss_scale: float = 1.0):
     """-> (stats[8] device tensor, dpred or None).  stats = [loss, L1, MSE, SSIM (MS-SSIM for Fusion10-12), PSNR, 0, 0, 0].

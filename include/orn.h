@@ -40,7 +40,9 @@ extern "C" {
                                   * orn_engine_train_steps_batch; + orn_engine_step_forward, orn_engine_step_backward (the split step);
                                   * + orn_frames_ingest_u8, orn_frames_pool_f32 (K11: frames of any size); + orn_stem_bwd_ws_bytes;
                                   * + ORN_BRANCH_ACB / _REPVGG / _ECB, orn_branch_ptrs, orn_branch_merge_fwd / _bwd_ws_bytes / _bwd, and, appended
-                                  * to orn_engine_desc, branch_kind + branch[] (N7: the paper's comparison blocks through an online merge) */
+                                  * to orn_engine_desc, branch_kind + branch[] (N7: the paper's comparison blocks through an online merge);
+                                  * + orn_engine_set_stage_targets / _stage_target_stats / _stage_stats and, appended to orn_engine_desc, multi_res + lw +
+                                  * side_head_w[] / side_head_b[] (N8: a head and a loss at every stage) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -316,6 +318,11 @@ typedef struct orn_engine_desc {
                                      * step, graph replay, batched and split step, decode; no pipelined form */
     int32_t reserved_;
     orn_branch_desc branch[ORN_MAX_LAYERS];
+    /* appended (multi-resolution heads); all zero = the engine of before */
+    int32_t multi_res;              /* 1: a head on every stage (model.py:597-625 without sin_res) and the objective of main_train.py:239-250,
+                                     * sum_{i < n-1} lw * loss(out_i, target_i) + loss(out_{n-1}, target_{n-1}); see orn_engine_set_stage_targets */
+    float lw;                       /* weight of the stages below the last (--lw) */
+    int64_t side_head_w[ORN_MAX_LAYERS], side_head_b[ORN_MAX_LAYERS];   /* heads of stages 0 .. n_layers-2: [3,C_i,1,1], [3]; head_w / head_b stay the last stage's */
 } orn_engine_desc;
 
 /* One entry of the per-step schedule (device array, uploaded per epoch by the caller). */
@@ -397,6 +404,29 @@ ORN_API int orn_engine_set_grad_mask(orn_engine *e, const float *mask);
 /* Optional table of orn_loss_target_stats for the frame table the following steps are given (device, 16-byte aligned, caller-owned,
  * alive while set; null removes it).  Used by the SSIM kinds (SSIM, Fusion1-6, Fusion9); other loss types ignore it. */
 ORN_API int orn_engine_set_target_stats(orn_engine *e, const float *stats);
+/* ---- N8  multi-resolution heads: a head and a loss at every stage       model.py:597-625, main_train.py:239-250 ----
+ * An engine created with multi_res = 1 trains every stage's head.  Stage i < n_layers - 1 (a SIDE stage) has the image
+ * out_i = act(W_i a_i + b_i) [3][H_i][W_i] of its block's output a_i, the loss of `loss_type` against its own target, weighted by lw,
+ * and the backward term  da_i += W_i^T du_i,  du_i = lw * dLoss_i/dout_i * act'(out_i),  which the side head's backward adds to the
+ * gradient buffer that block i + 1's dgrad has already written (orn_side_head.hip; 16-bit layers: the stored half + the term in fp32,
+ * rounded once).  The last stage, every conv, merge and Adam launch are those of a single-resolution engine; lw = 0 gives its bits.
+ * Forms: orn_engine_train_step, orn_engine_train_steps (always the serial form here), _graph, _batch.  The split step
+ * (orn_engine_step_forward) returns ORN_E_ARG: a caller's objective takes one image.  Decode and evaluation run no side head.
+ * A 16-bit engine keeps its first block apart from the second (no fused first pair), so that the block's output exists in a layout a
+ * head can read.  A non-finite pre-activation of a side head, side loss or side-head gradient raises the step's flag like any other.
+ * orn_engine_create refuses (ORN_E_ARG, the stage named) a descriptor whose loss does not take a stage's size: an SSIM kind needs
+ * H_i, W_i > 10, an MS-SSIM kind min(H_i, W_i) > 160 (pytorch_msssim asserts there).
+ *   set_stage_targets: the resident target table of side stage `stage`, fp32 [n][3][H_i][W_i] (device, 16-byte aligned, caller-owned,
+ *     alive while set), indexed by the schedule's frame index like `frames`: adaptive_avg_pool2d of the SOURCE frames to that stage's
+ *     size (orn_frames_ingest_u8 / orn_frames_pool_f32).  Every side stage needs one before a training step (ORN_E_STATE otherwise).
+ *   set_stage_target_stats: orn_loss_target_stats of that table (SSIM kinds; optional; null removes it), as orn_engine_set_target_stats.
+ *   set_stage_stats: optional device ring [n_slots][n_layers][2] = {unweighted loss_i, psnr_i} of every stage, the last included,
+ *     written at the slot of the step's record; in a batched step at the frame's place in the batch (null removes it).
+ * The [n_slots][8] record keeps its layout: its loss entry holds the weighted sum, ((lw l_0 + lw l_1) + ..) + l_last in fp32; L1, MSE,
+ * s and PSNR stay the last stage's.  All three calls drop the graph cache. */
+ORN_API int orn_engine_set_stage_targets(orn_engine *e, int32_t stage, const float *frames);
+ORN_API int orn_engine_set_stage_target_stats(orn_engine *e, int32_t stage, const float *stats);
+ORN_API int orn_engine_set_stage_stats(orn_engine *e, float *out, int32_t n_slots);
 /* One eager training step with HIP events around the conv launches, on the launch stream; synchronises it.  ms_out (host,
  * 2*n_layers + 2 floats): [i] forward conv of layer i, [n_layers + i] dgrad launch of layer i (0: none), [2*n_layers] the
  * batched wgrad launch of the 16-bit layers, [2*n_layers + 1] its split-K reduction (0 in fp32 mode, where each layer's

@@ -110,6 +110,35 @@ ORN_API int orn_debug_msssim_level_bwd(int form, const float *x, const float *y,
                                        const int *frame_idx, size_t frame_stride, int planes, int H, int W, float g_l1, float g_l2,
                                        float *g, float *part_l1, void *stream);
 ORN_API int orn_debug_loss_msssim_layout(int loss_type, int B, int Ch, int H, int W, int64_t *out);
+/* The side heads of a multi-resolution generator (model.py:597-625 without sin_res; orn_side_head.hip): the head of a stage below
+ * the last one, whose backward ADDS to a gradient buffer the block above has already written.  tests/test_gpu_side_head.py pins
+ * them elementwise to fp64.  w [3][C], b [3], out / dout [3][H][W] planar fp32; 1 <= C <= 512, H*W <= 2^30; sigmoid: 0 = (tanh + 1) / 2.
+ *   fwd (16 bit): z [H][W][C] channels-last pre-activation (bf16 / IEEE half); out = act(W SiLU(z) + b), every element written.
+ *          Per-pixel arithmetic and, with C % 32 == 0, summation order of the last stage's 16-bit head.
+ *   fwd_f32: a [C][H][W] activation (fp32 NCHW); out = act(W a + b), one c-ordered fmaf chain per output, expf / tanhf.
+ *   bwd (16 bit): du = dout * lw * gs * act'(out).  dypad: the block's gradient buffer, [H/sp + 2][W/sp + 2][C sp^2] channels-last,
+ *          pixel (h, w) channel c at ((h/sp + 1) (W/sp + 2) + w/sp + 1) C sp^2 + ((h % sp) sp + w % sp) C + c (H % sp == W % sp == 0).
+ *          Every interior element becomes round16(fp32(old) + (W^T du)[c] * SiLU'(z)): one rounding; the one-pixel ring is neither
+ *          read nor written.  16-byte accesses when C % 8 == 0 and z, dypad are 16-byte aligned, element-wise otherwise.
+ *          dw [3][C] = sum_pixels du SiLU(z) / gs, db [3] = sum du / gs: overwritten, fixed summation order.
+ *   bwd_f32: a [C][H][W] activation, da [C][H][W] the gradient with respect to it: da += W^T du with du = dout * lw * act'(out);
+ *          dw = sum du a, db = sum du.
+ *   ws: orn_debug_side_head_bwd_ws_bytes(C, H, W) bytes (0 for sizes outside the ranges above), 4-byte aligned; ORN_E_WS below that. */
+ORN_API size_t orn_debug_side_head_bwd_ws_bytes(int C, int H, int W);
+ORN_API int orn_debug_side_head_fwd_bf16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                         void *stream);
+ORN_API int orn_debug_side_head_fwd_f16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                        void *stream);
+ORN_API int orn_debug_side_head_fwd_f32(const float *a, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                        void *stream);
+ORN_API int orn_debug_side_head_bwd_bf16(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W,
+                                         int sigmoid, int sp, float lw, float gs, void *dypad, float *dw, float *db, void *ws,
+                                         size_t ws_bytes, void *stream);
+ORN_API int orn_debug_side_head_bwd_f16(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W,
+                                        int sigmoid, int sp, float lw, float gs, void *dypad, float *dw, float *db, void *ws,
+                                        size_t ws_bytes, void *stream);
+ORN_API int orn_debug_side_head_bwd_f32(const float *a, const float *w, const float *out, const float *dout, int C, int H, int W,
+                                        int sigmoid, float lw, float *da, float *dw, float *db, void *ws, size_t ws_bytes, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
