@@ -305,3 +305,4 @@ __device__ __forceinline__ void orn_loss_finalize_block(const OrnLossFinalJob &j
 // ---- internal cross-file entry points (not exported) -----------------------------------------
 // Generic deterministic column reduce: out[j] = sum_{i<rows} in[i*ld + j], fixed order.
 int orn_launch_reduce_rows(const float *in, int rows, size_t ld, size_t n, float *out, hipStream_t st);
+bool orn_reduce_rows_is_tall(int rows, size_t n);      // which of its two kernels it launches

@@ -226,42 +226,69 @@ int orn_conv3x3_f32_nsplit(int B, int C, int O, int H, int W)
     return ns < 1 ? 1 : ns;
 }
 
+// What orn_launch_conv3x3_f32 launches for a shape: the one copy of the selection (the launcher and orn_debug_conv_f32_plan).
+struct ConvSel {
+    bool small;                // 2-row tiles
+    int tiles_w, tiles_h;
+    bool split;                // input channels over blockIdx.z into partial slabs, then a row reduction
+    int nsplit, c_per_split;
+    bool tail32;               // O % 64 == 32 on 8-row tiles: the last 32 channels on a 32-channel tile
+    int n64;                   // 64-channel tiles of the (first) launch; 0: the tail alone
+};
+static ConvSel conv_select(int B, int C, int O, int H, int W, int epi, bool may_split)
+{
+    ConvSel s;
+    s.small = conv_small(B, O, H, W);
+    s.tiles_w = orn_cdiv(W, CV_TW);
+    s.tiles_h = orn_cdiv(H, s.small ? 2 : CV_TH);
+    s.split = false; s.nsplit = 1; s.c_per_split = C;
+    s.tail32 = false; s.n64 = orn_cdiv(O, CV_BO);
+    const int ns = (epi == EPI_PLAIN && may_split) ? orn_conv3x3_f32_nsplit(B, C, O, H, W) : 1;
+    if (ns > 1) {
+        s.split = true;
+        s.c_per_split = orn_cdiv(orn_cdiv(C, ns), CV_CC) * CV_CC;
+        s.nsplit = orn_cdiv(C, s.c_per_split);
+        return s;
+    }
+    if (!s.small && epi == EPI_PLAIN && O % CV_BO == 32) {
+        // whole 64-channel tiles, then the last 32 channels on a 32-channel tile
+        s.tail32 = true;
+        s.n64 = O / CV_BO;
+    }
+    return s;
+}
+
 int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, int B, int C, int O, int H, int W,
                            int s, int epi, float *z, float *out, hipStream_t st, float *split_ws)
 {
     ConvP p;
     p.x = x; p.w = w; p.bias = bias; p.out = out; p.z = z;
     p.B = B; p.C = C; p.O = O; p.H = H; p.W = W; p.s = s;
-    const bool small = conv_small(B, O, H, W);
-    p.tiles_w = orn_cdiv(W, CV_TW);
-    p.tiles_h = orn_cdiv(H, small ? 2 : CV_TH);
-    p.nsplit = 1; p.c_per_split = C; p.o_first = 0;
-    if (epi == EPI_PLAIN && split_ws && !bias) {
-        const int ns = orn_conv3x3_f32_nsplit(B, C, O, H, W);
-        if (ns > 1) {
-            p.c_per_split = orn_cdiv(orn_cdiv(C, ns), CV_CC) * CV_CC;
-            p.nsplit = orn_cdiv(C, p.c_per_split);
-            p.out = split_ws;
-            dim3 grid(p.tiles_w * p.tiles_h, orn_cdiv(O, CV_BO), B * p.nsplit);
-            if (small) hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0>), grid, dim3(256), 0, st, p);
-            ORN_LAUNCH_CHECK("conv3x3_f32(split)");
-            const size_t n = (size_t)B * O * H * W;
-            return orn_launch_reduce_rows(split_ws, p.nsplit, n, n, out, st);
-        }
+    const ConvSel sel = conv_select(B, C, O, H, W, epi, split_ws && !bias);
+    const bool small = sel.small;
+    p.tiles_w = sel.tiles_w;
+    p.tiles_h = sel.tiles_h;
+    p.nsplit = sel.nsplit; p.c_per_split = sel.c_per_split; p.o_first = 0;
+    if (sel.split) {
+        p.out = split_ws;
+        dim3 grid(p.tiles_w * p.tiles_h, sel.n64, B * p.nsplit);
+        if (small) hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 1>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0>), grid, dim3(256), 0, st, p);
+        ORN_LAUNCH_CHECK("conv3x3_f32(split)");
+        const size_t n = (size_t)B * O * H * W;
+        return orn_launch_reduce_rows(split_ws, p.nsplit, n, n, out, st);
     }
-    if (!small && epi == EPI_PLAIN && O % CV_BO == 32) {
-        // whole 64-channel tiles, then the last 32 channels on a 32-channel tile
-        if (O >= CV_BO) {
-            hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0, 2>), dim3(p.tiles_w * p.tiles_h, O / CV_BO, B), dim3(256), 0, st, p);
+    if (sel.tail32) {
+        if (sel.n64) {
+            hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0, 2>), dim3(p.tiles_w * p.tiles_h, sel.n64, B), dim3(256), 0, st, p);
             ORN_LAUNCH_CHECK("conv3x3_f32");
         }
-        p.o_first = O / CV_BO * CV_BO;
+        p.o_first = sel.n64 * CV_BO;
         hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0, 1>), dim3(p.tiles_w * p.tiles_h, 1, B), dim3(256), 0, st, p);
         ORN_LAUNCH_CHECK("conv3x3_f32(32)");
         return 0;
     }
-    dim3 grid(p.tiles_w * p.tiles_h, orn_cdiv(O, CV_BO), B);
+    dim3 grid(p.tiles_w * p.tiles_h, sel.n64, B);
     if (epi == EPI_PS_SILU) {
         if (small) hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 1>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 0>), grid, dim3(256), 0, st, p);
@@ -704,23 +731,35 @@ static bool wgrad_v2_ok(int C, int O)
     return O % W2F_BO == 0 && C % W2F_CN == 0;
 }
 
-static int wgrad_split(int B, int C, int O, int H, int W)
+// The wgrad launch of a shape: form, K tiles, split-K slabs and work items -- the one copy (the launcher, the workspace size and
+// orn_debug_conv_f32_plan).
+struct WgradGeo { int form, tiles_w, tiles_h, n_ktiles, S, n_ntiles, n_otiles, n_items, items_per_xcd; };
+static WgradGeo wgrad_geo(int B, int C, int O, int H, int W)
 {
+    WgradGeo g;
+    int S;
     if (wgrad_v2_ok(C, O)) {
-        const int n_ktiles = B * orn_cdiv(H, W2F_TH) * orn_cdiv(W, W2F_TW);
-        const int tiles = (O / W2F_BO) * (C / W2F_CN);
+        g.form = 2;
+        g.tiles_w = orn_cdiv(W, W2F_TW); g.tiles_h = orn_cdiv(H, W2F_TH);
+        g.n_ntiles = C / W2F_CN; g.n_otiles = O / W2F_BO;
+        g.n_ktiles = B * g.tiles_w * g.tiles_h;
         constexpr int WGS = 512;                           // one full round of two work-groups per CU
-        int S = WGS / tiles;
-        if (S > n_ktiles) S = n_ktiles;
-        return S < 1 ? 1 : S;
+        S = WGS / (g.n_otiles * g.n_ntiles);
+    } else {
+        g.form = 1;
+        g.tiles_w = orn_cdiv(W, WG_TW); g.tiles_h = orn_cdiv(H, WG_TH);
+        g.n_ntiles = orn_cdiv(C * 9, WG_BN); g.n_otiles = orn_cdiv(O, WG_BO);
+        g.n_ktiles = B * g.tiles_w * g.tiles_h;
+        S = orn_cdiv(1024, g.n_otiles * g.n_ntiles);
     }
-    const int n_ktiles = B * orn_cdiv(H, WG_TH) * orn_cdiv(W, WG_TW);
-    const int tiles = orn_cdiv(O, WG_BO) * orn_cdiv(C * 9, WG_BN);
-    int S = orn_cdiv(1024, tiles);
-    if (S > n_ktiles) S = n_ktiles;
-    if (S < 1) S = 1;
-    return S;
+    if (S > g.n_ktiles) S = g.n_ktiles;
+    g.S = S < 1 ? 1 : S;
+    g.n_items = g.n_otiles * g.n_ntiles * g.S;
+    g.items_per_xcd = orn_cdiv(g.n_items, 8);
+    return g;
 }
+
+static int wgrad_split(int B, int C, int O, int H, int W) { return wgrad_geo(B, C, O, H, W).S; }
 
 static int dbp_rows(int H, int W)
 {
@@ -747,7 +786,7 @@ int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, con
 {
     const size_t HW = (size_t)H * W;
     const int chunks = orn_cdiv((long)HW, DY_PPB);
-    const int S = wgrad_split(B, C, O, H, W);
+    const int S = wgrad_geo(B, C, O, H, W).S;
     float *dy = ws;
     float *wd = dy + orn_align((size_t)B * O * HW * 4) / 4;
     float *slabs = wd + orn_align((size_t)O * C * 9 * 4) / 4;
@@ -772,25 +811,19 @@ int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, con
     WgradP p;
     p.x = x; p.dy = dy; p.partial = slabs;
     p.B = B; p.C = C; p.O = O; p.H = H; p.W = W;
-    if (wgrad_v2_ok(C, O)) {
-        p.tiles_w = orn_cdiv(W, W2F_TW); p.tiles_h = orn_cdiv(H, W2F_TH);
-        p.n_ktiles = B * p.tiles_w * p.tiles_h;
-        p.S = S;
-        p.n_ntiles = C / W2F_CN; p.n_otiles = O / W2F_BO;
-        p.n_items = p.n_otiles * p.n_ntiles * S;
-        p.items_per_xcd = orn_cdiv(p.n_items, 8);
+    const WgradGeo g = wgrad_geo(B, C, O, H, W);
+    p.tiles_w = g.tiles_w; p.tiles_h = g.tiles_h;
+    p.n_ktiles = g.n_ktiles;
+    p.S = g.S;
+    p.n_ntiles = g.n_ntiles; p.n_otiles = g.n_otiles;
+    p.n_items = g.n_items;
+    p.items_per_xcd = g.items_per_xcd;
+    if (g.form == 2) {
         hipLaunchKernelGGL(k_wgrad_f32_v2, dim3(p.items_per_xcd * 8), dim3(256), 0, st, p);
         ORN_LAUNCH_CHECK("wgrad_f32_v2");
     } else {
-    p.tiles_w = orn_cdiv(W, WG_TW); p.tiles_h = orn_cdiv(H, WG_TH);
-    p.n_ktiles = B * p.tiles_w * p.tiles_h;
-    p.S = S;
-    p.n_ntiles = orn_cdiv(C * 9, WG_BN);
-    p.n_otiles = orn_cdiv(O, WG_BO);
-    p.n_items = p.n_otiles * p.n_ntiles * S;
-    p.items_per_xcd = orn_cdiv(p.n_items, 8);
-    hipLaunchKernelGGL(k_wgrad_f32, dim3(p.items_per_xcd * 8), dim3(256), 0, st, p);
-    ORN_LAUNCH_CHECK("wgrad_f32");
+        hipLaunchKernelGGL(k_wgrad_f32, dim3(p.items_per_xcd * 8), dim3(256), 0, st, p);
+        ORN_LAUNCH_CHECK("wgrad_f32");
     }
     ORN_TRY(orn_launch_reduce_rows(slabs, S, (size_t)O * C * 9, (size_t)O * C * 9, dwf, st));
 
@@ -814,4 +847,87 @@ extern "C" int orn_conv3x3_ps_silu_bwd(const float *x, const float *wf, const fl
         return ORN_E_WS;
     }
     return orn_launch_conv_bwd_f32(x, wf, z, da, B, C, O, H, W, s, dx, dwf, dbf, (float *)ws, (hipStream_t)stream);
+}
+
+// ================================================================================================
+// Test entry points (include/orn_debug.h): what the launchers above select, and the forms no public entry reaches
+// ================================================================================================
+static int reduce_kind(bool launched, int rows, size_t n) { return !launched ? 0 : orn_reduce_rows_is_tall(rows, n) ? 2 : 1; }
+
+extern "C" int orn_debug_conv_f32_plan(int B, int C, int O, int H, int W, int32_t *out)
+{
+    ORN_REQUIRE(out && B > 0 && C > 0 && O > 0 && H > 0 && W > 0, "debug_conv_f32_plan: bad arguments");
+    const size_t HW = (size_t)H * W;
+    const ConvSel f = conv_select(B, C, O, H, W, EPI_PS_SILU, false);
+    out[0] = f.small;
+    out[1] = f.tiles_w * f.tiles_h * f.n64 * B;
+    // dgrad: conv(dy, Wd), C_in = O, O_out = C, with the channel-split workspace and no bias (orn_launch_conv_bwd_f32)
+    const ConvSel d = conv_select(B, O, C, H, W, EPI_PLAIN, true);
+    out[2] = d.small;
+    out[3] = d.nsplit;
+    out[4] = d.c_per_split;
+    out[5] = d.n64 > 0;
+    out[6] = d.tail32;
+    out[7] = reduce_kind(d.split, d.nsplit, (size_t)B * C * HW);
+    out[8] = d.tiles_w * d.tiles_h * (d.n64 + d.tail32) * B * d.nsplit;
+    const WgradGeo g = wgrad_geo(B, C, O, H, W);
+    out[9] = g.form;
+    out[10] = g.S;
+    out[11] = g.n_ktiles;
+    out[12] = g.n_items;
+    out[13] = reduce_kind(true, g.S, (size_t)O * C * 9);
+    // conv dbias partial rows: k_silu_bwd_unshuffle's chunks, and the fused head backward's work-groups (B == 1)
+    out[14] = B * orn_cdiv((long)HW, DY_PPB);
+    out[15] = reduce_kind(true, out[14], (size_t)O);
+    out[16] = orn_head_bwd_fused_f32_blocks(H, W);
+    out[17] = reduce_kind(true, out[16], (size_t)O);
+    return 0;
+}
+
+extern "C" int orn_debug_conv_fwd_f32(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
+                                      float *z, float *a, void *stream)
+{
+    ORN_REQUIRE(x && wf && (z || a), "debug_conv_fwd_f32: null pointer");
+    ORN_REQUIRE(B > 0 && C > 0 && O > 0 && H > 0 && W > 0 && s > 0, "debug_conv_fwd_f32: bad sizes");
+    ORN_REQUIRE(O % (s * s) == 0, "debug_conv_fwd_f32: O=%d not divisible by s*s=%d", O, s * s);
+    return orn_launch_conv3x3_f32(x, wf, bf, B, C, O, H, W, s, EPI_PS_SILU, z, a, (hipStream_t)stream, nullptr);
+}
+
+// workspace of orn_debug_conv_bwd_f32_head: the conv backward's, the head's partials, the pre-flipped kernel
+static size_t head_dbg_hws_bytes(int O, int H, int W)
+{
+    return orn_align((size_t)(orn_head_bwd_fused_f32_blocks(H, W) + 1) * (3 * (size_t)(O / 4) + 3) * 4);
+}
+
+extern "C" size_t orn_debug_conv_bwd_f32_head_ws_bytes(int C, int O, int H, int W)
+{
+    if (C <= 0 || O <= 0 || H <= 0 || W <= 0 || O % 4) return 0;
+    return orn_align(orn_conv3x3_ps_silu_bwd_ws_bytes(1, C, O, H, W)) + head_dbg_hws_bytes(O, H, W) + orn_align((size_t)O * C * 9 * 4);
+}
+
+extern "C" int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
+                                           const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
+                                           float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
+                                           void *stream)
+{
+    ORN_REQUIRE(x && wf && z && head_w && head_out && head_dout && dwf && dbf && head_dw && head_db && ws,
+                "debug_conv_bwd_f32_head: null pointer");
+    ORN_REQUIRE(C > 0 && O > 0 && H > 0 && W > 0 && O % 4 == 0, "debug_conv_bwd_f32_head: bad sizes");
+    ORN_REQUIRE(O / 4 <= 512, "debug_conv_bwd_f32_head: Cn=%d > 512 unsupported", O / 4);     // (the head kernels' LDS copy of w)
+    ORN_REQUIRE(((uintptr_t)ws & 3) == 0, "debug_conv_bwd_f32_head: workspace not 4-byte aligned");
+    if (ws_bytes < orn_debug_conv_bwd_f32_head_ws_bytes(C, O, H, W)) {
+        orn_set_error("debug_conv_bwd_f32_head: workspace %zu < %zu", ws_bytes, orn_debug_conv_bwd_f32_head_ws_bytes(C, O, H, W));
+        return ORN_E_WS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float *cws = (float *)ws;
+    float *hws = cws + orn_align(orn_conv3x3_ps_silu_bwd_ws_bytes(1, C, O, H, W)) / 4;
+    float *wd = hws + head_dbg_hws_bytes(O, H, W) / 4;
+    const OrnHeadBwdFuse hf = {head_w, head_out, head_dout, sigmoid, head_dw, head_db, hws};
+    if (preflip && dx) {
+        const float *wfs[1] = {wf};
+        float *wds[1] = {wd};
+        ORN_TRY(orn_launch_flip_transpose_all(1, wfs, wds, &O, &C, st));
+    }
+    return orn_launch_conv_bwd_f32(x, wf, z, nullptr, 1, C, O, H, W, 2, dx, dwf, dbf, cws, st, &hf, (preflip && dx) ? wd : nullptr);
 }

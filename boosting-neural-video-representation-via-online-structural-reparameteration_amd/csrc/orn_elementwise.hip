@@ -70,10 +70,13 @@ __global__ void __launch_bounds__(1024) k_reduce_rows_tall(const float *__restri
     if (ry == 0 && j < n) out[j] = (sm[0][cx] + sm[8][cx]) + (sm[16][cx] + sm[24][cx]);
 }
 
+// many rows, few columns: k_reduce_rows_tall (the one copy of the choice: the launcher below and orn_debug_conv_f32_plan)
+bool orn_reduce_rows_is_tall(int rows, size_t n) { return rows >= 32 && n <= 65536; }
+
 int orn_launch_reduce_rows(const float *in, int rows, size_t ld, size_t n, float *out, hipStream_t st)
 {
     if (n == 0) return 0;
-    if (rows >= 32 && n <= 65536) {
+    if (orn_reduce_rows_is_tall(rows, n)) {
         hipLaunchKernelGGL(k_reduce_rows_tall, dim3(orn_cdiv((long)n, 32)), dim3(1024), 0, st, in, rows, ld, n, out);
         ORN_LAUNCH_CHECK("reduce_rows_tall");
         return 0;
@@ -379,6 +382,13 @@ extern "C" int orn_head_fwd(const float *a, const float *w, const float *b, int 
 {
     ORN_REQUIRE(a && w && b && out && B > 0 && C > 0 && H > 0 && W > 0, "head_fwd: bad arguments");
     return orn_launch_head_fwd(a, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, false);
+}
+
+extern "C" int orn_debug_head_fwd_z(const float *z, const float *w, const float *b, int B, int C, int H, int W, int sigmoid,
+                                    float *out, void *stream)
+{
+    ORN_REQUIRE(z && w && b && out && B > 0 && C > 0 && H > 0 && W > 0, "debug_head_fwd_z: bad arguments");
+    return orn_launch_head_fwd(z, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, true);
 }
 
 // Backward.  Block = 256 threads x PPT pixels of one batch item.  du kept in registers; per channel c:

@@ -2,7 +2,8 @@
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
  * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
  * the merge backward's (tests/test_gpu_merge16.py), the fused first block's and the slab-summing stem backward's
- * (tests/test_gpu_stage0.py) and the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py). */
+ * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py) and the fp32 conv path's
+ * (tests/test_gpu_conv32_forms.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -139,6 +140,45 @@ ORN_API int orn_debug_side_head_bwd_f16(const void *z, const float *w, const flo
                                         size_t ws_bytes, void *stream);
 ORN_API int orn_debug_side_head_bwd_f32(const float *a, const float *w, const float *out, const float *dout, int C, int H, int W,
                                         int sigmoid, float lw, float *da, float *dw, float *db, void *ws, size_t ws_bytes, void *stream);
+/* The fp32 block path (orn_conv_f32.hip) and the fp32 engine's fused head backward (k_head_bwd_fused_f32, orn_elementwise.hip):
+ * which kernel form the launchers pick for a shape, and the forms no public entry reaches.  tests/test_conv32_plan_host.py pins
+ * the selection, tests/test_gpu_conv32_forms.py every form elementwise to fp64.  x [B][C][H][W], wf [O][C][3][3], bf [O],
+ * z / a [B][O/s^2][H s][W s] (fp32 NCHW, device).  Every entry returns ORN_E_ARG with a message for arguments it declines (a null
+ * pointer, a size below 1, O not a multiple of s^2) and launches nothing then.
+ *   conv_f32_plan: no GPU is touched.  out[18] (host), from the selection functions the launchers themselves call, for the block
+ *          (B, C, O, H, W):
+ *            forward (orn_conv3x3_ps_silu_fwd)  0: 1 = 2-row tiles (fewer than 256 work-groups on 8-row tiles), 0 = 8-row tiles;
+ *                   1: work-groups of the launch.
+ *            dgrad = conv(dy, Wd) with C_in = O, O_out = C (orn_conv3x3_ps_silu_bwd)  2: 2-row tiles; 3: nsplit, the partial
+ *                   slabs the input channels are split over (1: none); 4: input channels per split; 5: 1 = a launch on 64-channel
+ *                   tiles happens; 6: 1 = the launch of the last 32 output channels on a 32-channel tile happens (8-row tiles,
+ *                   O_out % 64 == 32, unsplit); 7: reduction of the slabs, 0 = none, 1 = k_reduce_rows, 2 = k_reduce_rows_tall;
+ *                   8: work-groups of all its conv launches.
+ *            wgrad  9: form, 1 = k_wgrad_f32, 2 = k_wgrad_f32_v2 (O % 128 == 0 and C % 32 == 0); 10: S, the split-K slabs;
+ *                   11: K tiles (4 x 32 pixels, form 2: 1 x 32); 12: work items (S x o tiles x n tiles); 13: reduction of the
+ *                   slabs, 1 or 2 as above.
+ *            conv dbias  14: rows of partials k_silu_bwd_unshuffle writes (B x chunks of 2048 pixels); 15: their reduction;
+ *                   16: rows the fused head backward writes instead (B == 1: work-groups of 512 pixels); 17: their reduction.
+ *   conv_fwd_f32: orn_conv3x3_ps_silu_fwd with either output optional: z == NULL or a == NULL (not both); a == NULL is the engine's
+ *          z-only form of the last block.
+ *   head_fwd_z: orn_head_fwd on the pre-activation: out = act(W SiLU(z) + b), SiLU formed in the kernel; z [B][C][H][W], C <= 512.
+ *   conv_bwd_f32_head: orn_conv3x3_ps_silu_bwd at B = 1, s = 2 with the head's backward fused in front, as the fp32 engine runs
+ *          its last block: instead of da it takes the head's w [3][O/4], out and dout [3][2H][2W]; du = dout * act'(out),
+ *          dy = unshuffle((W^T du) * SiLU'(z)).  dx (optional) [C][H][W], dwf, dbf as orn_conv3x3_ps_silu_bwd; head_dw [3][O/4] =
+ *          sum du SiLU(z), head_db [3] = sum du: overwritten, fixed summation order.  preflip != 0: the dgrad's flipped kernel is
+ *          made first by the engine's all-layers launch (orn_launch_flip_transpose_all, one layer) in a region of ws of its own and
+ *          handed over ready-made; same bits as preflip == 0.  O % 4 == 0, O / 4 <= 512.  ws: 4-byte aligned,
+ *          orn_debug_conv_bwd_f32_head_ws_bytes(C, O, H, W) bytes (0 for sizes without a meaning); ORN_E_WS below that. */
+ORN_API int orn_debug_conv_f32_plan(int B, int C, int O, int H, int W, int32_t *out);
+ORN_API int orn_debug_conv_fwd_f32(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
+                                   float *z, float *a, void *stream);
+ORN_API int orn_debug_head_fwd_z(const float *z, const float *w, const float *b, int B, int C, int H, int W, int sigmoid, float *out,
+                                 void *stream);
+ORN_API size_t orn_debug_conv_bwd_f32_head_ws_bytes(int C, int O, int H, int W);
+ORN_API int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
+                                        const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
+                                        float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
+                                        void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
