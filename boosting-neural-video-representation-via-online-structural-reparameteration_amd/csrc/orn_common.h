@@ -45,7 +45,7 @@ void orn_set_error(const char *fmt, ...);
     } while (0)
 
 // Wave priority of the kernels on the caller's stream that run beside the side branch's full-chip weight-gradient launch in the
-// pipelined step (orn_engine.hip): where a SIMD hosts a wave of each, this one issues first -- the caller's stream is the critical
+// pipelined step (orn_engine_step.hip): where a SIMD hosts a wave of each, this one issues first -- the caller's stream is the critical
 // path, the side branch has slack (same box, 720p step: 1.045 -> 1.036 ms).  Alone on the chip (serial steps) it changes nothing.
 #ifdef ORN_PRIO_LEVEL      /* tools/probes: tagged builds with another level (0: none) */
 #define ORN_PRIO_HIGH() __builtin_amdgcn_s_setprio(ORN_PRIO_LEVEL)

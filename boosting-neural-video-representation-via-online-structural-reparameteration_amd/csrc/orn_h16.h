@@ -185,5 +185,10 @@ int orn_launch_head_finish_bf16(const float *partial, int blocks, int C, float g
 void set_debug_wgrad(int flags);
 // orn_decode_out.hip
 int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
+// orn_side_head.hip
+int orn_launch_side_head_fwd_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
+                                 OrnScaleState *sc);
+int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
+                                 int sp, float lw, float gs, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
 
 }  // namespace HNS

@@ -123,19 +123,11 @@ int orn_head_bwd_fused_f32_blocks(int H, int W);
 int orn_launch_head_bwd_fused_f32(const float *z, const float *w, const float *out, const float *dout, int Cn, int H, int W,
                                   int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st);
 
-// orn_side_head.hip: the heads of the stages below the last one (multi-resolution engine; include/orn.h, N8).  16-bit entries: z is
-// the block's channels-last pre-activation, dypad its padded un-shuffled gradient buffer, which the backward ADDS to; fp32 entries:
-// the NCHW activation and the gradient with respect to it.  sc: the step's scale-state entry (the scale is read from it, a
-// non-finite pre-activation / dw / db raises its flag).  ws: orn_side_head_bwd_ws_floats floats.
+// orn_side_head.hip: the heads of the stages below the last one (multi-resolution engine; include/orn.h, N8).  16-bit entries
+// (OrnHalfOps::side_head_fwd / _bwd): z is the block's channels-last pre-activation, dypad its padded un-shuffled gradient buffer,
+// which the backward ADDS to; fp32 entries: the NCHW activation and the gradient with respect to it.  sc: the step's scale-state
+// entry (the scale is read from it, a non-finite pre-activation / dw / db raises its flag).  ws: orn_side_head_bwd_ws_floats floats.
 size_t orn_side_head_bwd_ws_floats(int C, int H, int W);
-int orn_launch_side_head_fwd_bf16(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
-                                  OrnScaleState *sc);
-int orn_launch_side_head_fwd_f16(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
-                                 OrnScaleState *sc);
-int orn_launch_side_head_bwd_bf16(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
-                                  int sp, float lw, float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
-int orn_launch_side_head_bwd_f16(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
-                                 int sp, float lw, float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
 int orn_launch_side_head_fwd_f32(const float *a, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
                                  OrnScaleState *sc);
 int orn_launch_side_head_bwd_f32(const float *a, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
@@ -251,6 +243,10 @@ struct OrnHalfOps {
                     const OrnLossFinalJob *fin);   // sc: gs from the device state; fin (optional): the loss's finalize stage as one more work-group
     // decode: head forward on z + the output stage above in one kernel (same per-pixel arithmetic as head_fwd)
     int (*decode_out)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
+    // multi-resolution engine: the head of a stage below the last (orn_side_head.hip, above)
+    int (*side_head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc);
+    int (*side_head_bwd)(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp, float lw,
+                         float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
 };
 const OrnHalfOps *orn_half_ops_bf16();
 const OrnHalfOps *orn_half_ops_f16();

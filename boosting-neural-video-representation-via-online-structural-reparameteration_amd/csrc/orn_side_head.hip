@@ -399,25 +399,13 @@ int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out,
 
 }  // namespace HNS
 
-// ---- the engine's type-erased launchers (orn_internal.h) and the test entry points (include/orn_debug.h), one set per element type ----
+// ---- the test entry points (include/orn_debug.h), one set per element type; the engine reaches the launchers above through
+// OrnHalfOps (orn_ops_bf16.hip) ----
 #ifdef ORN_FP16
 #define HOOK(bf16_, f16_) f16_
 #else
 #define HOOK(bf16_, f16_) bf16_
 #endif
-
-int HOOK(orn_launch_side_head_fwd_bf16, orn_launch_side_head_fwd_f16)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid,
-                                                                      float *out, hipStream_t st, OrnScaleState *sc)
-{
-    return HNS::orn_launch_side_head_fwd_h16((const h16 *)z, w, b, C, HW, sigmoid, out, st, sc);
-}
-
-int HOOK(orn_launch_side_head_bwd_bf16, orn_launch_side_head_bwd_f16)(const void *z, const float *w, const float *out, const float *dout, int C,
-                                                                      int H, int W, int sigmoid, int sp, float lw, float gs, void *dypad,
-                                                                      float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc)
-{
-    return HNS::orn_launch_side_head_bwd_h16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, (h16 *)dypad, dw, db, ws, st, sc);
-}
 
 extern "C" int HOOK(orn_debug_side_head_fwd_bf16, orn_debug_side_head_fwd_f16)(const void *z, const float *w, const float *b, int C, int H, int W,
                                                                                int sigmoid, float *out, void *stream)

@@ -10,6 +10,7 @@ enqueued without a host sync -- as plain stream launches pipelined over the engi
 A loss the library does not build trains through the split step (`step_with` / `run_with`): the engine's
 forward, a torch function of its output on the caller's stream, the engine's backward and Adam.
 """
+import contextlib
 import ctypes
 from ctypes import byref, c_int32, c_size_t, c_void_p
 from typing import List, Optional, Sequence, Tuple
@@ -51,6 +52,15 @@ def arena_layout(named_shapes: Sequence[Tuple[str, Tuple[int, ...]]]):
     return out, off
 
 
+def stage_hw(model) -> List[Tuple[int, int]]:
+    """Image size of every stage of `model`; the last is the decoder's output."""
+    H, W, out = model.fc_h, model.fc_w, []
+    for blk in model.layers:
+        H, W = H * blk.stride, W * blk.stride
+        out.append((H, W))
+    return out
+
+
 def is_multi_res(model) -> bool:
     """A head on every stage (Generator(sin_res=False), model.py:597-625), not on the last alone."""
     return len(model.head_layers) > 1 and all(h is not None for h in model.head_layers)
@@ -82,10 +92,10 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
         d.multi_res, d.lw = 1, lw
         for i in range(n_layers - 1):
             d.side_head_w[i], d.side_head_b[i] = layout[f'head_layers.{i}.weight'][0], layout[f'head_layers.{i}.bias'][0]
-    H, W = model.fc_h, model.fc_w
+    in_hw = [(model.fc_h, model.fc_w)] + stage_hw(model)      # a block's input: the stage below it
     for i, blk in enumerate(model.layers):
         L = d.layer[i]
-        L.C, L.O, L.s, L.H, L.W = blk.ngf, blk.out_channels, blk.stride, H, W
+        L.C, L.O, L.s, (L.H, L.W) = blk.ngf, blk.out_channels, blk.stride, in_hw[i]
         for f in ('w3x3', 'b3x3', 'w3x1', 'b3x1', 'w1x3', 'b1x3', 'w1', 'w2', 'w3'):
             setattr(L, f, -1)
         X = d.branch[i]
@@ -105,7 +115,6 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
                 setattr(X, f[2:], layout[name][0])
             else:
                 setattr(L, f, layout[name][0])
-        H, W = H * blk.stride, W * blk.stride
     return d
 
 
@@ -119,18 +128,51 @@ def make_schedule(entries: Sequence[Tuple[int, int, float]]) -> np.ndarray:
     return arr
 
 
-def _out_hw(model):
-    Hs, Ws = model.fc_h, model.fc_w
-    for blk in model.layers:
-        Hs, Ws = Hs * blk.stride, Ws * blk.stride
-    return Hs, Ws
-
-
 class _Decoding:
-    """Forward-only entry points of an engine handle (`_h`, `device`, `out_hw`, `desc`; `frames` / `embeds` when a video is
-    resident): shared by TrainEngine and the decode-only Decoder."""
+    """Construction and the forward-only entry points of an engine handle (`_h`, `device`, `out_hw`, `desc`; `frames` / `embeds`
+    when a video is resident): shared by TrainEngine and the decode-only Decoder."""
     frames = None
     embeds = None
+
+    def _rehome(self, model, device, grads: bool):
+        """The module's parameters become views into one flat arena, `params` (so the module and the engine share the memory), and
+        with `grads` their .grad views into a second one."""
+        if not torch.cuda.is_available():
+            raise OrnError(f'{type(self).__name__} needs a GPU: there is no CPU path')
+        self.device = torch.device(device or f'cuda:{torch.cuda.current_device()}')
+        self.model = model
+        self.layout, self.n_params = arena_layout([(k, tuple(p.shape)) for k, p in model.named_parameters()])
+        self.params = torch.zeros(self.n_params, device=self.device)
+        if grads:
+            self.grads = torch.zeros(self.n_params, device=self.device)
+        with torch.no_grad():
+            for k, p in model.named_parameters():
+                off, n = self.layout[k]
+                view = self.params[off:off + n].view(p.shape)
+                view.copy_(p.detach().to(self.device))
+                p.data = view
+                if grads:
+                    p.grad = self.grads[off:off + n].view(p.shape)
+
+    def _create(self, precision: str, train: bool, *desc_args, **desc_kw):
+        """The engine of build_desc(model, ..): its zeroed workspace and, for training, the Adam arenas beside `grads`."""
+        self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
+        self.desc = build_desc(self.model, self.layout, self.n_params, *desc_args, precision=self.precision, **desc_kw)
+        nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
+        if nbytes == 0:
+            raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        if train:
+            self.adam_m, self.adam_v = (torch.zeros(self.n_params, device=self.device) for _ in range(2))
+        arenas = (self.grads, self.adam_m, self.adam_v) if train else (None, None, None)
+        self._h = c_void_p()
+        check(lib().orn_engine_create(byref(self.desc), _lib.ptr(self.params), *(_lib.ptr(t) for t in arenas), _lib.ptr(self.ws),
+                                      c_size_t(nbytes), byref(self._h)), 'orn_engine_create')
+        self.out_hw = self.stage_hw()[-1]
+
+    def stage_hw(self) -> List[Tuple[int, int]]:
+        """Image size of every stage, the last included."""
+        return stage_hw(self.model)
 
     def decode(self, embed: torch.Tensor) -> torch.Tensor:
         """Forward only: embed [E] or [1,E] -> image [1,3,H,W]."""
@@ -237,30 +279,9 @@ class Decoder(_Decoding):
     precision was evaluated with); 'fp32' is the reference's."""
 
     def __init__(self, model, precision: str = 'fp16', device: Optional[torch.device] = None):
-        if not torch.cuda.is_available():
-            raise OrnError('Decoder needs a GPU: there is no CPU path')
-        self.device = torch.device(device or f'cuda:{torch.cuda.current_device()}')
-        self.model = model
-        named = [(k, tuple(p.shape)) for k, p in model.named_parameters()]
-        self.layout, self.n_params = arena_layout(named)
-        self.params = torch.zeros(self.n_params, device=self.device)
-        with torch.no_grad():
-            for k, p in model.named_parameters():
-                off, n = self.layout[k]
-                view = self.params[off:off + n].view(p.shape)
-                view.copy_(p.detach().to(self.device))
-                p.data = view                                   # the module and the engine share the arena
-        self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
+        self._rehome(model, device, grads=False)
         # (a multi-resolution model decodes its last stage: the single-resolution engine on the tensors the two share)
-        self.desc = build_desc(model, self.layout, self.n_params, 'L2', 0.5, 0.999, 1e-8, self.precision, multi_res=False)
-        nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
-        if nbytes == 0:
-            raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
-        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self._h = c_void_p()
-        check(lib().orn_engine_create(byref(self.desc), _lib.ptr(self.params), None, None, None, _lib.ptr(self.ws), c_size_t(nbytes),
-                                      byref(self._h)), 'orn_engine_create')
-        self.out_hw = _out_hw(model)
+        self._create(precision, False, 'L2', multi_res=False)
 
 
 class TrainEngine(_Decoding):
@@ -268,36 +289,11 @@ class TrainEngine(_Decoding):
 
     def __init__(self, model, loss_type: str = 'Fusion6', beta: float = 0.5, precision: str = 'fp32',
                  device: Optional[torch.device] = None, n_slots: int = 4096, target_cache: bool = True, lw: float = 1.0):
-        if not torch.cuda.is_available():
-            raise OrnError('TrainEngine needs a GPU: there is no CPU path')
-        self.device = torch.device(device or f'cuda:{torch.cuda.current_device()}')
-        self.model = model
-        named = [(k, tuple(p.shape)) for k, p in model.named_parameters()]
-        self.layout, self.n_params = arena_layout(named)
+        self._rehome(model, device, grads=True)                # parameters now live in the arena, their grads in the grad arena
         dev = self.device
-        self.params = torch.zeros(self.n_params, device=dev)
-        self.grads = torch.zeros(self.n_params, device=dev)
-        self.adam_m = torch.zeros(self.n_params, device=dev)
-        self.adam_v = torch.zeros(self.n_params, device=dev)
-        with torch.no_grad():
-            for k, p in model.named_parameters():
-                off, n = self.layout[k]
-                view = self.params[off:off + n].view(p.shape)
-                view.copy_(p.detach().to(dev))
-                p.data = view                                   # parameters now live in the arena
-                p.grad = self.grads[off:off + n].view(p.shape)  # and their grads in the grad arena
-        self.precision = {'fp32': 0, 'bf16': 1, 'fp16': 2}[precision]
         # a model with a head on every stage (Generator(sin_res=False)) trains them all: sum_{i < n-1} lw * loss_i + loss_{n-1}
-        self.desc = build_desc(model, self.layout, self.n_params, loss_type, beta, 0.999, 1e-8, self.precision, lw)
+        self._create(precision, True, loss_type, beta, lw=lw)
         self.multi_res = bool(self.desc.multi_res)
-        nbytes = lib().orn_engine_ws_bytes(byref(self.desc))
-        if nbytes == 0:
-            raise OrnError('orn_engine_ws_bytes: ' + _lib.last_error())
-        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self._h = c_void_p()
-        check(lib().orn_engine_create(byref(self.desc), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.adam_m),
-                                      _lib.ptr(self.adam_v), _lib.ptr(self.ws), c_size_t(nbytes), byref(self._h)),
-              'orn_engine_create')
         self.target_cache = bool(target_cache) and _lib.loss_spec(loss_type)[1] == _lib.LOSS_KIND_SSIM
         self.tstats = None
         self.n_slots = n_slots
@@ -314,13 +310,28 @@ class TrainEngine(_Decoding):
         self._sched_host = None                            # host copy of the uploaded schedule and of the device cursor: which
         self._cursor_host = 0                              # frame the next step takes is known without a sync (step_with)
         self._sched_len = 0
+        self._batch_max = 0                                # frames the batch workspace takes (run_batched; 0: none yet)
         self.open_frame = None
         self.global_step = 0
         self.skipped_carry = 0                             # steps skipped by engines this one replaced (main_train fall-back)
-        self.out_hw = _out_hw(model)
         # HIP graphs cannot be captured on the legacy default stream: the engine runs on its own
         # stream, ordered against the caller's current stream on entry and exit.
         self.stream = torch.cuda.Stream(device=dev)
+
+    @contextlib.contextmanager
+    def _on_stream(self):
+        """Orders the engine's stream behind the caller's current one, yields its handle, then orders the caller's behind it."""
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        yield c_void_p(self.stream.cuda_stream)
+        cur.wait_stream(self.stream)
+
+    def _step_args(self):
+        """What every stepping entry takes first: the handle, the resident video, the schedule with its cursor, the stats ring."""
+        if self.frames is None or self.sched is None:
+            raise OrnError('set_video() and set_schedule() first')
+        return [self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched), _lib.ptr(self.cursor),
+                _lib.ptr(self.stats_ring), c_int32(self.n_slots)]
 
     # ---- data ---------------------------------------------------------------------------------
     def set_video(self, frames: torch.Tensor, embeds: torch.Tensor, stage_frames: Optional[Sequence[torch.Tensor]] = None):
@@ -353,14 +364,6 @@ class TrainEngine(_Decoding):
                 check(lib().orn_engine_set_target_stats(self._h, _lib.ptr(self.tstats)), 'orn_engine_set_target_stats')
         if self.multi_res:
             self._set_stage_tables(source, stage_frames)
-
-    def stage_hw(self) -> List[Tuple[int, int]]:
-        """Image size of every stage, the last included."""
-        H, W, out = self.model.fc_h, self.model.fc_w, []
-        for blk in self.model.layers:
-            H, W = H * blk.stride, W * blk.stride
-            out.append((H, W))
-        return out
 
     def _set_stage_tables(self, source: torch.Tensor, given=None):
         """The target table of every stage below the last: F.adaptive_avg_pool2d(data, out_i.shape[-2:]) of main_train.py:239, pooled
@@ -414,38 +417,27 @@ class TrainEngine(_Decoding):
             if graph:
                 raise OrnError('run: the batched step has no graph form (graph=True with batch > 1)')
             return self.run_batched(n_steps, batch)
-        if self.frames is None or self.sched is None:
-            raise OrnError('set_video() and set_schedule() first')
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        st = c_void_p(self.stream.cuda_stream)
-        if graph is None:
-            check(lib().orn_engine_train_steps(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                               _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots),
-                                               c_int32(n_steps), st), 'orn_engine_train_steps')
-        elif graph:
-            check(lib().orn_engine_train_steps_graph(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                                     _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots),
-                                                     c_int32(n_steps), st), 'orn_engine_train_steps_graph')
-        else:
-            for _ in range(n_steps):
-                check(lib().orn_engine_train_step(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                                  _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots), st),
-                      'orn_engine_train_step')
-        cur.wait_stream(self.stream)
+        args = self._step_args()
+        with self._on_stream() as st:
+            if graph is None:
+                check(lib().orn_engine_train_steps(*args, c_int32(n_steps), st), 'orn_engine_train_steps')
+            elif graph:
+                check(lib().orn_engine_train_steps_graph(*args, c_int32(n_steps), st), 'orn_engine_train_steps_graph')
+            else:
+                for _ in range(n_steps):
+                    check(lib().orn_engine_train_step(*args, st), 'orn_engine_train_step')
         self.global_step += n_steps
         self._cursor_host += n_steps
 
     def run_batched(self, n_steps: int, batch: int):
         """`n_steps` optimiser steps of `batch` frames each through orn_engine_train_steps_batch (what run() calls for batch > 1;
         batch = 1 gives the bits of the single-frame step).  The batch workspace is allocated on first use and grows with `batch`."""
-        if self.frames is None or self.sched is None:
-            raise OrnError('set_video() and set_schedule() first')
+        args = self._step_args()
         if not 1 <= batch <= _lib.ORN_MAX_BATCH:
             raise OrnError(f'run: batch={batch} outside [1, {_lib.ORN_MAX_BATCH}]')
-        if n_steps * batch > getattr(self, '_sched_len', 0):
-            raise OrnError(f'run: {n_steps} steps of {batch} frames need {n_steps * batch} schedule entries, {getattr(self, "_sched_len", 0)} uploaded')
-        if getattr(self, '_batch_max', 0) < batch:
+        if n_steps * batch > self._sched_len:
+            raise OrnError(f'run: {n_steps} steps of {batch} frames need {n_steps * batch} schedule entries, {self._sched_len} uploaded')
+        if self._batch_max < batch:
             nbytes = lib().orn_engine_batch_ws_bytes(byref(self.desc), batch)
             if nbytes == 0:
                 raise OrnError('orn_engine_batch_ws_bytes: ' + _lib.last_error())
@@ -453,13 +445,8 @@ class TrainEngine(_Decoding):
             self._batch_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             check(lib().orn_engine_set_batch_ws(self._h, _lib.ptr(self._batch_ws), c_size_t(nbytes), batch), 'orn_engine_set_batch_ws')
             self._batch_max = batch
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        check(lib().orn_engine_train_steps_batch(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                                 _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots),
-                                                 c_int32(n_steps), c_int32(batch), c_void_p(self.stream.cuda_stream)),
-              'orn_engine_train_steps_batch')
-        cur.wait_stream(self.stream)
+        with self._on_stream() as st:
+            check(lib().orn_engine_train_steps_batch(*args, c_int32(n_steps), c_int32(batch), st), 'orn_engine_train_steps_batch')
         self.global_step += n_steps
         self._cursor_host += n_steps * batch
 
@@ -472,17 +459,12 @@ class TrainEngine(_Decoding):
         if self.multi_res:
             raise OrnError('forward_step: a multi-resolution engine has no split step (a caller-supplied objective takes one image; '
                            'build the model with sin_res=True)')
-        if self.frames is None or self.sched is None:
-            raise OrnError('set_video() and set_schedule() first')
+        *args, _ring, n_slots = self._step_args()
         if self._cursor_host >= self._sched_len:
             raise OrnError(f'forward_step: the uploaded schedule ({self._sched_len} entries) is used up')
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
         pred = c_void_p()
-        check(lib().orn_engine_step_forward(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                            _lib.ptr(self.cursor), c_int32(self.n_slots), byref(pred), c_void_p(self.stream.cuda_stream)),
-              'orn_engine_step_forward')
-        cur.wait_stream(self.stream)
+        with self._on_stream() as st:
+            check(lib().orn_engine_step_forward(*args, n_slots, byref(pred), st), 'orn_engine_step_forward')
         self.open_frame = int(self._sched_host[self._cursor_host, 0])
         self._cursor_host += 1
         H, W = self.out_hw
@@ -507,12 +489,9 @@ class TrainEngine(_Decoding):
             if not isinstance(loss, torch.Tensor) or not loss.is_cuda or loss.device != self.device or loss.numel() != 1:
                 raise OrnError(f'backward_step: loss must be a one-element tensor on {self.device}')
             loss = loss.detach().to(torch.float32).reshape(1)
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        check(lib().orn_engine_step_backward(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(dpred), _lib.ptr(loss),
-                                             _lib.ptr(self.stats_ring), c_int32(self.n_slots), c_void_p(self.stream.cuda_stream)),
-              'orn_engine_step_backward')
-        cur.wait_stream(self.stream)
+        with self._on_stream() as st:
+            check(lib().orn_engine_step_backward(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(dpred), _lib.ptr(loss),
+                                                 _lib.ptr(self.stats_ring), c_int32(self.n_slots), st), 'orn_engine_step_backward')
         for t in (dpred, loss):                                 # allocated on the caller's stream, read on the engine's
             if t is not None:
                 t.record_stream(self.stream)
@@ -565,17 +544,11 @@ class TrainEngine(_Decoding):
         host lists / floats in ms: 'fwd'[i] forward conv of layer i, 'dgrad'[i] dgrad launch of layer i (fp32 mode: the
         layer's whole backward call), 'wgrad' the batched wgrad launch of the 16-bit layers, 'wgrad_reduce' its split-K
         reduction.  Consumes one schedule entry; synchronises."""
-        if self.frames is None or self.sched is None:
-            raise OrnError('set_video() and set_schedule() first')
-        import ctypes
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
+        args = self._step_args()
         n = self.desc.n_layers
         ms = (ctypes.c_float * (2 * n + 2))()
-        check(lib().orn_engine_profile_step(self._h, _lib.ptr(self.frames), _lib.ptr(self.embeds), _lib.ptr(self.sched),
-                                            _lib.ptr(self.cursor), _lib.ptr(self.stats_ring), c_int32(self.n_slots), ms,
-                                            c_void_p(self.stream.cuda_stream)), 'orn_engine_profile_step')
-        cur.wait_stream(self.stream)
+        with self._on_stream() as st:
+            check(lib().orn_engine_profile_step(*args, ms, st), 'orn_engine_profile_step')
         self.global_step += 1
         self._cursor_host += 1
         v = [float(x) for x in ms]
