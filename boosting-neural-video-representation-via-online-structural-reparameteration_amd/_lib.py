@@ -178,6 +178,13 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_side_head_bwd_bf16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, c_float, P, P, P, P, c_size_t, P]),
                'orn_debug_side_head_bwd_f16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, c_float, P, P, P, P, c_size_t, P]),
                'orn_debug_side_head_bwd_f32': (c_int, [P] * 4 + [c_int] * 4 + [c_float, P, P, P, P, c_size_t, P]),
+               'orn_debug_head16_bwd_blocks': (c_int, [c_int] * 2),
+               'orn_debug_head16_bwd_ws_bytes': (c_size_t, [c_int]),
+               'orn_debug_head16_bwd_rider_ws_bytes': (c_size_t, [c_int] * 4),
+               'orn_debug_head_fwd_bf16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
+               'orn_debug_head_fwd_f16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
+               'orn_debug_head_bwd_bf16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, P, P, P, P, c_size_t, P, P, c_int, P, P]),
+               'orn_debug_head_bwd_f16': (c_int, [P] * 4 + [c_int] * 5 + [c_float, P, P, P, P, c_size_t, P, P, c_int, P, P]),
                'orn_debug_conv_f32_plan': (c_int, [c_int] * 5 + [POINTER(c_int32)]),
                'orn_debug_conv_fwd_f32': (c_int, [P, P, P] + [c_int] * 6 + [P, P, P]),
                'orn_debug_head_fwd_z': (c_int, [P, P, P] + [c_int] * 5 + [P, P]),

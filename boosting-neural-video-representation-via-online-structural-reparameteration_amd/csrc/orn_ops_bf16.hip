@@ -543,6 +543,78 @@ extern "C" int HOOK(orn_debug_conv_dgrad_bf16, orn_debug_conv_dgrad_f16)(const v
                                       (hipStream_t)stream, c_real);
 }
 
+// The last stage's head (include/orn_debug.h): the launchers above and the two forms of the dW / db finish, as the per-op path and the
+// engine call them.  The sizes are the launchers' own functions; the un-typed ones live in the bf16 build.
+#ifdef ORN_FP16
+extern "C" size_t orn_debug_head16_bwd_ws_bytes(int C);
+extern "C" size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int loss_type);
+#else
+extern "C" int orn_debug_head16_bwd_blocks(int H, int W) { return (H >= 1 && W >= 1) ? orn_head_bwd_bf16_blocks(H, W) : 0; }
+extern "C" size_t orn_debug_head16_bwd_ws_bytes(int C)
+{
+    return (C == 32 || C == 64 || C == 96 || C == 128) ? orn_head_bwd_bf16_ws_floats(C) * sizeof(float) : 0;
+}
+extern "C" size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int loss_type)
+{
+    const size_t head = orn_debug_head16_bwd_ws_bytes(C), loss = orn_loss_ws_bytes_for(loss_type, 1, 3, H, W);
+    return head && loss ? orn_align(head) + loss : 0;
+}
+#endif
+
+extern "C" int HOOK(orn_debug_head_fwd_bf16, orn_debug_head_fwd_f16)(const void *z, const float *w, const float *b, int C, int H, int W,
+                                                                     int sigmoid, float *out, void *stream)
+{
+    ORN_REQUIRE(z && w && b && out, "head_fwd: null pointer");
+    ORN_REQUIRE(C >= 32 && H >= 1 && W >= 1, "head_fwd: bad sizes C=%d %dx%d", C, H, W);
+    return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream);
+}
+
+extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void *z, const float *w, const float *out, float *dout, int C,
+                                                                     int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
+                                                                     float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
+                                                                     int loss_type, float *stats, void *stream)
+{
+    ORN_REQUIRE(z && w && out && dout && dypad && dw && db && ws && (!target || stats), "head_bwd: null pointer");
+    const size_t head_bytes = orn_debug_head16_bwd_ws_bytes(C);
+    ORN_REQUIRE(head_bytes, "head_bwd: unsupported C=%d", C);
+    ORN_REQUIRE(H >= 1 && W >= 1 && sp >= 1 && H % sp == 0 && W % sp == 0, "head_bwd: %dx%d not divisible by the stride %d", H, W, sp);
+    ORN_REQUIRE(gs > 0.f, "head_bwd: gradient scale %g", (double)gs);
+    const size_t need = target ? orn_debug_head16_bwd_rider_ws_bytes(C, H, W, loss_type) : head_bytes;
+    ORN_REQUIRE(need, "head_bwd: loss_type %d does not take a %dx%d image", loss_type, H, W);
+    ORN_REQUIRE(!target || (uintptr_t)ws % 16 == 0, "head_bwd: the rider needs a 16-byte aligned workspace");
+    if (ws_bytes < need) { orn_set_error("head_bwd: workspace %zu < %zu", ws_bytes, need); return ORN_E_WS; }
+    hipStream_t st = (hipStream_t)stream;
+    OrnScaleState *sc = nullptr;
+    OrnScaleState s0 = {};
+    if (flag) {                                         // the engine's form: the scale lives in a state entry on the device
+        s0.gs = s0.gs_max = gs;
+        s0.inv_gs = 1.0f / gs;
+        ORN_HIP(hipMalloc(&sc, sizeof(s0)));
+        const hipError_t e = hipMemcpy(sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { orn_set_error("head_bwd: %s", hipGetErrorString(e)); (void)hipFree(sc); return (int)e; }
+    }
+    int rc = 0;
+    OrnLossFinalJob fj = {};
+    if (target)                                         // the loss writes dout and leaves its finalize stage to the head backward
+        rc = orn_launch_loss(out, target, nullptr, 0, 1, 3, H, W, loss_type, gs, stats, dout, (float *)((char *)ws + orn_align(head_bytes)), st,
+                             nullptr, nullptr, sc, nullptr, &fj);
+    if (rc == 0)
+        rc = orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs, (h16 *)dypad, flag ? nullptr : dw,
+                                      flag ? nullptr : db, (float *)ws, st, sc, target ? &fj : nullptr);
+    if (rc == 0 && flag) {
+        const OrnHeadFinish hf = {(const float *)ws, orn_head_bwd_bf16_blocks(H, W), C, 1.0f / gs, dw, db, sc};
+        rc = orn_launch_wgrad_bf16_batch(0, nullptr, st, &hf, nullptr, 0);
+    }
+    if (flag) {
+        hipError_t e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(&s0, sc, sizeof(s0), hipMemcpyDeviceToHost);
+        if (rc == 0 && e != hipSuccess) { orn_set_error("head_bwd: %s", hipGetErrorString(e)); rc = (int)e; }
+        if (rc == 0) *flag = s0.flag;
+        (void)hipFree(sc);
+    }
+    return rc;
+}
+
 }  // namespace HNS
 
 const OrnHalfOps *

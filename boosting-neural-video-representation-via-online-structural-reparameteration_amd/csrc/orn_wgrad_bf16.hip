@@ -173,6 +173,21 @@ size_t orn_wgrad_bf16_ws_floats(int H, int W, int O)
     return (size_t)(S > Smax ? S : Smax) * (9 * (size_t)O * 96 + O);
 }
 
+// Both wgrad kernels are launched with WB_LDS_BYTES of dynamic LDS: their attribute is raised once per process, before the first
+// launch of either (wgrad_fill, and the batch launch that carries riders only and fills no job).
+static int wgrad_lds_setup()
+{
+    static bool attr_done = false;
+    if (!attr_done) {
+        const size_t smem = WB_LDS_BYTES;
+        hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) { orn_set_error("wgrad_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+        attr_done = true;
+    }
+    return 0;
+}
+
 // dwf [O][C][3][3] and dbf [O] (PyTorch channel order), both overwritten.  C <= 96 real channels; xpad always has 96
 // channels per pixel (zeros above C).
 static int wgrad_fill(WgradBP &p, const h16 *xpad, const h16 *dypad, int H, int W, int C, int O, int s, float *slabs, int smax = 0)
@@ -189,15 +204,7 @@ static int wgrad_fill(WgradBP &p, const h16 *xpad, const h16 *dypad, int H, int 
     p.S = orn_wgrad_bf16_split(H, W, O, smax);
     p.bias_slabs = slabs + (size_t)p.S * 9 * O * 96;
     p.n_otiles = orn_cdiv(O, WB_BO);
-    static bool attr_done = false;
-    if (!attr_done) {
-        const size_t smem = WB_LDS_BYTES;
-        hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) { orn_set_error("wgrad_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done = true;
-    }
-    return 0;
+    return wgrad_lds_setup();
 }
 
 // slabs only (no reduction), several layers in one launch
@@ -215,6 +222,7 @@ int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, con
         total += 3 * a.p[i].n_otiles * a.p[i].S;        // S % 8 == 0: every start is a multiple of 8
     }
     a.start[n] = total;
+    if (n == 0) ORN_TRY(wgrad_lds_setup());             // riders alone: no wgrad_fill has run for this launch
     a.hf = OrnHeadFinish{};
     a.hf_blocks = 0;
     if (hf) { a.hf = *hf; a.hf_blocks = 3 * hf->C + 3; total += a.hf_blocks; }

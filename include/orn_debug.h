@@ -2,7 +2,8 @@
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
  * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
  * the merge backward's (tests/test_gpu_merge16.py), the fused first block's and the slab-summing stem backward's
- * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py) and the fp32 conv path's
+ * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py), the side heads'
+ * (tests/test_gpu_side_head.py), the last stage's 16-bit head's (tests/test_gpu_head16.py) and the fp32 conv path's
  * (tests/test_gpu_conv32_forms.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
@@ -179,6 +180,41 @@ ORN_API int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, const f
                                         const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
                                         float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
                                         void *stream);
+/* The last stage's 16-bit head (k_head_fwd_nhwc_bf16, k_head_bwd_nhwc_bf16<C / 32>, orn_ops_bf16.hip) and the reduction of its dW / db
+ * partials (head_finish_body, orn_wgrad_bf16.hip), through the launchers the engine calls; tests/test_gpu_head16.py pins them
+ * elementwise to fp64.  w [3][C], b [3], out / dout / target [3][H][W] planar fp32; sigmoid: 0 = (tanh + 1) / 2.
+ *   bwd_blocks: work-groups of the backward = rows of partials it leaves (64 pixels each, at most 512: above 512 x 64 pixels a lane
+ *          walks several pixels); bwd_ws_bytes: its workspace, (512 + 1) x (3 C + 3) floats.  No GPU is touched; 0 for sizes without a
+ *          meaning (H or W below 1; C outside {32, 64, 96, 128}).
+ *   fwd:   z [H][W][C] channels-last pre-activation (bf16 / IEEE half), C % 32 == 0, 32 <= C <= 256; out = act(W SiLU(z) + b), every
+ *          element written.  Above 8192 x 64 pixels a lane walks several pixels.
+ *   bwd:   du = dout * gs * act'(out).  dypad [H/sp + 2][W/sp + 2][C sp^2] channels-last (layout: the side head's, above); every interior
+ *          element is OVERWRITTEN with round16((W^T du)[c] * SiLU'(z)), the one-pixel ring is neither read nor written.  dw [3][C] =
+ *          sum_pixels du SiLU(z) / gs, db [3] = sum du / gs: overwritten, fixed summation order.
+ *          flag == NULL, the per-op form: gs travels by value and the reduction is a launch of its own (k_head_bf16_finish).
+ *          flag != NULL, the engine's form: gs and 1 / gs are read from a scale state of the entry's own (allocated and freed inside,
+ *          `stream` synchronised), the reduction rides on a batched weight-gradient launch without jobs; *flag: the state's flag word
+ *          after the call (1: dw or db was not finite).  Same bits in both forms.
+ *          target != NULL, the rider: orn_loss_fwd_bwd's launches on (out, target) with loss_scale = gs come first and WRITE dout; the
+ *          loss's last stage then runs as one more work-group of the head backward and leaves stats[8] (device) as orn_loss_fwd_bwd does.
+ *   ws:    4-byte aligned, orn_debug_head16_bwd_ws_bytes(C) bytes.  With a target: 16-byte aligned,
+ *          orn_debug_head16_bwd_rider_ws_bytes(C, H, W, loss_type) bytes (0 where the loss takes no such image) -- the head's part,
+ *          rounded up to a multiple of 256 bytes, then the loss's orn_loss_ws_bytes_for(loss_type, 1, 3, H, W) bytes.
+ *   Refused with ORN_E_ARG and nothing launched: a null pointer, C outside {32, 64, 96, 128}, H or W not a multiple of sp, gs <= 0;
+ *   ORN_E_WS: a workspace below the size. */
+ORN_API int orn_debug_head16_bwd_blocks(int H, int W);
+ORN_API size_t orn_debug_head16_bwd_ws_bytes(int C);
+ORN_API size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int loss_type);
+ORN_API int orn_debug_head_fwd_bf16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                    void *stream);
+ORN_API int orn_debug_head_fwd_f16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                   void *stream);
+ORN_API int orn_debug_head_bwd_bf16(const void *z, const float *w, const float *out, float *dout, int C, int H, int W, int sigmoid,
+                                    int sp, float gs, void *dypad, float *dw, float *db, void *ws, size_t ws_bytes, int *flag,
+                                    const float *target, int loss_type, float *stats, void *stream);
+ORN_API int orn_debug_head_bwd_f16(const void *z, const float *w, const float *out, float *dout, int C, int H, int W, int sigmoid,
+                                   int sp, float gs, void *dypad, float *dw, float *db, void *ws, size_t ws_bytes, int *flag,
+                                   const float *target, int loss_type, float *stats, void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);

@@ -24,6 +24,8 @@ import pytest
 import torch
 from ctypes import c_float, c_size_t
 
+from head_ref import BAND, banded, bands_intact, dsilu64, interior, silu64      # shared with test_gpu_head16.py
+
 pytestmark = pytest.mark.gpu
 
 C_FWD, C_BWD, C_DW = 2.0, 8.0, 8.0
@@ -38,7 +40,6 @@ U16 = {'f16': 2.0 ** -11, 'bf16': 2.0 ** -8, 'f32': 0.0}
 D16 = {'f16': 2.0 ** -25, 'bf16': 0.0, 'f32': 0.0}
 GS = {'f16': 1024.0, 'bf16': 1.0, 'f32': 1.0}
 LW = 0.7
-BAND = 64           # guard elements on each side of every output
 
 
 @pytest.fixture(scope='module')
@@ -47,30 +48,6 @@ def L():
     lib = _lib.lib()
     assert hasattr(lib, 'orn_debug_side_head_bwd_f32'), 'liborn.so has no side-head entry points'
     return _lib
-
-
-def banded(shape, dtype, fill=None):
-    """(whole buffer, view of `shape` inside it): NaN guard bands of BAND elements around the view, which starts 16-byte aligned."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * BAND,), float('nan'), dtype=dtype, device='cuda')
-    view = buf[BAND:BAND + n].view(shape)
-    if fill is not None:
-        view.copy_(fill)
-    assert view.data_ptr() % 16 == 0 and view.is_contiguous()
-    return buf, view
-
-
-def bands_intact(buf):
-    return bool(torch.isnan(buf[:BAND]).all()) and bool(torch.isnan(buf[-BAND:]).all())
-
-
-def silu64(z):
-    return z / (1 + torch.exp(-z))
-
-
-def dsilu64(z):
-    s = 1 / (1 + torch.exp(-z))
-    return s * (1 + z * (1 - s))
 
 
 def make_inputs(C, H, W, s, kind, seed):
@@ -99,12 +76,6 @@ def ref_forward(x, w, b, sigmoid, kind, dtype=torch.float64):
     mag = torch.einsum('kc,chw->khw', wd.abs(), a.abs()) + bd.abs()[:, None, None] + 1
     out = torch.sigmoid(u) if sigmoid else (torch.tanh(u) + 1) * 0.5
     return out, mag, a
-
-
-def interior(t, C, H, W, s):
-    """The padded un-shuffled buffer [H/s + 2, W/s + 2, C s^2] as [C,H,W] values of its interior (a copy)."""
-    v = t[1:-1, 1:-1].reshape(H // s, W // s, s, s, C)              # [ph, pw, i, j, c]
-    return v.permute(4, 0, 2, 1, 3).reshape(C, H, W)
 
 
 def ref_backward(x, w, out, dout, old, sigmoid, kind, C, H, W, s, dtype=torch.float64):
