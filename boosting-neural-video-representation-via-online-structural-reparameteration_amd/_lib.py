@@ -77,7 +77,9 @@ class EngineDesc(ctypes.Structure):
                 # appended (all zero: the engine `erb` describes)
                 ('branch_kind', c_int32), ('reserved_', c_int32), ('branch', BranchDesc * ORN_MAX_LAYERS),
                 # appended (multi-resolution heads; all zero: a single-resolution engine)
-                ('multi_res', c_int32), ('lw', c_float), ('side_head_w', c_int64 * ORN_MAX_LAYERS), ('side_head_b', c_int64 * ORN_MAX_LAYERS)]
+                ('multi_res', c_int32), ('lw', c_float), ('side_head_w', c_int64 * ORN_MAX_LAYERS), ('side_head_b', c_int64 * ORN_MAX_LAYERS),
+                # appended (--act; all zero: swish)
+                ('act', c_int32), ('reserved2_', c_int32)]
 
 
 P = c_void_p
@@ -149,7 +151,17 @@ _SIGS = {
     'orn_engine_fused_kernel': (c_int, [P, c_int, POINTER(c_void_p), POINTER(c_void_p)]),
     'orn_engine_scale_state': (c_int, [P, P]),
     'orn_engine_set_grad_scale': (c_int, [P, c_float, c_float]),
+    # the entries above that evaluate the block activation, with ORN_ACT_* as one more trailing int
+    'orn_stem_fwd_act': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int]),
+    'orn_stem_bwd_act': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int]),
+    'orn_conv3x3_ps_silu_fwd_act': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int]),
+    'orn_conv3x3_ps_silu_bwd_act': (c_int, [P, P, P, P] + [c_int] * 6 + [P, P, P, P, c_size_t, P, c_int]),
+    'orn_conv3x3_ps_silu_fwd_bf16_act': (c_int, [P, P, P] + [c_int] * 5 + [P, P, P, c_size_t, P, c_int]),
+    'orn_conv3x3_ps_silu_bwd_bf16_act': (c_int, [P, P, P, P] + [c_int] * 5 + [P, P, P, P, c_size_t, P, c_int]),
+    'orn_conv3x3_ps_silu_fwd_f16_act': (c_int, [P, P, P] + [c_int] * 5 + [P, P, P, c_size_t, P, c_int]),
+    'orn_conv3x3_ps_silu_bwd_f16_act': (c_int, [P, P, P, P] + [c_int] * 5 + [P, P, P, P, c_size_t, P, c_int]),
 }
+ACT_SWISH, ACT_GELU = 0, 1          # ORN_ACT_* of include/orn.h
 EXPORTS = tuple(_SIGS.keys())
 # test and probe entry points (include/orn_debug.h): resolved if present, never required
 _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, [c_void_p]),
@@ -189,7 +201,14 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_conv_fwd_f32': (c_int, [P, P, P] + [c_int] * 6 + [P, P, P]),
                'orn_debug_head_fwd_z': (c_int, [P, P, P] + [c_int] * 5 + [P, P]),
                'orn_debug_conv_bwd_f32_head_ws_bytes': (c_size_t, [c_int] * 4),
-               'orn_debug_conv_bwd_f32_head': (c_int, [P] * 6 + [c_int] * 6 + [P] * 6 + [c_size_t, P])}
+               'orn_debug_conv_bwd_f32_head': (c_int, [P] * 6 + [c_int] * 6 + [P] * 6 + [c_size_t, P]),
+               'orn_debug_act_eval': (c_int, [c_int, c_int, P, c_size_t, P, P, P])}
+# the *_act twins of the debug entries that evaluate the block activation: the same arguments + a trailing int
+for _n in ('conv_fwd_bf16', 'conv_fwd_f16', 'conv_dgrad_bf16', 'conv_dgrad_f16', 'head_fwd_bf16', 'head_fwd_f16', 'head_bwd_bf16', 'head_bwd_f16',
+           'side_head_fwd_bf16', 'side_head_fwd_f16', 'side_head_bwd_bf16', 'side_head_bwd_f16', 'stage0_fwd', 'stage0_bwd', 'stem_bwd_slabs',
+           'conv_fwd_f32', 'head_fwd_z', 'conv_bwd_f32_head'):
+    _DEBUG_SIGS[f'orn_debug_{_n}_act'] = (_DEBUG_SIGS[f'orn_debug_{_n}'][0], _DEBUG_SIGS[f'orn_debug_{_n}'][1] + [c_int])
+del _n
 
 _lib = None
 

@@ -83,6 +83,8 @@ __device__ __forceinline__ float orn_silu_grad_exact(float z)
     return s * (1.0f + z * (1.0f - s));
 }
 
+#include "orn_act.h"
+
 __device__ __forceinline__ float orn_wave_sum(float v)
 {
 #pragma unroll
@@ -95,12 +97,13 @@ __device__ __forceinline__ float orn_wave_sum(float v)
 // B == 1, second linear layer of the stem backward, 16 output rows per 256-thread work-group (k_stem_bwd_l2, or trailing
 // work-groups of a later launch: the 16-bit engine runs it inside the batched wgrad launch, since only Adam and the stem's last
 // kernel -- which then trails the slab-reduction launch -- consume its results):
-//   d[o] = (sum_s dy_slabs[s][o]) * silu'(pre[o]);  db[o] = d[o];  dw[o][k] = d[o] * x[k];  partial[wg][k] = sum_o w[o][k] * d[o]
+//   d[o] = (sum_s dy_slabs[s][o]) * act'(pre[o]);  db[o] = d[o];  dw[o][k] = d[o] * x[k];  partial[wg][k] = sum_o w[o][k] * d[o]
 #define ORN_STEM_ROWS 16
 struct OrnStemL2Job {
     const float *w, *x, *pre, *dy_slabs; int nslab; size_t slab_ld; int K, N; float *dw, *db, *partial;
 };
 // t in [0, 256); sd: 16 floats of LDS; contains a work-group barrier (every thread of the work-group must call)
+template <int ACT = ORN_ACT_SWISH>
 __device__ __forceinline__ void orn_stem_l2_block(const OrnStemL2Job &j, int blk, int t, float *sd)
 {
     const int o0 = blk * ORN_STEM_ROWS, wave = t >> 6, lane = t & 63, N = j.N, K = j.K;
@@ -123,7 +126,7 @@ __device__ __forceinline__ void orn_stem_l2_block(const OrnStemL2Job &j, int blk
             const int r = wave + 4 * i, o = o0 + r;
             const float tot = orn_wave_sum(v[i]);
             if (lane == 0) {
-                const float d = o < N ? tot * orn_silu_grad_exact(pr[i]) : 0.f;
+                const float d = o < N ? tot * OrnAct<ACT>::df_exact(pr[i]) : 0.f;
                 sd[r] = d;
                 if (o < N) j.db[o] = d;
             }
@@ -152,6 +155,7 @@ struct OrnStemW0Job {
     const float *x; const int *row_idx; size_t row_stride; const float *pre, *dy_slabs; int nslab, K, N; float *dpre, *dw, *db;
 };
 // t in [0, 128); sh: 2 floats of LDS private to the row's two waves; contains a work-group barrier (every thread must call)
+template <int ACT = ORN_ACT_SWISH>
 __device__ __forceinline__ void orn_stem_w0_row(const OrnStemW0Job &j, int o, int t, float *sh)
 {
     const bool ok = o < j.N;
@@ -164,16 +168,17 @@ __device__ __forceinline__ void orn_stem_w0_row(const OrnStemW0Job &j, int o, in
     if ((t & 63) == 0) sh[t >> 6] = v;
     __syncthreads();
     if (!ok) return;
-    const float d = (sh[0] + sh[1]) * orn_silu_grad_exact(j.pre[o]);
+    const float d = (sh[0] + sh[1]) * OrnAct<ACT>::df_exact(j.pre[o]);
     if (t == 0) { j.dpre[o] = d; j.db[o] = d; }
     for (int k = t; k < j.K; k += 128) j.dw[(size_t)o * j.K + k] = d * x[k];
 }
 
-// One output neuron of y = silu(W x + b) per wave (B rows of x); shared by k_linear_silu and the merge launches that carry
+// One output neuron of y = act(W x + b) per wave (B rows of x); shared by k_linear_silu and the merge launches that carry
 // the stem's linear layers as extra work-groups (orn_merge.hip).
 struct OrnLinearJob {
     const float *x; const int *row_idx; size_t row_stride; const float *w, *bias; int B, K, N; float *pre, *y;
 };
+template <int ACT = ORN_ACT_SWISH>
 __device__ __forceinline__ void orn_linear_silu_wave(const OrnLinearJob &j, int wave, int lane)
 {
     if (wave >= j.N) return;
@@ -187,7 +192,8 @@ __device__ __forceinline__ void orn_linear_silu_wave(const OrnLinearJob &j, int 
         if (lane == 0) {
             const float p = acc + j.bias[wave];
             j.pre[(size_t)b * j.N + wave] = p;
-            j.y[(size_t)b * j.N + wave] = p / (1.0f + expf(-p));
+            if constexpr (ACT == ORN_ACT_SWISH) j.y[(size_t)b * j.N + wave] = p / (1.0f + expf(-p));
+            else j.y[(size_t)b * j.N + wave] = OrnAct<ACT>::f_exact(p);
         }
     }
 }

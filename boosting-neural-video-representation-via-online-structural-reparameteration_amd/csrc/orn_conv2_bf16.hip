@@ -122,7 +122,7 @@ constexpr int c2_pidx(int role, int t) { const int n = (role + 2) & 3; return n 
 constexpr int c2_cnt(int role, int t) { return c2_wcnt(role) + (c2_pidx(role, t) >= 0 ? 1 : 0); }
 static_assert(c2_pbase(6) == C2_PATCH_INSTR && C2_NSLOT == 4, "conv2: the piece deal assumes 22 patch pieces and the 4-deep ring (LAG 1)");
 
-template <int EPI, int ROLE>
+template <int EPI, int ROLE, int ACT>
 __device__ __forceinline__ void c2_body(const Conv2P &p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -292,7 +292,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
                                                        ok ? ((oh * Ws + ow) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);   // < 2^31 bytes: launcher
                 if (EPI == C2_FWD) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = orn_silu(v[e]);
+                    for (int e = 0; e < 8; ++e) v[e] = OrnAct<ACT>::f(v[e]);
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack_h16x2(v[0], v[1]), pack_h16x2(v[2], v[3]), pack_h16x2(v[4], v[5]), pack_h16x2(v[6], v[7])}, a_rsrc,
                                                            ok ? (((oh + 1) * (Ws + 2) + (ow + 1)) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);
                 }
@@ -325,7 +325,7 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
                 if (ok) {
                     h16x8 o8;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o8[e] = (h16)(v[e] * orn_silu_grad((float)zz[j][e]));
+                    for (int e = 0; e < 8; ++e) o8[e] = (h16)(v[e] * OrnAct<ACT>::df((float)zz[j][e]));
                     *reinterpret_cast<h16x8 *>(p.dyprev + ((size_t)(ph + 1) * (W / sp + 2) + (pw + 1)) * (96 * sp * sp) + sub * 96 + c8) = o8;
                 }
             }
@@ -333,36 +333,37 @@ __device__ __forceinline__ void c2_body(const Conv2P &p)
     }
 }
 
-template <int EPI>
+template <int EPI, int ACT = ORN_ACT_SWISH>
 __global__ void __launch_bounds__(256, 2) k_conv2_nhwc(Conv2P p)
 {
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {       // one copy of the body per DMA role (wave-uniform)
-    case 0: c2_body<EPI, 0>(p); break;
-    case 1: c2_body<EPI, 1>(p); break;
-    case 2: c2_body<EPI, 2>(p); break;
-    default: c2_body<EPI, 3>(p); break;
+    case 0: c2_body<EPI, 0, ACT>(p); break;
+    case 1: c2_body<EPI, 1, ACT>(p); break;
+    case 2: c2_body<EPI, 2, ACT>(p); break;
+    default: c2_body<EPI, 3, ACT>(p); break;
     }
 }
 
-template <int EPI>
+template <int EPI, int ACT = ORN_ACT_SWISH>
 static int c2_launch(const Conv2P &p, int blocks, size_t lds, hipStream_t st, const char *what)
 {
     // (one process drives one device: the attribute is set once per process, see include/orn.h)
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_conv2_nhwc<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C2_LDS + 2048));
+        hipError_t e = hipFuncSetAttribute((const void *)k_conv2_nhwc<EPI, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C2_LDS + 2048));
         if (e != hipSuccess) { orn_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return (int)e; }
         attr_done = true;
     }
-    hipLaunchKernelGGL(k_conv2_nhwc<EPI>, dim3(blocks), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((k_conv2_nhwc<EPI, ACT>), dim3(blocks), dim3(256), lds, st, p);
     ORN_LAUNCH_CHECK(what);
     return 0;
 }
 
 // dgrad of a block whose input image has >= 128 pixel tiles: dx = conv_transpose(dy) x SiLU'(z_prev) into the previous block's
 // dypad.  dypad [H+2][W+2][O], wd [9][96][O] (+ slack: see orn_conv_bf16_wd_elems), O % 32 == 0.
-int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st)
+int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv_bf16_dgrad: unknown activation %d", act);
     ORN_REQUIRE(O % C2_CK == 0 && zprev && dyprev && sp >= 1 && sp < 65536 && H % sp == 0 && W % sp == 0 && H < 65536 && W < 65536,
                 "conv_bf16_dgrad: unsupported O=%d sp=%d", O, sp);
     Conv2P p = {};
@@ -371,13 +372,14 @@ int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, cons
     p.qseg = O / C2_CK;
     p.tiles_w = orn_cdiv(W, C2_TW); p.tiles_h = orn_cdiv(H, C2_TH); p.ptiles = p.tiles_w * p.tiles_h; p.nsplit = 1;
     p.zprev = zprev; p.dyprev = dyprev; p.sp = sp; p.mSp = conv_magic(sp);
-    return c2_launch<C2_DGRAD>(p, p.ptiles, C2_LDS, st, "dgrad2_nhwc");
+    ORN_ACT_SWITCH(act, A, return (c2_launch<C2_DGRAD, A>(p, p.ptiles, C2_LDS, st, "dgrad2_nhwc")));
 }
 
 // forward of a block with 96 input channels and O % 96 == 0 output channels.  Returns -1 without launching when the shape is
 // not this form's (the caller falls back to the first form).
-int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st)
+int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv_bf16_fwd: unknown activation %d", act);
     if (O % 96 != 0 || O > 2048) return -1;
     Conv2P p = {};
     p.xpad = xpad; p.w = wb; p.H = H; p.W = W; p.Cx = 96;
@@ -395,7 +397,8 @@ int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, 
     p.mCn = conv_magic(p.Cn); p.mS = conv_magic(s);
     const int blocks = orn_cdiv(p.ptiles, 8) * 8 * p.nsplit;
     const size_t lds = C2_LDS + 96 * 4;
-    return apad ? c2_launch<C2_FWD>(p, blocks, lds, st, "fwd2_nhwc") : c2_launch<C2_FWD_LAST>(p, blocks, lds, st, "fwd2_nhwc_last");
+    if (!apad) return c2_launch<C2_FWD_LAST>(p, blocks, lds, st, "fwd2_nhwc_last");      // z only: no activation in it
+    ORN_ACT_SWITCH(act, A, return (c2_launch<C2_FWD, A>(p, blocks, lds, st, "fwd2_nhwc")));
 }
 
 }  // namespace HNS

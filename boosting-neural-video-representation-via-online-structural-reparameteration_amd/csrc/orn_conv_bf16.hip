@@ -375,6 +375,7 @@ int orn_dgrad_f32_slabs(int H, int W, int O)
 // Small images (too few pixel tiles to fill the chip): the dgrad runs split over the input chunks into fp32 partial
 // slabs [Q][H][W][96]; this pass sums them (fixed order), applies SiLU'(z_prev) and scatters into the previous layer's
 // dypad -- what the dgrad epilogue of orn_conv2_bf16.hip does in one go on large images.
+template <int ACT>
 __global__ void __launch_bounds__(256) k_dgrad_finish(const float *__restrict__ slabs, int Q, const h16 *__restrict__ zprev, int H, int W,
                                                      int sp, h16 *__restrict__ dyprev)
 {
@@ -393,7 +394,7 @@ __global__ void __launch_bounds__(256) k_dgrad_finish(const float *__restrict__ 
     const h16x8 zz = *reinterpret_cast<const h16x8 *>(zprev + pix * 96 + c8);
     h16x8 o8;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = (h16)(v[e] * orn_silu_grad((float)zz[e]));
+    for (int e = 0; e < 8; ++e) o8[e] = (h16)(v[e] * OrnAct<ACT>::df((float)zz[e]));
     const int ph = gh / sp, pw = gw / sp, sub = (gh - ph * sp) * sp + (gw - pw * sp);
     *reinterpret_cast<h16x8 *>(dyprev + ((size_t)(ph + 1) * (W / sp + 2) + (pw + 1)) * (96 * sp * sp) + sub * 96 + c8) = o8;
 }
@@ -403,8 +404,9 @@ __global__ void __launch_bounds__(256) k_dgrad_finish(const float *__restrict__ 
 // c_real (fp32-output form only): output channels that are not zero padding; <= 32 of them on a chunk-split launch take the
 // all-taps-resident N = 32 form and only channels [0, 32) of the slabs are written
 int orn_launch_conv_bf16_dgrad(const h16 *dypad, const h16 *wd, int H, int W, int O, int C, const h16 *zprev,
-                               h16 *dyprev, int sp, float *dx_f32, hipStream_t st, int c_real)
+                               h16 *dyprev, int sp, float *dx_f32, hipStream_t st, int c_real, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv_bf16_dgrad: unknown activation %d", act);
     ORN_REQUIRE(O % CB_CK == 0 && C == 96, "conv_bf16_dgrad: unsupported O=%d C=%d", O, C);
     ConvBP p = {};
     p.dbg = g_conv_dbg;
@@ -421,14 +423,15 @@ int orn_launch_conv_bf16_dgrad(const h16 *dypad, const h16 *wd, int H, int W, in
         if (!zprev) return launch_conv_cfg<8, 1, 1, 3, EPI_B_DGRAD_F32>(p, st);
         ORN_REQUIRE(dyprev && sp >= 1 && H % sp == 0 && W % sp == 0 && p.qsplit, "conv_bf16_dgrad: bad split-epilogue arguments");
         ORN_TRY((launch_conv_cfg<8, 1, 1, 3, EPI_B_DGRAD_F32>(p, st)));
-        hipLaunchKernelGGL(k_dgrad_finish, dim3(orn_cdiv((long)H * W * 12, 256)), dim3(256), 0, st, dx_f32, O / CB_CK, zprev, H, W, sp, dyprev);
+        ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_dgrad_finish<A>, dim3(orn_cdiv((long)H * W * 12, 256)), dim3(256), 0, st, dx_f32, O / CB_CK, zprev, H, W,
+                                                  sp, dyprev));
         ORN_LAUNCH_CHECK("dgrad_finish");
         return 0;
     }
     ORN_REQUIRE(zprev && dyprev && sp >= 1 && H % sp == 0 && W % sp == 0, "conv_bf16_dgrad: bad epilogue arguments");
     // (Round 3 also built the block's own wgrad riding behind these dgrad tiles in one launch: the two combined launches took 17 us
     // less than the launches they replaced, the STEP 13 us more -- DESIGN 4.5; removed in round 4.)
-    return orn_launch_dgrad2(dypad, wd, H, W, O, zprev, dyprev, sp, st);       // two work-groups per CU: orn_conv2_bf16.hip
+    return orn_launch_dgrad2(dypad, wd, H, W, O, zprev, dyprev, sp, st, act);       // two work-groups per CU: orn_conv2_bf16.hip
 }
 
 #ifdef ORN_CONV_STAMP

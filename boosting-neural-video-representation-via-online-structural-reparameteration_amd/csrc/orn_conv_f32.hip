@@ -48,7 +48,7 @@ struct ConvP {
 #endif
 // NOB = 32-channel blocks of the work-group's output-channel tile: 2 (64 channels), or 1 for the last 32 channels of an O that is
 // 32 mod 64 (the dgrad of every 96-channel layer: as a second 64-channel tile, half of its MFMA work was thrown away).
-template <int EPI, int SMALL, int NOB = 2>
+template <int EPI, int SMALL, int NOB = 2, int ACT = ORN_ACT_SWISH>
 __global__ void __launch_bounds__(256, F32_MINB) k_conv3x3_f32(ConvP p)
 {
     constexpr int TH = SMALL ? 2 : CV_TH;
@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(256, F32_MINB) k_conv3x3_f32(ConvP p)
                     const int n = o >> 2, si = (o >> 1) & 1;
                     const size_t idx = (((size_t)b * Cn + n) * (H * 2) + (gh * 2 + si)) * (size_t)(W * 2) + (size_t)gw * 2;
                     if (p.z) *reinterpret_cast<float2 *>(p.z + idx) = make_float2(v0, v1);
-                    if (p.out) *reinterpret_cast<float2 *>(p.out + idx) = make_float2(orn_silu_exact(v0), orn_silu_exact(v1));
+                    if (p.out) *reinterpret_cast<float2 *>(p.out + idx) = make_float2(OrnAct<ACT>::f_exact(v0), OrnAct<ACT>::f_exact(v1));
                 }
                 continue;
             }
@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(256, F32_MINB) k_conv3x3_f32(ConvP p)
                     const int Cn = p.O / ss;
                     const size_t idx = (((size_t)b * Cn + n) * (H * s) + (gh * s + si)) * (size_t)(W * s) + (gw * s + sj);
                     if (p.z) p.z[idx] = v;
-                    if (p.out) p.out[idx] = orn_silu_exact(v);
+                    if (p.out) p.out[idx] = OrnAct<ACT>::f_exact(v);
                 }
             }
         }
@@ -259,8 +259,9 @@ static ConvSel conv_select(int B, int C, int O, int H, int W, int epi, bool may_
 }
 
 int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, int B, int C, int O, int H, int W,
-                           int s, int epi, float *z, float *out, hipStream_t st, float *split_ws)
+                           int s, int epi, float *z, float *out, hipStream_t st, float *split_ws, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv3x3_f32: unknown activation %d", act);
     ConvP p;
     p.x = x; p.w = w; p.bias = bias; p.out = out; p.z = z;
     p.B = B; p.C = C; p.O = O; p.H = H; p.W = W; p.s = s;
@@ -290,8 +291,8 @@ int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, in
     }
     dim3 grid(p.tiles_w * p.tiles_h, sel.n64, B);
     if (epi == EPI_PS_SILU) {
-        if (small) hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 0>), grid, dim3(256), 0, st, p);
+        if (small) ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 1, 2, A>), grid, dim3(256), 0, st, p));
+        else ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_conv3x3_f32<EPI_PS_SILU, 0, 2, A>), grid, dim3(256), 0, st, p));
     } else {
         if (small) hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 1>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((k_conv3x3_f32<EPI_PLAIN, 0>), grid, dim3(256), 0, st, p);
@@ -300,13 +301,20 @@ int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, in
     return 0;
 }
 
-extern "C" int orn_conv3x3_ps_silu_fwd(const float *x, const float *wf, const float *bf, int B, int C, int O, int H,
-                                       int W, int s, float *z, float *a, void *stream)
+extern "C" int orn_conv3x3_ps_silu_fwd_act(const float *x, const float *wf, const float *bf, int B, int C, int O, int H,
+                                           int W, int s, float *z, float *a, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv3x3_ps_silu_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && a, "conv3x3_ps_silu_fwd: null pointer");
     ORN_REQUIRE(B > 0 && C > 0 && O > 0 && H > 0 && W > 0 && s > 0, "conv3x3_ps_silu_fwd: bad sizes");
     ORN_REQUIRE(O % (s * s) == 0, "conv3x3_ps_silu_fwd: O=%d not divisible by s*s=%d", O, s * s);
-    return orn_launch_conv3x3_f32(x, wf, bf, B, C, O, H, W, s, EPI_PS_SILU, z, a, (hipStream_t)stream, nullptr);
+    return orn_launch_conv3x3_f32(x, wf, bf, B, C, O, H, W, s, EPI_PS_SILU, z, a, (hipStream_t)stream, nullptr, act);
+}
+
+extern "C" int orn_conv3x3_ps_silu_fwd(const float *x, const float *wf, const float *bf, int B, int C, int O, int H,
+                                       int W, int s, float *z, float *a, void *stream)
+{
+    return orn_conv3x3_ps_silu_fwd_act(x, wf, bf, B, C, O, H, W, s, z, a, stream, ORN_ACT_SWISH);
 }
 
 // ================================================================================================
@@ -314,6 +322,7 @@ extern "C" int orn_conv3x3_ps_silu_fwd(const float *x, const float *wf, const fl
 // grid: (chunks, O, B); each block sums its chunk -> partial[(b*chunks + chunk)*O + o]
 // ================================================================================================
 #define DY_PPB 2048
+template <int ACT>
 __global__ void __launch_bounds__(256)
 k_silu_bwd_unshuffle(const float *__restrict__ da, const float *__restrict__ z, int O, int H, int W, int s,
                      float *__restrict__ dy, float *__restrict__ partial)
@@ -334,7 +343,7 @@ k_silu_bwd_unshuffle(const float *__restrict__ da, const float *__restrict__ z, 
         if (pix < HW) {
             const int h = (int)(pix / W), w = (int)(pix - (size_t)h * W);
             const size_t src = (size_t)(h * s + si) * Ws + (size_t)(w * s + sj);
-            const float v = dab[src] * orn_silu_grad_exact(zb[src]);
+            const float v = dab[src] * OrnAct<ACT>::df_exact(zb[src]);
             dyb[pix] = v;
             sum += v;
         }
@@ -345,6 +354,7 @@ k_silu_bwd_unshuffle(const float *__restrict__ da, const float *__restrict__ z, 
 
 // stride 2: output channels (o, o + 1), o even, are the horizontal sub-pixels sj = 0, 1 of one (n, si): one 8-byte load of da and
 // of z per thread instead of two 4-byte loads 8 bytes apart.  grid: (chunks, O / 2, B)
+template <int ACT>
 __global__ void __launch_bounds__(256)
 k_silu_bwd_unshuffle_s2(const float *__restrict__ da, const float *__restrict__ z, int O, int H, int W,
                         float *__restrict__ dy, float *__restrict__ partial)
@@ -367,7 +377,7 @@ k_silu_bwd_unshuffle_s2(const float *__restrict__ da, const float *__restrict__ 
             const size_t src = (size_t)(h * 2 + si) * Ws + (size_t)w * 2;
             const float2 d = *reinterpret_cast<const float2 *>(dab + src);
             const float2 zz = *reinterpret_cast<const float2 *>(zb + src);
-            const float v0 = d.x * orn_silu_grad_exact(zz.x), v1 = d.y * orn_silu_grad_exact(zz.y);
+            const float v0 = d.x * OrnAct<ACT>::df_exact(zz.x), v1 = d.y * OrnAct<ACT>::df_exact(zz.y);
             dy0[pix] = v0; dy1[pix] = v1;
             sum0 += v0; sum1 += v1;
         }
@@ -782,8 +792,9 @@ extern "C" size_t orn_conv3x3_ps_silu_bwd_ws_bytes(int B, int C, int O, int H, i
 
 int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, const float *da, int B, int C, int O,
                             int H, int W, int s, float *dx, float *dwf, float *dbf, float *ws, hipStream_t st,
-                            const OrnHeadBwdFuse *head, const float *wd_ready)
+                            const OrnHeadBwdFuse *head, const float *wd_ready, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv_bwd_f32: unknown activation %d", act);
     const size_t HW = (size_t)H * W;
     const int chunks = orn_cdiv((long)HW, DY_PPB);
     const int S = wgrad_geo(B, C, O, H, W).S;
@@ -800,10 +811,10 @@ int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, con
         ORN_REQUIRE(B == 1 && s == 2, "conv_bwd_f32: fused head backward needs B == 1, s == 2");
         dbp_n = orn_head_bwd_fused_f32_blocks(H, W);
         ORN_TRY(orn_launch_head_bwd_fused_f32(z, head->w, head->out, head->dout, O / 4, H, W, head->sigmoid, dy, dbp, head->dw, head->db,
-                                              head->hws, st));
+                                              head->hws, st, act));
     } else {
-        if (s == 2) hipLaunchKernelGGL(k_silu_bwd_unshuffle_s2, dim3(chunks, O / 2, B), dim3(256), 0, st, da, z, O, H, W, dy, dbp);
-        else hipLaunchKernelGGL(k_silu_bwd_unshuffle, dim3(chunks, O, B), dim3(256), 0, st, da, z, O, H, W, s, dy, dbp);
+        if (s == 2) ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_silu_bwd_unshuffle_s2<A>, dim3(chunks, O / 2, B), dim3(256), 0, st, da, z, O, H, W, dy, dbp));
+        else ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_silu_bwd_unshuffle<A>, dim3(chunks, O, B), dim3(256), 0, st, da, z, O, H, W, s, dy, dbp));
         ORN_LAUNCH_CHECK("silu_bwd_unshuffle");
     }
     ORN_TRY(orn_launch_reduce_rows(dbp, dbp_n, (size_t)O, (size_t)O, dbf, st));
@@ -831,22 +842,30 @@ int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, con
         if (wd_ready) wd = const_cast<float *>(wd_ready);      // (the engine flips every layer's kernel in one launch)
         else hipLaunchKernelGGL(k_flip_transpose_w, dim3(orn_cdiv((long)O * C * 9, 256)), dim3(256), 0, st, wf, O, C, wd);
         ORN_LAUNCH_CHECK("flip_transpose_w");
-        ORN_TRY(orn_launch_conv3x3_f32(dy, wd, nullptr, B, O, C, H, W, 1, EPI_PLAIN, nullptr, dx, st, dgs));
+        ORN_TRY(orn_launch_conv3x3_f32(dy, wd, nullptr, B, O, C, H, W, 1, EPI_PLAIN, nullptr, dx, st, dgs, ORN_ACT_SWISH));   // (plain epilogue: no activation in it)
     }
     return 0;
 }
 
-extern "C" int orn_conv3x3_ps_silu_bwd(const float *x, const float *wf, const float *z, const float *da, int B,
-                                       int C, int O, int H, int W, int s, float *dx, float *dwf, float *dbf,
-                                       void *ws, size_t ws_bytes, void *stream)
+extern "C" int orn_conv3x3_ps_silu_bwd_act(const float *x, const float *wf, const float *z, const float *da, int B,
+                                           int C, int O, int H, int W, int s, float *dx, float *dwf, float *dbf,
+                                           void *ws, size_t ws_bytes, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv3x3_ps_silu_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && z && da && dwf && dbf && ws, "conv3x3_ps_silu_bwd: null pointer");
     ORN_REQUIRE(B > 0 && C > 0 && O > 0 && H > 0 && W > 0 && s > 0 && O % (s * s) == 0, "conv3x3_ps_silu_bwd: bad sizes");
     if (ws_bytes < orn_conv3x3_ps_silu_bwd_ws_bytes(B, C, O, H, W)) {
         orn_set_error("conv3x3_ps_silu_bwd: workspace %zu < %zu", ws_bytes, orn_conv3x3_ps_silu_bwd_ws_bytes(B, C, O, H, W));
         return ORN_E_WS;
     }
-    return orn_launch_conv_bwd_f32(x, wf, z, da, B, C, O, H, W, s, dx, dwf, dbf, (float *)ws, (hipStream_t)stream);
+    return orn_launch_conv_bwd_f32(x, wf, z, da, B, C, O, H, W, s, dx, dwf, dbf, (float *)ws, (hipStream_t)stream, nullptr, nullptr, act);
+}
+
+extern "C" int orn_conv3x3_ps_silu_bwd(const float *x, const float *wf, const float *z, const float *da, int B,
+                                       int C, int O, int H, int W, int s, float *dx, float *dwf, float *dbf,
+                                       void *ws, size_t ws_bytes, void *stream)
+{
+    return orn_conv3x3_ps_silu_bwd_act(x, wf, z, da, B, C, O, H, W, s, dx, dwf, dbf, ws, ws_bytes, stream, ORN_ACT_SWISH);
 }
 
 // ================================================================================================
@@ -884,13 +903,20 @@ extern "C" int orn_debug_conv_f32_plan(int B, int C, int O, int H, int W, int32_
     return 0;
 }
 
-extern "C" int orn_debug_conv_fwd_f32(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
-                                      float *z, float *a, void *stream)
+extern "C" int orn_debug_conv_fwd_f32_act(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
+                                          float *z, float *a, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "debug_conv_fwd_f32: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && (z || a), "debug_conv_fwd_f32: null pointer");
     ORN_REQUIRE(B > 0 && C > 0 && O > 0 && H > 0 && W > 0 && s > 0, "debug_conv_fwd_f32: bad sizes");
     ORN_REQUIRE(O % (s * s) == 0, "debug_conv_fwd_f32: O=%d not divisible by s*s=%d", O, s * s);
-    return orn_launch_conv3x3_f32(x, wf, bf, B, C, O, H, W, s, EPI_PS_SILU, z, a, (hipStream_t)stream, nullptr);
+    return orn_launch_conv3x3_f32(x, wf, bf, B, C, O, H, W, s, EPI_PS_SILU, z, a, (hipStream_t)stream, nullptr, act);
+}
+
+extern "C" int orn_debug_conv_fwd_f32(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
+                                      float *z, float *a, void *stream)
+{
+    return orn_debug_conv_fwd_f32_act(x, wf, bf, B, C, O, H, W, s, z, a, stream, ORN_ACT_SWISH);
 }
 
 // workspace of orn_debug_conv_bwd_f32_head: the conv backward's, the head's partials, the pre-flipped kernel
@@ -905,11 +931,12 @@ extern "C" size_t orn_debug_conv_bwd_f32_head_ws_bytes(int C, int O, int H, int 
     return orn_align(orn_conv3x3_ps_silu_bwd_ws_bytes(1, C, O, H, W)) + head_dbg_hws_bytes(O, H, W) + orn_align((size_t)O * C * 9 * 4);
 }
 
-extern "C" int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
-                                           const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
-                                           float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
-                                           void *stream)
+extern "C" int orn_debug_conv_bwd_f32_head_act(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
+                                               const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
+                                               float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
+                                               void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "debug_conv_bwd_f32_head: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && z && head_w && head_out && head_dout && dwf && dbf && head_dw && head_db && ws,
                 "debug_conv_bwd_f32_head: null pointer");
     ORN_REQUIRE(C > 0 && O > 0 && H > 0 && W > 0 && O % 4 == 0, "debug_conv_bwd_f32_head: bad sizes");
@@ -929,5 +956,14 @@ extern "C" int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, cons
         float *wds[1] = {wd};
         ORN_TRY(orn_launch_flip_transpose_all(1, wfs, wds, &O, &C, st));
     }
-    return orn_launch_conv_bwd_f32(x, wf, z, nullptr, 1, C, O, H, W, 2, dx, dwf, dbf, cws, st, &hf, (preflip && dx) ? wd : nullptr);
+    return orn_launch_conv_bwd_f32(x, wf, z, nullptr, 1, C, O, H, W, 2, dx, dwf, dbf, cws, st, &hf, (preflip && dx) ? wd : nullptr, act);
+}
+
+extern "C" int orn_debug_conv_bwd_f32_head(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
+                                           const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
+                                           float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
+                                           void *stream)
+{
+    return orn_debug_conv_bwd_f32_head_act(x, wf, z, head_w, head_out, head_dout, C, O, H, W, sigmoid, preflip, dx, dwf, dbf, head_dw, head_db,
+                                           ws, ws_bytes, stream, ORN_ACT_SWISH);
 }

@@ -76,7 +76,7 @@ __device__ __forceinline__ void convf_wait_set(h16x8 (&fa)[NSET][MB], h16x8 (&fb
 // tiles 72 KB -- so an N tile is ONE rendezvous and 72 back-to-back MFMAs per wave instead of nine rounds of barrier +
 // counted wait + 24 MFMAs of which two thirds multiply zeros.  Rows are 64 B: 4 chunks, XOR swizzle (chunk ^ ((row >> 2) & 3)).
 // ALLTAPS: all nine weight tiles of the (single) K chunk resident, one rendezvous per N tile -- the narrow form.
-template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK)>
+template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK), int ACT = ORN_ACT_SWISH>
 __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(ConvFP p)
 {
     ORN_PRIO_HIGH();
@@ -335,8 +335,8 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{za0, za1, zb0, zb1}, z_rsrc,
                                                            okc ? ((oh * Ws + ow) * p.Cn + n) * 2 : (int)0x80000000, 0, 0);   // < 2^31 bytes: launcher
                     if (APAD) {
-                        unsigned aa0 = pack_h16x2(orn_silu(va[0]), orn_silu(va[1])), aa1 = pack_h16x2(orn_silu(va[2]), orn_silu(va[3]));
-                        unsigned ab0 = pack_h16x2(orn_silu(vb[0]), orn_silu(vb[1])), ab1 = pack_h16x2(orn_silu(vb[2]), orn_silu(vb[3]));
+                        unsigned aa0 = pack_h16x2(OrnAct<ACT>::f(va[0]), OrnAct<ACT>::f(va[1])), aa1 = pack_h16x2(OrnAct<ACT>::f(va[2]), OrnAct<ACT>::f(va[3]));
+                        unsigned ab0 = pack_h16x2(OrnAct<ACT>::f(vb[0]), OrnAct<ACT>::f(vb[1])), ab1 = pack_h16x2(OrnAct<ACT>::f(vb[2]), OrnAct<ACT>::f(vb[3]));
                         swap_halves(aa0, ab0); swap_halves(aa1, ab1);
                         // the activation copy leaves right away (the next vmcnt wait is a whole tap of the next N tile away)
                         __builtin_amdgcn_raw_buffer_store_b128(u32x4{aa0, aa1, ab0, ab1}, a_rsrc,
@@ -359,7 +359,7 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) k_conv_fwd_nhwc_bf16(Co
 #undef WAIT_VM
 #undef BARRIER
 
-template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK)>
+template <int WAVES_M, int WAVES_N, int MB, int NB, int EPI, int CK = CB_CK, bool ALLTAPS = (CK != CB_CK), int ACT = ORN_ACT_SWISH>
 static int launch_convf_cfg(const ConvFP &p, int n_tiles_total, hipStream_t st)
 {
     constexpr int BN = WAVES_N * NB * 32;
@@ -369,7 +369,7 @@ static int launch_convf_cfg(const ConvFP &p, int n_tiles_total, hipStream_t st)
 #ifdef ORN_CONV_STAMP
     smem += 1024;
 #endif
-    auto kern = k_conv_fwd_nhwc_bf16<WAVES_M, WAVES_N, MB, NB, EPI, CK, ALLTAPS>;
+    auto kern = k_conv_fwd_nhwc_bf16<WAVES_M, WAVES_N, MB, NB, EPI, CK, ALLTAPS, ACT>;
     static bool attr_done = false;
     if (!attr_done) {
         // opt in once for the largest request (bias copy up to 2048 channels)
@@ -397,8 +397,9 @@ void set_debug_fwd(int flags) { g_convf_dbg = flags; }
 // N tile 128 (waves 4x2, wave tile 64 px x 64 ch)
 // c_real: input channels that are not zero padding (<= Cin); <= 32 of them take the narrow form (forward of a non-last block)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
-                             h16 *z, h16 *apad, hipStream_t st, int c_real)
+                             h16 *z, h16 *apad, hipStream_t st, int c_real, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv_bf16_fwd: unknown activation %d", act);
     // O % 32: whole MFMA blocks; an O that is not a multiple of the 128-channel N tile gets a ragged last tile whose weight
     // DMA reads up to 96 rows past row O of each tap: `wb` must be readable for 96 * Cin elements behind its last row
     // (orn_conv_bf16_wb_elems; the values are never used).  Both epilogues store 8 consecutive channels of one sub-pixel: Cn % 8
@@ -424,16 +425,18 @@ int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p
     const float cost_whole = (float)orn_cdiv(ptiles, 256) * nt_total;
     const float cost_split = (float)orn_cdiv(ptiles * nt_total, 256) * 1.3f;
     p.n_tiles_per_wg = (ptiles >= 512 || cost_whole <= cost_split) ? nt_total : 1;
-    if (apad && c_real > 0 && c_real <= 32) return launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD, 32>(p, nt_total, st);
+    if (apad && c_real > 0 && c_real <= 32)
+        ORN_ACT_SWITCH(act, A, return (launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD, 32, true, A>(p, nt_total, st)));
     // large images with whole 96-channel N tiles: the two-work-groups-per-CU form (orn_conv2_bf16.hip).  Measured in the step:
     // the last block (z only) 150 -> 140 us at 720p; blocks that also write the activation copy are neutral at 230 pixel tiles
     // (720p, 180 x 320: 74.2 vs 73.9 us for the two such launches) and gain from ~500 tiles on (1080p: 181 -> 168 us for its
     // three), so those take it from 400 tiles.
     if (Cin == 96 && O % 96 == 0 && ptiles >= 128 && (!apad || ptiles >= 400)) {
-        const int rc = orn_launch_fwd2(xpad, wb, bias_p, H, W, O, s, z, apad, st);
+        const int rc = orn_launch_fwd2(xpad, wb, bias_p, H, W, O, s, z, apad, st, act);
         if (rc != -1) return rc;
     }
-    return apad ? launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD>(p, nt_total, st) : launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD_LAST>(p, nt_total, st);
+    if (!apad) return launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD_LAST>(p, nt_total, st);      // z only: no activation in it
+    ORN_ACT_SWITCH(act, A, return (launch_convf_cfg<4, 2, 2, 2, EPI_B_FWD, CB_CK, false, A>(p, nt_total, st)));
 }
 
 

@@ -62,6 +62,7 @@ __device__ __forceinline__ void orn_decode_stats_block(float ef, float eq, const
 
 namespace HNS {
 
+template <int ACT>
 __global__ void __launch_bounds__(256)
 k_decode_out_nhwc(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ bias, int C, size_t HW, int sigmoid,
                   OrnDecodeOut o)
@@ -101,7 +102,7 @@ k_decode_out_nhwc(const h16 *__restrict__ z, const float *__restrict__ w, const 
         float a0 = 0.f, a1 = 0.f, a2 = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (q < nq) head_accum8(vc[q], (q * 4 + sub) * 8, C, sw, a0, a1, a2);
+            if (q < nq) head_accum8<ACT>(vc[q], (q * 4 + sub) * 8, C, sw, a0, a1, a2);
         head_reduce4(a0, a1, a2);
         const float v = sub < 3 ? head_act(a0, a1, a2, sub, C, sw, sigmoid) : 0.f;
         const unsigned qv = sub < 3 ? orn_quant8(v) : 0u;
@@ -131,13 +132,15 @@ k_decode_out_nhwc(const h16 *__restrict__ z, const float *__restrict__ w, const 
     if (o.stats) orn_decode_stats_block(ef, eq, o, HW, sd, sf);
 }
 
-int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st)
+int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st,
+                              int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "decode_out: unknown activation %d", act);
     ORN_REQUIRE(C % 32 == 0 && C <= 128, "decode_out: unsupported C=%d", C);
     ORN_REQUIRE(!o.stats || (o.targets && o.row && o.ws), "decode_out: stats need targets and a workspace");
     int blocks = orn_cdiv((long)HW, 64);
     if (blocks > ORN_DECODE_MAX_BLOCKS) blocks = ORN_DECODE_MAX_BLOCKS;     // (the head forward's own grid: 8192 beat 2048 there)
-    hipLaunchKernelGGL(k_decode_out_nhwc, dim3(blocks), dim3(256), 0, st, z, w, b, C, HW, sigmoid, o);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_decode_out_nhwc<A>, dim3(blocks), dim3(256), 0, st, z, w, b, C, HW, sigmoid, o));
     ORN_LAUNCH_CHECK("decode_out");
     return 0;
 }

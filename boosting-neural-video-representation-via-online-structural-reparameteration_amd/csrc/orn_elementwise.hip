@@ -116,20 +116,35 @@ extern "C" int orn_pe_fwd(const float *pos, int B, const float *lbase_pow, int l
 // ------------------------------------------------------------------------------------------------
 // y[b][o] = silu(pre), pre = bias[o] + sum_k w[o][k]*x[b][k]; one wave per output neuron.
 // x row selected through an optional device index (engine: frame index of the current step).
+template <int ACT>
 __global__ void k_linear_silu(const float *__restrict__ x, const int *__restrict__ row_idx, size_t row_stride,
                               const float *__restrict__ w, const float *__restrict__ bias, int B, int K, int N,
                               float *__restrict__ pre, float *__restrict__ y)
 {
     const OrnLinearJob j = {x, row_idx, row_stride, w, bias, B, K, N, pre, y};
-    orn_linear_silu_wave(j, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63);
+    orn_linear_silu_wave<ACT>(j, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63);
 }
 
 int orn_launch_linear_silu(const float *x, const int *row_idx, size_t row_stride, const float *w, const float *b,
-                           int B, int K, int N, float *pre, float *y, hipStream_t st)
+                           int B, int K, int N, float *pre, float *y, hipStream_t st, int act)
 {
-    hipLaunchKernelGGL(k_linear_silu, dim3(orn_cdiv((long)N * 64, 256)), dim3(256), 0, st, x, row_idx, row_stride,
-                       w, b, B, K, N, pre, y);
+    ORN_REQUIRE(orn_act_known(act), "linear_act: unknown activation %d", act);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_linear_silu<A>, dim3(orn_cdiv((long)N * 64, 256)), dim3(256), 0, st, x, row_idx, row_stride,
+                                              w, b, B, K, N, pre, y));
     ORN_LAUNCH_CHECK("linear_silu");
+    return 0;
+}
+
+extern "C" int orn_stem_fwd_act(const float *embed, const float *w0, const float *b0, const float *w1, const float *b1,
+                                int B, int E, int Hd, int Nout, float *pre1, float *h1, float *pre2, float *h2,
+                                void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "stem_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(embed && w0 && b0 && w1 && b1 && pre1 && h1 && pre2 && h2, "stem_fwd: null pointer");
+    ORN_REQUIRE(B > 0 && E > 0 && Hd > 0 && Nout > 0, "stem_fwd: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    ORN_TRY(orn_launch_linear_silu(embed, nullptr, 0, w0, b0, B, E, Hd, pre1, h1, st, act));
+    ORN_TRY(orn_launch_linear_silu(h1, nullptr, 0, w1, b1, B, Hd, Nout, pre2, h2, st, act));
     return 0;
 }
 
@@ -137,15 +152,11 @@ extern "C" int orn_stem_fwd(const float *embed, const float *w0, const float *b0
                             int B, int E, int Hd, int Nout, float *pre1, float *h1, float *pre2, float *h2,
                             void *stream)
 {
-    ORN_REQUIRE(embed && w0 && b0 && w1 && b1 && pre1 && h1 && pre2 && h2, "stem_fwd: null pointer");
-    ORN_REQUIRE(B > 0 && E > 0 && Hd > 0 && Nout > 0, "stem_fwd: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    ORN_TRY(orn_launch_linear_silu(embed, nullptr, 0, w0, b0, B, E, Hd, pre1, h1, st));
-    ORN_TRY(orn_launch_linear_silu(h1, nullptr, 0, w1, b1, B, Hd, Nout, pre2, h2, st));
-    return 0;
+    return orn_stem_fwd_act(embed, w0, b0, w1, b1, B, E, Hd, Nout, pre1, h1, pre2, h2, stream, ORN_ACT_SWISH);
 }
 
 // dpre[b][o] = dy[b][o]*silu'(pre[b][o]);  db[o] = sum_b dpre;  dw[o][k] = sum_b dpre[b][o]*x[b][k]
+template <int ACT>
 __global__ void k_linear_silu_bwd_w(const float *__restrict__ x, const int *__restrict__ row_idx, size_t row_stride,
                                     const float *__restrict__ pre, const float *__restrict__ dy, int B, int K, int N,
                                     float *__restrict__ dpre, float *__restrict__ dw, float *__restrict__ db)
@@ -156,7 +167,7 @@ __global__ void k_linear_silu_bwd_w(const float *__restrict__ x, const int *__re
     if (row_idx) x += (size_t)(*row_idx) * row_stride;
     float dsum = 0.f;
     for (int b = 0; b < B; ++b) {
-        const float d = dy[(size_t)b * N + o] * orn_silu_grad_exact(pre[(size_t)b * N + o]);
+        const float d = dy[(size_t)b * N + o] * OrnAct<ACT>::df_exact(pre[(size_t)b * N + o]);
         dsum += d;
         if (lane == 0) dpre[(size_t)b * N + o] = d;
     }
@@ -164,7 +175,7 @@ __global__ void k_linear_silu_bwd_w(const float *__restrict__ x, const int *__re
     for (int k = lane; k < K; k += 64) {
         float acc = 0.f;
         for (int b = 0; b < B; ++b) {
-            const float d = dy[(size_t)b * N + o] * orn_silu_grad_exact(pre[(size_t)b * N + o]);
+            const float d = dy[(size_t)b * N + o] * OrnAct<ACT>::df_exact(pre[(size_t)b * N + o]);
             acc = fmaf(d, x[(size_t)b * K + k], acc);
         }
         dw[(size_t)o * K + k] = acc;
@@ -173,6 +184,7 @@ __global__ void k_linear_silu_bwd_w(const float *__restrict__ x, const int *__re
 
 // B == 1 variant whose upstream gradient arrives as `nslab` partial rows (k_linear_bwd_x_partial): the block sums its
 // column in fixed order itself, so no standalone reduction launch is needed.
+template <int ACT>
 __global__ void __launch_bounds__(128)
 k_linear_silu_bwd_w_slabs(const float *__restrict__ x, const int *__restrict__ row_idx, size_t row_stride,
                           const float *__restrict__ pre, const float *__restrict__ dy_slabs, int nslab, int K, int N,
@@ -186,7 +198,7 @@ k_linear_silu_bwd_w_slabs(const float *__restrict__ x, const int *__restrict__ r
     for (int r = threadIdx.x; r < nslab; r += blockDim.x) v += dy_slabs[(size_t)r * N + o];
     const float tot = orn_block_sum(v, sred);
     if (threadIdx.x == 0) {
-        const float d = tot * orn_silu_grad_exact(pre[o]);
+        const float d = tot * OrnAct<ACT>::df_exact(pre[o]);
         sd = d;
         dpre[o] = d;
         db[o] = d;
@@ -216,17 +228,19 @@ __global__ void k_linear_bwd_x_partial(const float *__restrict__ w, const float 
 // B == 1, second linear layer, one launch (orn_stem_l2_block, orn_common.h): the upstream gradient arrives as `nslab` partial rows
 // (the first block's per-work-group dx shares, or one finished row), 16 output rows per work-group
 // (was: slab reduction + k_linear_silu_bwd_w + k_linear_bwd_x_partial, three graph nodes of ~5-9 us each)
+template <int ACT>
 __global__ void __launch_bounds__(256) k_stem_bwd_l2(OrnStemL2Job j)
 {
     __shared__ float sd[ORN_STEM_ROWS];
-    orn_stem_l2_block(j, (int)blockIdx.x, (int)threadIdx.x, sd);
+    orn_stem_l2_block<ACT>(j, (int)blockIdx.x, (int)threadIdx.x, sd);
 }
 
 int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_stride, const float *w1, const float *pre1,
                         const float *h1, const float *pre2, const float *dh2, int B, int E, int Hd, int Nout,
                         float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab, OrnStemW0Job *defer_w0,
-                        OrnStemL2Job *defer_l2)
+                        OrnStemL2Job *defer_l2, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "stem_bwd: unknown activation %d", act);
     // ws (orn_stem_bwd_ws_floats): dpre2 [B*Nout] | dpre1 [B*Hd] | dh1 [B*Hd] | partial [CHUNKS*B*Hd], at B == 1 [cdiv(Nout,16)][Hd]
     float *dpre2 = ws;
     float *dpre1 = dpre2 + (size_t)B * Nout;
@@ -237,29 +251,29 @@ int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_strid
         const OrnStemL2Job l2 = {w1, h1, pre2, dh2, dh2_nslab, (size_t)Nout, Hd, Nout, dw1, db1, partial};
         if (defer_l2 && defer_w0) *defer_l2 = l2;      // the caller runs it as trailing work-groups of a later launch (and w0 behind that one)
         else {
-            hipLaunchKernelGGL(k_stem_bwd_l2, dim3(nwg), dim3(256), 0, st, l2);
+            ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_stem_bwd_l2<A>, dim3(nwg), dim3(256), 0, st, l2));
             ORN_LAUNCH_CHECK("stem_bwd_l2");
         }
         if (defer_w0) {      // the caller appends this job to a later launch (orn_stem_w0_row)
             *defer_w0 = OrnStemW0Job{embed, row_idx, row_stride, pre1, partial, nwg, E, Hd, dpre1, dw0, db0};
             return 0;
         }
-        hipLaunchKernelGGL(k_linear_silu_bwd_w_slabs, dim3(Hd), dim3(128), 0, st, embed, row_idx, row_stride, pre1, partial, nwg, E, Hd,
-                           dpre1, dw0, db0);
+        ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_linear_silu_bwd_w_slabs<A>, dim3(Hd), dim3(128), 0, st, embed, row_idx, row_stride, pre1,
+                                                  partial, nwg, E, Hd, dpre1, dw0, db0));
         ORN_LAUNCH_CHECK("stem_bwd_w0");
         return 0;
     }
     ORN_REQUIRE(dh2_nslab == 1, "stem_bwd: gradient slabs need B == 1");
-    hipLaunchKernelGGL(k_linear_silu_bwd_w, dim3(orn_cdiv(Nout, 4)), dim3(256), 0, st, h1, nullptr, 0, pre2, dh2, B, Hd, Nout,
-                       dpre2, dw1, db1);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_linear_silu_bwd_w<A>, dim3(orn_cdiv(Nout, 4)), dim3(256), 0, st, h1, nullptr, 0, pre2, dh2, B,
+                                              Hd, Nout, dpre2, dw1, db1));
     ORN_LAUNCH_CHECK("stem_bwd_w1");
     const int rpc = orn_cdiv(Nout, ORN_STEM_CHUNKS);
     hipLaunchKernelGGL(k_linear_bwd_x_partial, dim3(orn_cdiv(Hd, 128), ORN_STEM_CHUNKS), dim3(128), 0, st, w1, dpre2, B,
                        Hd, Nout, rpc, partial);
     ORN_LAUNCH_CHECK("stem_bwd_x");
     ORN_TRY(orn_launch_reduce_rows(partial, ORN_STEM_CHUNKS, (size_t)B * Hd, (size_t)B * Hd, dh1, st));
-    hipLaunchKernelGGL(k_linear_silu_bwd_w, dim3(orn_cdiv(Hd, 2)), dim3(128), 0, st, embed, row_idx, row_stride, pre1, dh1, B, E, Hd,
-                       dpre1, dw0, db0);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_linear_silu_bwd_w<A>, dim3(orn_cdiv(Hd, 2)), dim3(128), 0, st, embed, row_idx, row_stride, pre1,
+                                              dh1, B, E, Hd, dpre1, dw0, db0));
     ORN_LAUNCH_CHECK("stem_bwd_w0");
     return 0;
 }
@@ -270,14 +284,22 @@ size_t orn_stem_bwd_ws_floats(int B, int Hd, int Nout)
     return (size_t)B * Nout + 2 * (size_t)B * Hd + rows * B * Hd;
 }
 
+extern "C" int orn_stem_bwd_act(const float *embed, const float *w1, const float *pre1, const float *h1,
+                                const float *pre2, const float *dh2, int B, int E, int Hd, int Nout, float *dw0,
+                                float *db0, float *dw1, float *db1, float *ws, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "stem_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(embed && w1 && pre1 && h1 && pre2 && dh2 && dw0 && db0 && dw1 && db1 && ws, "stem_bwd: null pointer");
+    ORN_REQUIRE(B > 0 && E > 0 && Hd > 0 && Nout > 0, "stem_bwd: bad sizes");
+    return orn_launch_stem_bwd(embed, nullptr, 0, w1, pre1, h1, pre2, dh2, B, E, Hd, Nout, dw0, db0, dw1, db1, ws,
+                               (hipStream_t)stream, 1, nullptr, nullptr, act);
+}
+
 extern "C" int orn_stem_bwd(const float *embed, const float *w1, const float *pre1, const float *h1,
                             const float *pre2, const float *dh2, int B, int E, int Hd, int Nout, float *dw0,
                             float *db0, float *dw1, float *db1, float *ws, void *stream)
 {
-    ORN_REQUIRE(embed && w1 && pre1 && h1 && pre2 && dh2 && dw0 && db0 && dw1 && db1 && ws, "stem_bwd: null pointer");
-    ORN_REQUIRE(B > 0 && E > 0 && Hd > 0 && Nout > 0, "stem_bwd: bad sizes");
-    return orn_launch_stem_bwd(embed, nullptr, 0, w1, pre1, h1, pre2, dh2, B, E, Hd, Nout, dw0, db0, dw1, db1, ws,
-                               (hipStream_t)stream, 1, nullptr, nullptr);
+    return orn_stem_bwd_act(embed, w1, pre1, h1, pre2, dh2, B, E, Hd, Nout, dw0, db0, dw1, db1, ws, stream, ORN_ACT_SWISH);
 }
 
 extern "C" size_t orn_stem_bwd_ws_bytes(int B, int Hd, int Nout)
@@ -288,10 +310,11 @@ extern "C" size_t orn_stem_bwd_ws_bytes(int B, int Hd, int Nout)
 
 // test entry point (include/orn_debug.h): the B == 1 form with the upstream gradient as partial rows, launched as the engine's
 // non-deferred path launches it
-extern "C" int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
-                                        const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0,
-                                        float *dw1, float *db1, float *ws, size_t ws_bytes, void *stream)
+extern "C" int orn_debug_stem_bwd_slabs_act(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                                            const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0,
+                                            float *dw1, float *db1, float *ws, size_t ws_bytes, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "debug_stem_bwd_slabs: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(embed && w1 && pre1 && h1 && pre2 && dh2_slabs && dw0 && db0 && dw1 && db1 && ws, "debug_stem_bwd_slabs: null pointer");
     ORN_REQUIRE(nslab >= 1 && E > 0 && Hd > 0 && Nout > 0, "debug_stem_bwd_slabs: bad sizes");
     if (ws_bytes < orn_stem_bwd_ws_bytes(1, Hd, Nout) || (uintptr_t)ws % 4 != 0) {
@@ -300,7 +323,39 @@ extern "C" int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, con
         return ORN_E_WS;
     }
     return orn_launch_stem_bwd(embed, nullptr, 0, w1, pre1, h1, pre2, dh2_slabs, 1, E, Hd, Nout, dw0, db0, dw1, db1, ws,
-                               (hipStream_t)stream, nslab, nullptr, nullptr);
+                               (hipStream_t)stream, nslab, nullptr, nullptr, act);
+}
+
+extern "C" int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                                        const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0,
+                                        float *dw1, float *db1, float *ws, size_t ws_bytes, void *stream)
+{
+    return orn_debug_stem_bwd_slabs_act(embed, w1, pre1, h1, pre2, dh2_slabs, nslab, E, Hd, Nout, dw0, db0, dw1, db1, ws, ws_bytes, stream,
+                                        ORN_ACT_SWISH);
+}
+
+// test entry point (include/orn_debug.h): the four device functions of OrnAct<act> as the kernels call them
+template <int ACT, bool EXACT>
+__global__ void k_act_eval(const float *__restrict__ z, size_t n, float *__restrict__ f, float *__restrict__ df)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = z[i];
+    f[i] = EXACT ? OrnAct<ACT>::f_exact(v) : OrnAct<ACT>::f(v);
+    df[i] = EXACT ? OrnAct<ACT>::df_exact(v) : OrnAct<ACT>::df(v);
+}
+
+extern "C" int orn_debug_act_eval(int act, int exact, const float *z, size_t n, float *f, float *df, void *stream)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_act_eval: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(z && f && df, "debug_act_eval: null pointer");
+    ORN_REQUIRE(n <= ((size_t)1 << 30), "debug_act_eval: %zu values above 2^30", n);
+    if (n == 0) return 0;
+    const dim3 grid(orn_cdiv((long)n, 256));
+    if (exact) ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_act_eval<A, true>), grid, dim3(256), 0, (hipStream_t)stream, z, n, f, df));
+    else ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_act_eval<A, false>), grid, dim3(256), 0, (hipStream_t)stream, z, n, f, df));
+    ORN_LAUNCH_CHECK("act_eval");
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -309,7 +364,7 @@ extern "C" int orn_debug_stem_bwd_slabs(const float *embed, const float *w1, con
 #define ORN_HEAD_MAXC 512
 
 // ZIN: the input is the pre-activation z and a = SiLU(z) is formed here (fp32 engine's training step: the last block stores z only)
-template <int V, bool ZIN = false>
+template <int V, bool ZIN = false, int ACT = ORN_ACT_SWISH>
 __global__ void k_head_fwd(const float *__restrict__ a, const float *__restrict__ w, const float *__restrict__ bias, int C,
                            size_t HW, int sigmoid, float *__restrict__ out)
 {
@@ -336,7 +391,7 @@ __global__ void k_head_fwd(const float *__restrict__ a, const float *__restrict_
         }
         if (ZIN) {
 #pragma unroll
-            for (int v = 0; v < V; ++v) av[v] = orn_silu_exact(av[v]);
+            for (int v = 0; v < V; ++v) av[v] = OrnAct<ACT>::f_exact(av[v]);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -358,14 +413,17 @@ __global__ void k_head_fwd(const float *__restrict__ a, const float *__restrict_
 }
 
 int orn_launch_head_fwd(const float *a, const float *w, const float *b, int B, int C, size_t HW, int sigmoid,
-                        float *out, hipStream_t st, bool z_input)
+                        float *out, hipStream_t st, bool z_input, int act)
 {
     ORN_REQUIRE(C <= ORN_HEAD_MAXC, "head: C=%d > %d unsupported", C, ORN_HEAD_MAXC);
     if (z_input) {
+        ORN_REQUIRE(orn_act_known(act), "head_fwd(z): unknown activation %d", act);
         if (HW % 4 == 0)
-            hipLaunchKernelGGL((k_head_fwd<4, true>), dim3(orn_cdiv((long)HW / 4, 256), B), dim3(256), 0, st, a, w, b, C, HW, sigmoid, out);
+            ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_fwd<4, true, A>), dim3(orn_cdiv((long)HW / 4, 256), B), dim3(256), 0, st, a, w, b, C, HW,
+                                                      sigmoid, out));
         else
-            hipLaunchKernelGGL((k_head_fwd<1, true>), dim3(orn_cdiv((long)HW, 256), B), dim3(256), 0, st, a, w, b, C, HW, sigmoid, out);
+            ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_fwd<1, true, A>), dim3(orn_cdiv((long)HW, 256), B), dim3(256), 0, st, a, w, b, C, HW,
+                                                      sigmoid, out));
         ORN_LAUNCH_CHECK("head_fwd(z)");
         return 0;
     }
@@ -381,14 +439,21 @@ extern "C" int orn_head_fwd(const float *a, const float *w, const float *b, int 
                             float *out, void *stream)
 {
     ORN_REQUIRE(a && w && b && out && B > 0 && C > 0 && H > 0 && W > 0, "head_fwd: bad arguments");
-    return orn_launch_head_fwd(a, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, false);
+    return orn_launch_head_fwd(a, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, false, ORN_ACT_SWISH);   // (`a` given: no activation in it)
+}
+
+extern "C" int orn_debug_head_fwd_z_act(const float *z, const float *w, const float *b, int B, int C, int H, int W, int sigmoid,
+                                        float *out, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_head_fwd_z: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(z && w && b && out && B > 0 && C > 0 && H > 0 && W > 0, "debug_head_fwd_z: bad arguments");
+    return orn_launch_head_fwd(z, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, true, act);
 }
 
 extern "C" int orn_debug_head_fwd_z(const float *z, const float *w, const float *b, int B, int C, int H, int W, int sigmoid,
                                     float *out, void *stream)
 {
-    ORN_REQUIRE(z && w && b && out && B > 0 && C > 0 && H > 0 && W > 0, "debug_head_fwd_z: bad arguments");
-    return orn_launch_head_fwd(z, w, b, B, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, true);
+    return orn_debug_head_fwd_z_act(z, w, b, B, C, H, W, sigmoid, out, stream, ORN_ACT_SWISH);
 }
 
 // Backward.  Block = 256 threads x PPT pixels of one batch item.  du kept in registers; per channel c:
@@ -504,6 +569,7 @@ int orn_launch_head_bwd(const float *a, const float *w, const float *out, const 
 // Block = 256 threads x 2 low-res pixels; partials in fixed order.
 #define HF_PPT 2                      /* 512 low-res pixels per work-group: 450 work-groups at 720p (2048 pixels per work-group left */
 #define HF_THREADS 256                /* half the CUs idle: 306 us) */
+template <int ACT>
 __global__ void __launch_bounds__(HF_THREADS)
 k_head_bwd_fused_f32(const float *__restrict__ z, const float *__restrict__ w, const float *__restrict__ out,
                      const float *__restrict__ dout, int Cn, int H, int W, int sigmoid, float *__restrict__ dy,
@@ -565,10 +631,17 @@ k_head_bwd_fused_f32(const float *__restrict__ z, const float *__restrict__ w, c
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float zz = (q & 1) ? zv[i][q >> 1].y : zv[i][q >> 1].x;
-                const float sg = orn_sigmoid_exact(zz);
-                const float a = zz * sg;                                           // == orn_silu_exact(zz): what the forward's head read
-                const float da = fmaf(w2, du[2][i][q], fmaf(w1, du[1][i][q], w0 * du[0][i][q]));
-                const float dz = da * (sg * (1.0f + zz * (1.0f - sg)));             // orn_silu_grad_exact
+                float a, dz;
+                if constexpr (ACT == ORN_ACT_SWISH) {
+                    const float sg = orn_sigmoid_exact(zz);
+                    a = zz * sg;                                                       // == orn_silu_exact(zz): what the forward's head read
+                    const float da = fmaf(w2, du[2][i][q], fmaf(w1, du[1][i][q], w0 * du[0][i][q]));
+                    dz = da * (sg * (1.0f + zz * (1.0f - sg)));                         // orn_silu_grad_exact
+                } else {
+                    a = OrnAct<ACT>::f_exact(zz);                                      // what the forward's head read
+                    const float da = fmaf(w2, du[2][i][q], fmaf(w1, du[1][i][q], w0 * du[0][i][q]));
+                    dz = da * OrnAct<ACT>::df_exact(zz);
+                }
                 s0 = fmaf(du[0][i][q], a, s0);
                 s1 = fmaf(du[1][i][q], a, s1);
                 s2 = fmaf(du[2][i][q], a, s2);
@@ -627,14 +700,16 @@ __global__ void __launch_bounds__(1024) k_head_partials_finish(const float *__re
 }
 
 int orn_launch_head_bwd_fused_f32(const float *z, const float *w, const float *out, const float *dout, int Cn, int H, int W,
-                                  int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st)
+                                  int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st, int act)
 {
     ORN_REQUIRE(Cn <= ORN_HEAD_MAXC, "head: C=%d > %d unsupported", Cn, ORN_HEAD_MAXC);
+    ORN_REQUIRE(orn_act_known(act), "head_bwd_fused_f32: unknown activation %d", act);
     const int nblk = orn_head_bwd_fused_f32_blocks(H, W);
     const size_t n = 3 * (size_t)Cn + 3;
     const size_t lds = ((size_t)3 * Cn + (size_t)(HF_THREADS / 64) * (7 * Cn + 3)) * sizeof(float);
     float *partial = hws, *red = hws + (size_t)nblk * n;
-    hipLaunchKernelGGL(k_head_bwd_fused_f32, dim3(nblk), dim3(HF_THREADS), lds, st, z, w, out, dout, Cn, H, W, sigmoid, dy, dbp, partial);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_head_bwd_fused_f32<A>, dim3(nblk), dim3(HF_THREADS), lds, st, z, w, out, dout, Cn, H, W, sigmoid, dy,
+                                              dbp, partial));
     ORN_LAUNCH_CHECK("head_bwd_fused_f32");
     (void)red;
     hipLaunchKernelGGL(k_head_partials_finish, dim3(orn_cdiv((long)n, 32)), dim3(1024), 0, st, partial, nblk, (int)n, Cn, dw, db);

@@ -45,6 +45,7 @@ int check_desc(const orn_engine_desc *d)
     ORN_REQUIRE(d, "engine: null desc");
     ORN_REQUIRE(d->n_layers >= 1 && d->n_layers <= ORN_MAX_LAYERS, "engine: n_layers=%d out of range", d->n_layers);
     ORN_REQUIRE(d->precision >= 0 && d->precision <= 2, "engine: precision %d not built", d->precision);
+    ORN_REQUIRE(orn_act_known(d->act), "engine: act = %d is not ORN_ACT_SWISH (0) or ORN_ACT_GELU (1)", d->act);
     ORN_REQUIRE(d->branch_kind == 0 || ((d->branch_kind == ORN_BRANCH_ACB || d->branch_kind == ORN_BRANCH_REPVGG || d->branch_kind == ORN_BRANCH_ECB) && !d->erb),
                 "engine: branch_kind %d (with erb = %d) is not 0 or ORN_BRANCH_ACB / _REPVGG / _ECB with erb = 0", d->branch_kind, d->erb);
     ORN_REQUIRE(d->embed_len > 0 && d->stem_dim > 0 && d->fc_h > 0 && d->fc_w > 0 && d->fc_dim > 0, "engine: bad stem geometry");

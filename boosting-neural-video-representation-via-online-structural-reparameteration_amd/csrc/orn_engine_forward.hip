@@ -12,7 +12,7 @@ static int side_forward(orn_engine *e, int i, const int *frame_idx, hipStream_t 
     const float *w = e->params + d.side_head_w[i], *b = e->params + d.side_head_b[i];
     const size_t HW = (size_t)s.H * s.W;
     if (i >= e->ff)
-        ORN_TRY(e->ops->side_head_fwd(e->L[i].zb, w, b, s.C, HW, d.sigmoid, s.img, st, sc));
+        ORN_TRY(e->ops->side_head_fwd(e->L[i].zb, w, b, s.C, HW, d.sigmoid, s.img, st, sc, d.act));
     else
         ORN_TRY(orn_launch_side_head_fwd_f32(e->L[i].a, w, b, s.C, HW, d.sigmoid, s.img, st, sc));
     return orn_launch_loss(s.img, s.targets, frame_idx, 3 * HW, 1, 3, s.H, s.W, d.loss_type, 1.0f, s.stats, s.dimg, s.loss_ws, st, nullptr, nullptr, sc,
@@ -41,12 +41,12 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
         int pk_par = 0, pk_t = 0;
         const void *pk = (keep_z && ms.mh_host) ? orn_merge_h16_pack(ms.mh_host, &pk_par, &pk_t) : nullptr;
         ORN_TRY(orn_launch_w2_transpose(ms.n, ms.ml, st, pk, pk_par));
-        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 0, ms.tiles[0], lin1, st));
-        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], lin2, st, e->stage0 ? nullptr : pk, e->stage0 ? 0 : pk_t));
+        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 0, ms.tiles[0], lin1, st, nullptr, 0, d.act));
+        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], lin2, st, e->stage0 ? nullptr : pk, e->stage0 ? 0 : pk_t, d.act));
         pack_t = e->stage0 ? pk : nullptr; pack_t_blocks = e->stage0 ? pk_t : 0;
     } else {
-        ORN_TRY(orn_launch_linear_silu(lin1.x, lin1.row_idx, lin1.row_stride, lin1.w, lin1.bias, 1, lin1.K, lin1.N, lin1.pre, lin1.y, st));
-        ORN_TRY(orn_launch_linear_silu(lin2.x, nullptr, 0, lin2.w, lin2.bias, 1, lin2.K, lin2.N, lin2.pre, lin2.y, st));
+        ORN_TRY(orn_launch_linear_silu(lin1.x, lin1.row_idx, lin1.row_stride, lin1.w, lin1.bias, 1, lin1.K, lin1.N, lin1.pre, lin1.y, st, d.act));
+        ORN_TRY(orn_launch_linear_silu(lin2.x, nullptr, 0, lin2.w, lin2.bias, 1, lin2.K, lin2.N, lin2.pre, lin2.y, st, d.act));
     }
     if (e->nbr && merge) ORN_TRY(orn_launch_branch_merge_fwd(e->nbr, e->bl, st));      // ACB / RepVGG / ECB: (wf, bf) of every block, one launch
     if (ff < nl && !d.erb && merge) {      // 16-bit operand copies of every fast layer's kernel, one launch (ERB: written by the merge's S launch)
@@ -67,14 +67,15 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
                 if (d.erb && merge)
                     for (int j = ff; j < (set == 1 ? nl - 1 : nl); ++j) pl[np++] = prep_layer(e, j);
                 ORN_TRY(orn_launch_stage0_fwd(x, b.wf, b.bf, l.C, l.O, l.H, l.W, l.s, keep_z ? b.z : nullptr, e->L[1].xpad, ORN_FAST_C,
-                                              d.precision, st, np, pl, pack_t, pack_t_blocks));
+                                              d.precision, st, np, pl, pack_t, pack_t_blocks, d.act));
             }
             else
             {
                 // fp32 engine, training step, last block: nothing but the head reads its activation, and the head's backward is fused with
                 // this block's (it reads z): store z only and let the head's forward form SiLU(z) (354 MB less written at 720p)
                 const bool z_only = keep_z && i == nl - 1 && f32_head_on_z(e);
-                ORN_TRY(orn_launch_conv3x3_f32(x, b.wf, b.bf, 1, l.C, l.O, l.H, l.W, l.s, 1, keep_z ? b.z : nullptr, z_only ? nullptr : b.a, st, nullptr));
+                ORN_TRY(orn_launch_conv3x3_f32(x, b.wf, b.bf, 1, l.C, l.O, l.H, l.W, l.s, 1, keep_z ? b.z : nullptr, z_only ? nullptr : b.a, st, nullptr,
+                                               d.act));
             }
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
             x = b.a;
@@ -87,19 +88,20 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
             if (e->side_busy && i + 3 == nl && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));   // (this conv overwrites the input of the block below the last)
             if (e->side_busy && i + 2 == nl) ORN_HIP(hipStreamWaitEvent(st, e->ev_wgrad, 0));
             if (e->side_busy && last) { ORN_HIP(hipStreamWaitEvent(st, e->ev_join, 0)); e->side_busy = false; }
-            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C));
+            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C, d.act));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
         }
         if (side_sc && i + 1 < nl) ORN_TRY(side_forward(e, i, row_idx, st, side_sc));
     }
     if (ff < nl) {
         if (head)
-            ORN_TRY(e->ops->head_fwd(e->L[nl - 1].zb, P + d.head_w, P + d.head_b, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img, st));
+            ORN_TRY(e->ops->head_fwd(e->L[nl - 1].zb, P + d.head_w, P + d.head_b, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img, st,
+                                     d.act));
     } else
     {
         const bool z_only = keep_z && f32_head_on_z(e);
         ORN_TRY(orn_launch_head_fwd(z_only ? e->L[nl - 1].z : x, P + d.head_w, P + d.head_b, 1, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img,
-                                    st, z_only));
+                                    st, z_only, d.act));
     }
     return 0;
 }
@@ -135,7 +137,8 @@ static int decode_frames(orn_engine *e, const float *embeds, const int32_t *rows
         const OrnDecodeOut o = {targets, rows + k, rgb8 ? rgb8 + (size_t)k * HW * 3 : nullptr, planes,
                                 stats ? stats + (size_t)k * 4 : nullptr, e->dec_ws};
         if (fast)
-            ORN_TRY(e->ops->decode_out(e->L[d.n_layers - 1].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st));
+            ORN_TRY(e->ops->decode_out(e->L[d.n_layers - 1].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st,
+                                       d.act));
         else
             ORN_TRY(orn_launch_decode_out_f32(e->img, HW, o, st));
         if (msssim && ((k + 1) % chunk == 0 || k + 1 == n)) {

@@ -98,7 +98,7 @@ static int side_backward(orn_engine *e, int i, hipStream_t st, OrnScaleState *sc
     float *dw = e->grads + d.side_head_w[i], *db = e->grads + d.side_head_b[i];
     if (i >= e->ff)
         return e->ops->side_head_bwd(e->L[i].zb, w, s.img, s.dimg, s.C, s.H, s.W, d.sigmoid, d.layer[i].s, d.lw, e->gs, e->L[i].dypad, dw, db,
-                                     s.head_ws, st, sc);
+                                     s.head_ws, st, sc, d.act);
     return orn_launch_side_head_bwd_f32(e->L[i].a, w, s.img, s.dimg, s.C, s.H, s.W, d.sigmoid, d.lw, e->L[i].da, dw, db, s.head_ws, st, sc);
 }
 
@@ -128,15 +128,15 @@ static int side_branch_backward(orn_engine *e, hipStream_t st)
     ORN_HIP(hipStreamWaitEvent(sd, e->ev_fork, 0));
     if (e->side_below) {      // (its dy is the output of the dgrad launch this branch forks behind; its slabs are reduced on the caller's stream)
         const OrnWgradJob wb = wgrad_job(e, nl - 2);
-        ORN_TRY(e->ops->wgrad_batch(1, &wb, sd, nullptr, nullptr, 1));
+        ORN_TRY(e->ops->wgrad_batch(1, &wb, sd, nullptr, nullptr, 1, d.act));
         ORN_HIP(hipEventRecord(e->ev_below, sd));
     }
     const OrnWgradJob wj = wgrad_job(e, nl - 1);
     const OrnHeadFinish hf = {e->head_ws, e->ops->head_bwd_blocks(e->Hout, e->Wout), e->Cn_last, 1.0f / e->gs, G + d.head_w, G + d.head_b, sc};
-    ORN_TRY(e->ops->wgrad_batch(1, &wj, sd, &hf, nullptr, 1));
+    ORN_TRY(e->ops->wgrad_batch(1, &wj, sd, &hf, nullptr, 1, d.act));
     ORN_HIP(hipEventRecord(e->ev_wgrad, sd));           // the last block's input buffer is free again
     const OrnWgradReduce wr = wgrad_reduce(e, nl - 1, sc);
-    ORN_TRY(e->ops->wgrad_reduce_all(1, &wr, sd, nullptr));
+    ORN_TRY(e->ops->wgrad_reduce_all(1, &wr, sd, nullptr, d.act));
     if (d.erb) {
         const orn_engine::MergeSet &ms = e->mset[2];
         ORN_TRY(orn_launch_merge_h16_bwd(ms.mh_tables, ms.mh_host, sd, sc));
@@ -165,8 +165,8 @@ static int side_branch_update(orn_engine *e, bool more)
         const orn_engine::MergeSet &ms = e->mset[2];
         const OrnLinearJob none = {};
         ORN_TRY(orn_launch_w2_transpose(ms.n, ms.ml, sd));
-        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 0, ms.tiles[0], none, sd));
-        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], none, sd));   // the S epilogue writes the 16-bit operand copies
+        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 0, ms.tiles[0], none, sd, nullptr, 0, d.act));
+        ORN_TRY(orn_launch_merge_group_linear(ms.tables, 1, ms.tiles[1], none, sd, nullptr, 0, d.act));   // the S epilogue writes the 16-bit operand copies
         packs = ms.mh_host;
     } else if (more) {
         const OrnPrepLayer pl = prep_layer(e, nl - 1);
@@ -202,13 +202,13 @@ static int fast_weight_grads(orn_engine *e, hipStream_t st, bool pipe, OrnScaleS
     }
     const OrnHeadFinish hf = {e->head_ws, e->ops->head_bwd_blocks(e->Hout, e->Wout), e->Cn_last, 1.0f / e->gs, e->grads + d.head_w, e->grads + d.head_b, sc};
     if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS], st);
-    ORN_TRY(e->ops->wgrad_batch(nj, wj, st, pipe ? nullptr : &hf, l2job, 0));
+    ORN_TRY(e->ops->wgrad_batch(nj, wj, st, pipe ? nullptr : &hf, l2job, 0, d.act));
     if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 1], st);
     OrnWgradReduce wr[ORN_MAX_LAYERS];
     for (int i = ff; i < n_main; ++i) wr[i - ff] = wgrad_reduce(e, i, sc);
     if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 2], st);
     if (pipe && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));
-    ORN_TRY(e->ops->wgrad_reduce_all(n_main - ff, wr, st, w0job));
+    ORN_TRY(e->ops->wgrad_reduce_all(n_main - ff, wr, st, w0job, d.act));
     if (e->prof) (void)hipEventRecord(e->prof_ev[4 * ORN_MAX_LAYERS + 3], st);
     return 0;
 }
@@ -287,7 +287,7 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
     if (pipe) { fin.cur_copy = e->cur_side; fin.sc_copy = e->sc_side; }     // (the previous step's side branch was joined in forward())
     if (ff < nl)
         ORN_TRY(e->ops->head_bwd(e->L[nl - 1].zb, P + d.head_w, e->img, dimg, e->Cn_last, e->Hout, e->Wout, d.sigmoid,
-                                 d.layer[nl - 1].s, e->gs, e->L[nl - 1].dypad, nullptr, nullptr, e->head_ws, st, sc, &fin));   // dW / db: finished with the wgrad batch
+                                 d.layer[nl - 1].s, e->gs, e->L[nl - 1].dypad, nullptr, nullptr, e->head_ws, st, sc, &fin, d.act));   // dW / db: finished with the wgrad batch
     const bool head_fused32 = f32_head_on_z(e);
     const OrnHeadBwdFuse hfuse = {P + d.head_w, e->img, dimg, d.sigmoid, G + d.head_w, G + d.head_b, e->head_ws};
     if (ff >= nl && !head_fused32)
@@ -312,9 +312,9 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
                 // few pixel tiles: input-chunk split through fp32 partial slabs in the scratch, finished into dypad
                 float *part = e->ops->dgrad_f32_slabs(l.H, l.W, l.O) > 1 ? e->scratch : nullptr;
                 ORN_TRY(e->ops->conv_dgrad(b.dypad, b.wd, l.H, l.W, l.O, l.C, e->L[i - 1].zb, e->L[i - 1].dypad, d.layer[i - 1].s,
-                                           part, st, l.C));
+                                           part, st, l.C, d.act));
             } else {
-                ORN_TRY(e->ops->conv_dgrad(b.dypad, b.wd, l.H, l.W, l.O, ORN_FAST_C, nullptr, nullptr, 1, e->dxn, st, l.C));
+                ORN_TRY(e->ops->conv_dgrad(b.dypad, b.wd, l.H, l.W, l.O, ORN_FAST_C, nullptr, nullptr, 1, e->dxn, st, l.C, d.act));
                 if (!e->stage0)
                 ORN_TRY(e->ops->to_nchw_f32(e->dxn, l.C, ORN_FAST_C, l.H, l.W, e->ops->dgrad_f32_slabs(l.H, l.W, l.O), 1.0f / e->gs, dx,
                                             st, sc));
@@ -322,10 +322,10 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
         } else if (e->stage0) {
             const orn_layer_desc &l1 = d.layer[1];
             ORN_TRY(orn_launch_stage0_bwd(x, b.wf, b.z, e->dxn, e->ops->dgrad_f32_slabs(l1.H, l1.W, l1.O), ORN_FAST_C, 1.0f / e->gs, l.C, l.O,
-                                          l.H, l.W, l.s, e->scratch + e->stem_ws, nullptr, G + l.w3x3, G + l.b3x3, st, sc));
+                                          l.H, l.W, l.s, e->scratch + e->stem_ws, nullptr, G + l.w3x3, G + l.b3x3, st, sc, d.act));
         } else
         ORN_TRY(orn_launch_conv_bwd_f32(x, b.wf, b.z, b.da, 1, l.C, l.O, l.H, l.W, l.s, dx, G + l.w3x3, G + l.b3x3, e->scratch, st,
-                                        (i == nl - 1 && head_fused32) ? &hfuse : nullptr, ff >= nl ? b.wd32 : nullptr));
+                                        (i == nl - 1 && head_fused32) ? &hfuse : nullptr, ff >= nl ? b.wd32 : nullptr, d.act));
         if (e->prof) (void)hipEventRecord(e->prof_ev[2 * ORN_MAX_LAYERS + 2 * i + 1], st);
         if (pipe && e->fork_behind_dgrad && i == nl - 1) ORN_TRY(side_branch_backward(e, st));     // fork: behind the last block's dgrad
         // multi-resolution heads: block i - 1's gradient buffer holds what this block sent down; its stage's head adds its own term
@@ -338,7 +338,8 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
     ORN_TRY(orn_launch_stem_bwd(embeds, fidx, d.embed_len, P + d.stem_w1, e->pre1, e->h1, e->pre2,
                                 e->stage0 ? e->scratch + e->stem_ws : e->dh2, 1, d.embed_len, d.stem_dim, Nout, G + d.stem_w0,
                                 G + d.stem_b0, G + d.stem_w1, G + d.stem_b1, e->scratch, st,
-                                e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr));
+                                e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr,
+                                d.act));
     if (ff < nl) ORN_TRY(fast_weight_grads(e, st, pipe, sc, &l2job, &w0job));
     if (pipe && !e->fork_behind_dgrad) ORN_TRY(side_branch_backward(e, st));     // fork: behind the lower blocks' slab reduction
     if (d.multi_res) {      // (behind the head's backward, which carries a 16-bit engine's loss finalize: the step's -- or, batched, the frame's -- record exists)

@@ -139,11 +139,12 @@ static inline unsigned conv_magic(int d)
 // output kernel of orn_decode_out.hip share it, so their fp32 results are bit-identical): 4 lanes per pixel, lane `sub` holds the
 // 8-channel groups q*4 + sub.  sw: LDS copy of W [3][C] followed by the three biases.
 #define HB_MAXC 256
+template <int ACT = ORN_ACT_SWISH>
 __device__ __forceinline__ void head_accum8(const h16x8 v, int c0, int C, const float *sw, float &a0, float &a1, float &a2)
 {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float a = orn_silu((float)v[e]);
+        const float a = OrnAct<ACT>::f((float)v[e]);
         a0 = fmaf(sw[c0 + e], a, a0);
         a1 = fmaf(sw[C + c0 + e], a, a1);
         a2 = fmaf(sw[2 * C + c0 + e], a, a2);
@@ -165,30 +166,35 @@ __device__ __forceinline__ float head_act(float a0, float a1, float a2, int sub,
 // ---- launchers and switches that one file of the path defines and another calls ------------------------------------------
 // orn_conv_fwd_bf16.hip.  c_real: input channels that are not zero padding (<= Cin)
 int orn_launch_conv_bf16_fwd(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
-                             h16 *z, h16 *apad, hipStream_t st, int c_real);
+                             h16 *z, h16 *apad, hipStream_t st, int c_real, int act);
 void set_debug_fwd(int flags);
 void set_stamps_fwd(void *buf);       // (-DORN_CONV_STAMP builds)
 // orn_conv_bf16.hip
 int orn_dgrad_f32_slabs(int H, int W, int O);
 int orn_launch_conv_bf16_dgrad(const h16 *dypad, const h16 *wd, int H, int W, int O, int C, const h16 *zprev,
-                               h16 *dyprev, int sp, float *dx_f32, hipStream_t st, int c_real);
+                               h16 *dyprev, int sp, float *dx_f32, hipStream_t st, int c_real, int act);
 // orn_conv2_bf16.hip
-int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st);
-int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st);
+int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, int W, int O, int s, h16 *z, h16 *apad, hipStream_t st,
+                    int act);
+int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st,
+                      int act);
 // orn_wgrad_bf16.hip
 size_t orn_wgrad_bf16_ws_floats(int H, int W, int O);
 int orn_launch_wgrad_bf16(const h16 *xpad, const h16 *dypad, int H, int W, int C, int O, int s, float gscale,
                           float *slabs, float *dwf, float *dbf, hipStream_t st);
-int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side);
-int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0);
+int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side,
+                                int act);      // act: of the stem job it carries
+int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0, int act);
 int orn_launch_head_finish_bf16(const float *partial, int blocks, int C, float gscale, float *dw, float *db, hipStream_t st);
 void set_debug_wgrad(int flags);
 // orn_decode_out.hip
-int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
+int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st,
+                              int act);
 // orn_side_head.hip
 int orn_launch_side_head_fwd_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
-                                 OrnScaleState *sc);
+                                 OrnScaleState *sc, int act);
 int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
-                                 int sp, float lw, float gs, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
+                                 int sp, float lw, float gs, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc,
+                                 int act);
 
 }  // namespace HNS

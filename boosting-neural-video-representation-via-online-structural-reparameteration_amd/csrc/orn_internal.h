@@ -4,16 +4,18 @@
 
 // orn_elementwise.hip
 int orn_launch_linear_silu(const float *x, const int *row_idx, size_t row_stride, const float *w, const float *b,
-                           int B, int K, int N, float *pre, float *y, hipStream_t st);
+                           int B, int K, int N, float *pre, float *y, hipStream_t st, int act);
 int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_stride, const float *w1, const float *pre1,
                         const float *h1, const float *pre2, const float *dh2, int B, int E, int Hd, int Nout,
-                        float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab = 1,
-                        OrnStemW0Job *defer_w0 = nullptr,    // defer_w0 (B == 1): the last kernel is returned as a job instead of launched
-                        OrnStemL2Job *defer_l2 = nullptr);   // defer_l2 (with defer_w0): so is the first one (it then has to run in an EARLIER launch than w0)
+                        float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab,
+                        OrnStemW0Job *defer_w0,    // defer_w0 (B == 1): the last kernel is returned as a job instead of launched
+                        OrnStemL2Job *defer_l2,    // defer_l2 (with defer_w0): so is the first one (it then has to run in an EARLIER launch than w0)
+                        int act);            // ORN_ACT_*; a deferred job must be run by a launch instantiated for the same one
 // dh2_nslab > 1 (B == 1): dh2 holds that many partial rows of Nout floats, summed in fixed order by the first kernel
 size_t orn_stem_bwd_ws_floats(int B, int Hd, int Nout);
 int orn_launch_head_fwd(const float *a, const float *w, const float *b, int B, int C, size_t HW, int sigmoid,
-                        float *out, hipStream_t st, bool z_input = false);   // z_input: `a` holds the pre-activation, SiLU is applied here
+                        float *out, hipStream_t st, bool z_input,    // z_input: `a` holds the pre-activation, the activation is applied here
+                        int act);
 int orn_launch_head_bwd(const float *a, const float *w, const float *out, const float *dout, int B, int C, size_t HW,
                         int sigmoid, float *da, float *dw, float *db, float *ws, hipStream_t st);
 int orn_launch_adam(float *p, const float *g, float *m, float *v, size_t n, double lr, int step, const OrnStepCur *sp,
@@ -38,11 +40,13 @@ bool orn_stage0_supported(int C, int O, int H, int W, int s);
 int orn_stage0_slabs(int O, int s);
 struct OrnPrepLayer;      // (below) 16-bit operand copies of later blocks' kernels, written by rider work-groups of this launch
 int orn_launch_stage0_fwd(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
-                          void *xpad_next, int Cp, int precision, hipStream_t st, int n_prep = 0, const OrnPrepLayer *prep = nullptr,
-                          const void *pack = nullptr, int pack_t_blocks = 0);   // pack: the merge backward's T -> Th copies as further riders
+                          void *xpad_next, int Cp, int precision, hipStream_t st, int n_prep, const OrnPrepLayer *prep,
+                          const void *pack, int pack_t_blocks,    // pack: the merge backward's T -> Th copies as further riders
+                          int act);
 int orn_launch_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs, int C,
                           int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, hipStream_t st,
-                          const OrnScaleState *sc = nullptr);   // sc: 1/scale from the device state instead of inv_gs
+                          const OrnScaleState *sc,    // sc: 1/scale from the device state instead of inv_gs
+                          int act);
 
 // orn_merge.hip
 int orn_launch_merge_fwd(const float *w3x3, const float *b3x3, const float *w3x1, const float *b3x1,
@@ -76,7 +80,8 @@ int orn_launch_w2_transpose(int n_layers, const OrnMergeLayer *L, hipStream_t st
 int orn_merge_groups_build(void *dev_tables, int n_layers, const OrnMergeLayer *L, bool fp32_bwd, int tiles[4]);
 int orn_launch_merge_group(const void *dev_tables, int which, int tiles, hipStream_t st);   // which = 2 / 3 (fp32 engine)
 int orn_launch_merge_group_linear(const void *dev_tables, int which, int tiles, const OrnLinearJob &job, hipStream_t st,
-                                  const void *pack = nullptr, int pack_blocks = 0);   // pack: trailing T -> Th pack jobs (orn_merge_h16_pack)
+                                  const void *pack, int pack_blocks,    // pack: trailing T -> Th pack jobs (orn_merge_h16_pack)
+                                  int act);                           // act: of the linear job
 
 // orn_merge_h16.hip: merge backward GEMMs of the 16-bit engine modes (packed half operands, fragments from global)
 size_t orn_merge_h16_layer_halfs(int C, int O);
@@ -112,16 +117,17 @@ int orn_launch_branch_merge_bwd(int n, const OrnBranchLayer *L, hipStream_t st);
 
 // orn_conv_f32.hip
 int orn_launch_conv3x3_f32(const float *x, const float *w, const float *bias, int B, int C, int O, int H, int W,
-                           int s, int epi, float *z, float *out, hipStream_t st, float *split_ws);
+                           int s, int epi, float *z, float *out, hipStream_t st, float *split_ws, int act);
 // head: fp32 engine only -- the last block's backward starts from the head's (out, dout) instead of da (orn_launch_head_bwd_fused_f32)
 struct OrnHeadBwdFuse { const float *w, *out, *dout; int sigmoid; float *dw, *db, *hws; };
 int orn_launch_conv_bwd_f32(const float *x, const float *wf, const float *z, const float *da, int B, int C, int O,
                             int H, int W, int s, float *dx, float *dwf, float *dbf, float *ws, hipStream_t st,
-                            const OrnHeadBwdFuse *head = nullptr, const float *wd_ready = nullptr);   // wd_ready: the flipped / transposed kernel, already made
+                            const OrnHeadBwdFuse *head, const float *wd_ready,    // wd_ready: the flipped / transposed kernel, already made
+                            int act);
 int orn_launch_flip_transpose_all(int n, const float *const *wf, float *const *wd, const int *O, const int *C, hipStream_t st);
 int orn_head_bwd_fused_f32_blocks(int H, int W);
 int orn_launch_head_bwd_fused_f32(const float *z, const float *w, const float *out, const float *dout, int Cn, int H, int W,
-                                  int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st);
+                                  int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st, int act);
 
 // orn_side_head.hip: the heads of the stages below the last one (multi-resolution engine; include/orn.h, N8).  16-bit entries
 // (OrnHalfOps::side_head_fwd / _bwd): z is the block's channels-last pre-activation, dypad its padded un-shuffled gradient buffer,
@@ -225,28 +231,28 @@ struct OrnDecodeOut { const float *targets; const int32_t *row; uint8_t *rgb8; f
 int orn_launch_decode_out_f32(const float *src, size_t HW, const OrnDecodeOut &o, hipStream_t st);
 struct OrnHalfOps {
     int (*conv_fwd)(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s, void *z, void *apad,
-                    hipStream_t st, int c_real);   // c_real <= Cin: input channels that are not zero padding
+                    hipStream_t st, int c_real, int act);   // c_real <= Cin: input channels that are not zero padding; act: ORN_ACT_* (here and below)
     int (*conv_dgrad)(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev, void *dyprev, int sp,
-                      float *dx_f32, hipStream_t st, int c_real);   // c_real: output channels that are not zero padding
+                      float *dx_f32, hipStream_t st, int c_real, int act);   // c_real: output channels that are not zero padding
     size_t (*wgrad_ws_floats)(int H, int W, int O);
-    int (*wgrad_batch)(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side);   // side: launched on the engine's side stream (default wave priority)   // several layers' slabs in one launch (+ optional head finish, + the stem backward's first kernel)
-    int (*wgrad_reduce_all)(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0);   // all layers' reductions in one launch (+ the stem backward's last kernel)
+    int (*wgrad_batch)(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side, int act);   // side: launched on the engine's side stream (default wave priority)   // several layers' slabs in one launch (+ optional head finish, + the stem backward's first kernel)
+    int (*wgrad_reduce_all)(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0, int act);   // all layers' reductions in one launch (+ the stem backward's last kernel)
     int (*prep_all)(int n, const OrnPrepLayer *L, hipStream_t st);
     int (*to_nhwc)(const float *src, int C, int Cp, int H, int W, void *dst, hipStream_t st);
     int (*to_nchw_f32)(const float *src, int C, int Cp, int H, int W, int nslab, float scale, float *dst, hipStream_t st, const OrnScaleState *sc);
     int (*dgrad_f32_slabs)(int H, int W, int O);
-    int (*head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st);
+    int (*head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, int act);
     size_t (*head_bwd_ws_floats)(int C);
     int (*head_bwd_blocks)(int H, int W);
     int (*head_bwd)(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp,
                     float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc,
-                    const OrnLossFinalJob *fin);   // sc: gs from the device state; fin (optional): the loss's finalize stage as one more work-group
+                    const OrnLossFinalJob *fin, int act);   // sc: gs from the device state; fin (optional): the loss's finalize stage as one more work-group
     // decode: head forward on z + the output stage above in one kernel (same per-pixel arithmetic as head_fwd)
-    int (*decode_out)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st);
+    int (*decode_out)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st, int act);
     // multi-resolution engine: the head of a stage below the last (orn_side_head.hip, above)
-    int (*side_head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc);
+    int (*side_head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc, int act);
     int (*side_head_bwd)(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp, float lw,
-                         float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc);
+                         float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc, int act);
 };
 const OrnHalfOps *orn_half_ops_bf16();
 const OrnHalfOps *orn_half_ops_f16();

@@ -449,6 +449,7 @@ __global__ void __launch_bounds__(256) k_gemm_f32_grouped(const GemmGroup *__res
 
 // The same launch with one of the stem's linear layers riding along as trailing work-groups (4 output neurons each): the
 // stem and the merge are independent latency-bound chains at the head of the step, and a graph node costs ~5 us by itself.
+template <int ACT>      // the activation of the stem layer it carries (the GEMM tiles and the pack jobs evaluate none)
 __global__ void __launch_bounds__(256) k_gemm_f32_grouped_linear(const GemmGroup *__restrict__ g, OrnLinearJob job, int gemm_tiles, int lin_blocks,
                                                                  MhPackAll pack)
 {
@@ -469,7 +470,7 @@ __global__ void __launch_bounds__(256) k_gemm_f32_grouped_linear(const GemmGroup
     if ((int)blockIdx.x >= gemm_tiles) {
 #pragma unroll 1
         for (int r = 0; r < G2_LIN_ROUNDS; ++r)
-            orn_linear_silu_wave(job, ((blockIdx.x - gemm_tiles) * G2_LIN_ROUNDS + r) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+            orn_linear_silu_wave<ACT>(job, ((blockIdx.x - gemm_tiles) * G2_LIN_ROUNDS + r) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
         return;
     }
     int local;
@@ -833,14 +834,16 @@ int orn_launch_merge_group(const void *dev_tables, int which, int tiles, hipStre
 
 // fp32 groups only (which = 0 / 1: the forward merge)
 int orn_launch_merge_group_linear(const void *dev_tables, int which, int tiles, const OrnLinearJob &job, hipStream_t st, const void *pack,
-                                  int pack_blocks)
+                                  int pack_blocks, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "merge_group_linear: unknown activation %d", act);
     const GemmGroup *g = (const GemmGroup *)dev_tables + which;
     const int lin_blocks = orn_cdiv(job.N, 4 * G2_LIN_ROUNDS);
     const size_t smem = G2_LDS_BYTES(which == 0 ? 1 : 0) > 64 * 65 * 4 ? G2_LDS_BYTES(which == 0 ? 1 : 0) : 64 * 65 * 4;
     MhPackAll pk = {};
     if (pack && pack_blocks > 0) pk = *(const MhPackAll *)pack; else pack_blocks = 0;
-    hipLaunchKernelGGL(k_gemm_f32_grouped_linear, dim3(tiles + lin_blocks + pack_blocks), dim3(256), smem, st, g, job, tiles, lin_blocks, pk);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_gemm_f32_grouped_linear<A>, dim3(tiles + lin_blocks + pack_blocks), dim3(256), smem, st, g, job, tiles,
+                                              lin_blocks, pk));
     ORN_LAUNCH_CHECK("merge_group_linear");
     return 0;
 }

@@ -159,6 +159,7 @@ int orn_launch_nhwc_to_nchw_f32(const float *src, int C, int Cp, int H, int W, i
 //   a = SiLU(z);  u = W a + b;  out = (tanh u + 1)/2 | sigmoid u           out: fp32 NCHW [3][H][W]
 // 4 lanes per pixel (C/4 channels each, 16-byte loads), 16 pixels per wave: fully coalesced.
 // ================================================================================================
+template <int ACT>
 __global__ void __launch_bounds__(256)
 k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ bias, int C, size_t HW,
                      int sigmoid, float *__restrict__ out)
@@ -192,7 +193,7 @@ k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
                     if (q < nq) vn[q] = *reinterpret_cast<const h16x8 *>(z + pnx * C + (q * 4 + sub) * 8);
             }
         }
-        auto proc = [&](const h16x8 v, int c0) { head_accum8(v, c0, C, sw, a0, a1, a2); };
+        auto proc = [&](const h16x8 v, int c0) { head_accum8<ACT>(v, c0, C, sw, a0, a1, a2); };
         if (piped) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -207,7 +208,7 @@ k_head_fwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
 
 // Backward: du = dout * act'(out); dz = (W^T du) * SiLU'(z) -> previous-layer dypad layout (bf16);
 // dW[k][c] += du[k]*SiLU(z[c]); db[k] += du[k].  partial[blk][3*C+3], reduced afterwards.
-template <int NQ>
+template <int NQ, int ACT>
 __global__ void __launch_bounds__(256)
 k_head_bwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ out,
                      const float *__restrict__ dout, int H, int W, int sigmoid, int sp, float gs_up, h16 *__restrict__ dypad,
@@ -274,10 +275,17 @@ k_head_bwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float zz = (float)v[e];
-                const float sg = orn_sigmoid(zz);
-                const float a = zz * sg;
-                const float da = fmaf(sw[2 * C + c0 + e], du[2], fmaf(sw[C + c0 + e], du[1], sw[c0 + e] * du[0]));
-                o8[e] = (h16)(da * (sg * (1.0f + zz * (1.0f - sg))));
+                float a;
+                if constexpr (ACT == ORN_ACT_SWISH) {
+                    const float sg = orn_sigmoid(zz);
+                    a = zz * sg;
+                    const float da = fmaf(sw[2 * C + c0 + e], du[2], fmaf(sw[C + c0 + e], du[1], sw[c0 + e] * du[0]));
+                    o8[e] = (h16)(da * (sg * (1.0f + zz * (1.0f - sg))));
+                } else {
+                    a = OrnAct<ACT>::f(zz);
+                    const float da = fmaf(sw[2 * C + c0 + e], du[2], fmaf(sw[C + c0 + e], du[1], sw[c0 + e] * du[0]));
+                    o8[e] = (h16)(da * OrnAct<ACT>::df(zz));
+                }
                 dwacc[q][e][0] = fmaf(du[0], a, dwacc[q][e][0]);
                 dwacc[q][e][1] = fmaf(du[1], a, dwacc[q][e][1]);
                 dwacc[q][e][2] = fmaf(du[2], a, dwacc[q][e][2]);
@@ -319,12 +327,13 @@ k_head_bwd_nhwc_bf16(const h16 *__restrict__ z, const float *__restrict__ w, con
 
 #define HB_BLOCKS 512
 
-int orn_launch_head_fwd_bf16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st)
+int orn_launch_head_fwd_bf16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "head_bf16: unknown activation %d", act);
     ORN_REQUIRE(C % 32 == 0 && C <= HB_MAXC, "head_bf16: unsupported C=%d", C);
     int blocks = orn_cdiv((long)HW, 64);
     if (blocks > 8192) blocks = 8192;           // measured: 8192 beats 2048 by ~7 us at 720p
-    hipLaunchKernelGGL(k_head_fwd_nhwc_bf16, dim3(blocks), dim3(256), 0, st, z, w, b, C, HW, sigmoid, out);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_head_fwd_nhwc_bf16<A>, dim3(blocks), dim3(256), 0, st, z, w, b, C, HW, sigmoid, out));
     ORN_LAUNCH_CHECK("head_fwd_bf16");
     return 0;
 }
@@ -334,9 +343,10 @@ int orn_head_bwd_bf16_blocks(int H, int W) { const int b = orn_cdiv((long)H * W,
 
 // gs_up: gradient scale carried by dypad (1 for bf16, 2^20 for fp16); dw/db are un-scaled here
 int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
-                             int sp, float gs_up, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc = nullptr,
-                             const OrnLossFinalJob *fin = nullptr)
+                             int sp, float gs_up, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc,
+                             const OrnLossFinalJob *fin, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "head_bwd_bf16: unknown activation %d", act);
     ORN_REQUIRE(C == 96 || C == 32 || C == 64 || C == 128, "head_bwd_bf16: unsupported C=%d", C);
     ORN_REQUIRE(H % sp == 0 && W % sp == 0, "head_bwd_bf16: H,W not divisible by stride");
     int blocks = orn_cdiv((long)H * W, 64);
@@ -346,10 +356,10 @@ int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, con
     if (fin) fj = *fin;
     const int nfin = (fin && fin->n_l1 > 0) ? 1 : 0;
     switch (C) {
-    case 32: hipLaunchKernelGGL(k_head_bwd_nhwc_bf16<1>, dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks); break;
-    case 64: hipLaunchKernelGGL(k_head_bwd_nhwc_bf16<2>, dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks); break;
-    case 96: hipLaunchKernelGGL(k_head_bwd_nhwc_bf16<3>, dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks); break;
-    default: hipLaunchKernelGGL(k_head_bwd_nhwc_bf16<4>, dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks); break;
+    case 32: ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_bwd_nhwc_bf16<1, A>), dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks)); break;
+    case 64: ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_bwd_nhwc_bf16<2, A>), dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks)); break;
+    case 96: ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_bwd_nhwc_bf16<3, A>), dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks)); break;
+    default: ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_head_bwd_nhwc_bf16<4, A>), dim3(blocks + nfin), dim3(256), 0, st, z, w, out, dout, H, W, sigmoid, sp, gs_up, dypad, partial, sc, fj, blocks)); break;
     }
     ORN_LAUNCH_CHECK("head_bwd_bf16");
     if (!dw) return 0;                  // deferred: rides along orn_launch_wgrad_bf16_batch (OrnHeadFinish)
@@ -358,27 +368,29 @@ int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, con
 
 // ---- type-erased operation table for the engine (one per compiled element type) -----------------------
 static int a_conv_fwd(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s, void *z, void *apad,
-                      hipStream_t st, int c_real)
-{ return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad, st, c_real); }
+                      hipStream_t st, int c_real, int act)
+{ return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad, st, c_real, act); }
 static int a_conv_dgrad(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev, void *dyprev, int sp,
-                        float *dx_f32, hipStream_t st, int c_real)
-{ return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32, st, c_real); }
+                        float *dx_f32, hipStream_t st, int c_real, int act)
+{ return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32, st, c_real, act); }
 static int a_to_nhwc(const float *src, int C, int Cp, int H, int W, void *dst, hipStream_t st)
 { return orn_launch_nchw_to_nhwc_pad_bf16(src, C, Cp, H, W, (h16 *)dst, st); }
 static int a_to_nchw_f32(const float *src, int C, int Cp, int H, int W, int nslab, float scale, float *dst, hipStream_t st, const OrnScaleState *sc)
 { return orn_launch_nhwc_to_nchw_f32(src, C, Cp, H, W, nslab, scale, dst, st, sc); }
-static int a_head_fwd(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st)
-{ return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, HW, sigmoid, out, st); }
-static int a_decode_out(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st)
-{ return orn_launch_decode_out_h16((const h16 *)z, w, b, C, HW, sigmoid, o, st); }
+static int a_head_fwd(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, int act)
+{ return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, HW, sigmoid, out, st, act); }
+static int a_decode_out(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st, int act)
+{ return orn_launch_decode_out_h16((const h16 *)z, w, b, C, HW, sigmoid, o, st, act); }
 static int a_head_bwd(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp,
-                      float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc, const OrnLossFinalJob *fin)
-{ return orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs_up, (h16 *)dypad, dw, db, ws, st, sc, fin); }
-static int a_side_head_fwd(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc)
-{ return orn_launch_side_head_fwd_h16((const h16 *)z, w, b, C, HW, sigmoid, out, st, sc); }
+                      float gs_up, void *dypad, float *dw, float *db, float *ws, hipStream_t st, const OrnScaleState *sc, const OrnLossFinalJob *fin,
+                      int act)
+{ return orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs_up, (h16 *)dypad, dw, db, ws, st, sc, fin, act); }
+static int a_side_head_fwd(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc,
+                           int act)
+{ return orn_launch_side_head_fwd_h16((const h16 *)z, w, b, C, HW, sigmoid, out, st, sc, act); }
 static int a_side_head_bwd(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp, float lw,
-                           float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc)
-{ return orn_launch_side_head_bwd_h16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, (h16 *)dypad, dw, db, ws, st, sc); }
+                           float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc, int act)
+{ return orn_launch_side_head_bwd_h16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, (h16 *)dypad, dw, db, ws, st, sc, act); }
 
 const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
                         a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out,
@@ -406,6 +418,7 @@ __global__ void k_nhwc_bf16_to_nchw_f32(const h16 *__restrict__ src, int C, int 
 }
 
 // fp32 NCHW z, da [Cn][Hs][Ws] -> z bf16 NHWC and dypad = unshuffle(da * SiLU'(z)) (o' order, padded)
+template <int ACT>
 __global__ void k_make_dy_bf16(const float *__restrict__ z, const float *__restrict__ da, int Cn, int H, int W, int s,
                                h16 *__restrict__ zb, h16 *__restrict__ dypad)
 {
@@ -421,7 +434,7 @@ __global__ void k_make_dy_bf16(const float *__restrict__ z, const float *__restr
     zb[pix * Cn + c] = zq;
     const int ph = oh / s, pw = ow / s, sub = (oh - ph * s) * s + (ow - pw * s);
     dypad[((size_t)(ph + 1) * (W + 2) + (pw + 1)) * ((size_t)Cn * s * s) + (size_t)sub * Cn + c] =
-        (h16)(da[src] * orn_silu_grad((float)zq));
+        (h16)(da[src] * OrnAct<ACT>::df((float)zq));
 }
 
 static inline size_t alh(size_t halfs) { return orn_align(halfs * 2) / 2; }
@@ -461,9 +474,10 @@ extern "C" size_t orn_conv3x3_ps_silu_bf16_ws_bytes(int C, int O, int H, int W, 
 
 // Same contract as orn_conv3x3_ps_silu_fwd (B = 1) but computed on the bf16 MFMA path.
 // `ws` must be zero-filled by the caller before the first use (the padded borders are never written).
-extern "C" int HOOK(orn_conv3x3_ps_silu_fwd_bf16, orn_conv3x3_ps_silu_fwd_f16)(const float *x, const float *wf, const float *bf, int C, int O, int H, int W,
-                                            int s, float *z, float *a, void *ws, size_t ws_bytes, void *stream)
+extern "C" int HOOK(orn_conv3x3_ps_silu_fwd_bf16_act, orn_conv3x3_ps_silu_fwd_f16_act)(const float *x, const float *wf, const float *bf, int C, int O, int H, int W,
+                                            int s, float *z, float *a, void *ws, size_t ws_bytes, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "conv3x3_ps_silu_fwd_bf16: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && bf && (z || a) && ws, "conv3x3_ps_silu_fwd_bf16: null pointer");   // a == NULL: the last block's form (z only)
     ORN_REQUIRE(C % CB_CK == 0 && O % 32 == 0 && O % (s * s) == 0, "conv3x3_ps_silu_fwd_bf16: unsupported C=%d O=%d s=%d", C, O, s);
     if (ws_bytes < orn_conv3x3_ps_silu_bf16_ws_bytes(C, O, H, W, s)) { orn_set_error("conv3x3_ps_silu_fwd_bf16: workspace too small"); return ORN_E_WS; }
@@ -472,18 +486,24 @@ extern "C" int HOOK(orn_conv3x3_ps_silu_fwd_bf16, orn_conv3x3_ps_silu_fwd_f16)(c
     const int Cn = O / (s * s), Hs = H * s, Ws = W * s;
     ORN_TRY(orn_launch_nchw_to_nhwc_pad_bf16(x, C, C, H, W, b.xpad, st));
     ORN_TRY(orn_launch_prep_weights_bf16(wf, bf, O, C, s, b.wb, b.wd, b.biasp, st));
-    ORN_TRY(orn_launch_conv_bf16_fwd(b.xpad, b.wb, b.biasp, H, W, C, O, s, b.zb, a ? b.apad : nullptr, st, C));
+    ORN_TRY(orn_launch_conv_bf16_fwd(b.xpad, b.wb, b.biasp, H, W, C, O, s, b.zb, a ? b.apad : nullptr, st, C, act));
     const long n = (long)Cn * Hs * Ws;
     if (z) hipLaunchKernelGGL(k_nhwc_bf16_to_nchw_f32, dim3(orn_cdiv(n, 256)), dim3(256), 0, st, b.zb, Cn, Hs, Ws, 0, z);
     if (a) hipLaunchKernelGGL(k_nhwc_bf16_to_nchw_f32, dim3(orn_cdiv(n, 256)), dim3(256), 0, st, b.apad, Cn, Hs, Ws, 1, a);
     ORN_LAUNCH_CHECK("nhwc_bf16_to_nchw_f32");
     return 0;
 }
-
-extern "C" int HOOK(orn_conv3x3_ps_silu_bwd_bf16, orn_conv3x3_ps_silu_bwd_f16)(const float *x, const float *wf, const float *z, const float *da, int C, int O,
-                                            int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
-                                            size_t ws_bytes, void *stream)
+extern "C" int HOOK(orn_conv3x3_ps_silu_fwd_bf16, orn_conv3x3_ps_silu_fwd_f16)(const float *x, const float *wf, const float *bf, int C, int O, int H, int W,
+                                            int s, float *z, float *a, void *ws, size_t ws_bytes, void *stream)
 {
+    return HOOK(orn_conv3x3_ps_silu_fwd_bf16_act, orn_conv3x3_ps_silu_fwd_f16_act)(x, wf, bf, C, O, H, W, s, z, a, ws, ws_bytes, stream, ORN_ACT_SWISH);
+}
+
+extern "C" int HOOK(orn_conv3x3_ps_silu_bwd_bf16_act, orn_conv3x3_ps_silu_bwd_f16_act)(const float *x, const float *wf, const float *z, const float *da, int C, int O,
+                                            int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
+                                            size_t ws_bytes, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "conv3x3_ps_silu_bwd_bf16: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf && z && da && dwf && dbf && ws, "conv3x3_ps_silu_bwd_bf16: null pointer");
     ORN_REQUIRE(C == 96 && O % 96 == 0 && O % (s * s) == 0, "conv3x3_ps_silu_bwd_bf16: unsupported C=%d O=%d", C, O);
     if (ws_bytes < orn_conv3x3_ps_silu_bf16_ws_bytes(C, O, H, W, s)) { orn_set_error("conv3x3_ps_silu_bwd_bf16: workspace too small"); return ORN_E_WS; }
@@ -493,14 +513,21 @@ extern "C" int HOOK(orn_conv3x3_ps_silu_bwd_bf16, orn_conv3x3_ps_silu_bwd_f16)(c
     ORN_TRY(orn_launch_nchw_to_nhwc_pad_bf16(x, C, C, H, W, b.xpad, st));
     ORN_TRY(orn_launch_prep_weights_bf16(wf, dbf /*scratch: overwritten below*/, O, C, s, b.wb, b.wd, b.biasp, st));
     const long n = (long)Cn * H * s * W * s;
-    hipLaunchKernelGGL(k_make_dy_bf16, dim3(orn_cdiv(n, 256)), dim3(256), 0, st, z, da, Cn, H, W, s, b.zb, b.dypad);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_make_dy_bf16<A>, dim3(orn_cdiv(n, 256)), dim3(256), 0, st, z, da, Cn, H, W, s, b.zb, b.dypad));
     ORN_LAUNCH_CHECK("make_dy_bf16");
     ORN_TRY(orn_launch_wgrad_bf16(b.xpad, b.dypad, H, W, C, O, s, 1.0f, b.slabs, dwf, dbf, st));
     if (dx) {
-        ORN_TRY(orn_launch_conv_bf16_dgrad(b.dypad, b.wd, H, W, O, C, nullptr, nullptr, 1, b.dxn, st, C));
+        ORN_TRY(orn_launch_conv_bf16_dgrad(b.dypad, b.wd, H, W, O, C, nullptr, nullptr, 1, b.dxn, st, C, act));   // (fp32 slabs: no activation in it)
         ORN_TRY(orn_launch_nhwc_to_nchw_f32(b.dxn, C, C, H, W, orn_dgrad_f32_slabs(H, W, O), 1.0f, dx, st));
     }
     return 0;
+}
+extern "C" int HOOK(orn_conv3x3_ps_silu_bwd_bf16, orn_conv3x3_ps_silu_bwd_f16)(const float *x, const float *wf, const float *z, const float *da, int C, int O,
+                                            int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
+                                            size_t ws_bytes, void *stream)
+{
+    return HOOK(orn_conv3x3_ps_silu_bwd_bf16_act, orn_conv3x3_ps_silu_bwd_f16_act)(x, wf, z, da, C, O, H, W, s, dx, dwf, dbf, ws, ws_bytes, stream,
+                                                                                   ORN_ACT_SWISH);
 }
 
 // Raw channels-last entry points (the engine's own layouts; used by bench.py's roofline leg).
@@ -509,7 +536,7 @@ extern "C" int HOOK(orn_conv_nhwc_bf16_fwd, orn_conv_nhwc_f16_fwd)(const void *x
 {
     ORN_REQUIRE(xpad && wb && z, "conv_nhwc_bf16_fwd: null pointer");
     return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, C, O, s, (h16 *)z, (h16 *)apad,
-                                    (hipStream_t)stream, C);
+                                    (hipStream_t)stream, C, ORN_ACT_SWISH);      // the raw entry is the swish form (include/orn.h)
 }
 
 extern "C" int HOOK(orn_wgrad_nhwc_bf16, orn_wgrad_nhwc_f16)(const void *xpad, const void *dypad, int H, int W, int C, int O, int s, float *slabs,
@@ -524,23 +551,38 @@ extern "C" int HOOK(orn_dgrad_nhwc_bf16, orn_dgrad_nhwc_f16)(const void *dypad, 
                                    void *dyprev, int sp, void *stream)
 {
     return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp,
-                                      nullptr, (hipStream_t)stream, C);
+                                      nullptr, (hipStream_t)stream, C, ORN_ACT_SWISH);      // the raw entry is the swish form (include/orn.h)
 }
 
 // Test entry points (include/orn_debug.h): the two conv launchers with the engine's full argument lists, so that a test reaches
 // every kernel form they select (the narrow c_real forms, the split dgrad + finish, the fp32 hand-off) with the engine's buffers.
+extern "C" int HOOK(orn_debug_conv_fwd_bf16_act, orn_debug_conv_fwd_f16_act)(const void *xpad, const void *wb, const float *bias_p, int H, int W,
+                                                                           int Cin, int O, int s, void *z, void *apad, int c_real, void *stream,
+                                                                           int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_conv_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad,
+                                    (hipStream_t)stream, c_real, act);
+}
 extern "C" int HOOK(orn_debug_conv_fwd_bf16, orn_debug_conv_fwd_f16)(const void *xpad, const void *wb, const float *bias_p, int H, int W,
                                                                    int Cin, int O, int s, void *z, void *apad, int c_real, void *stream)
 {
-    return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad,
-                                    (hipStream_t)stream, c_real);
+    return HOOK(orn_debug_conv_fwd_bf16_act, orn_debug_conv_fwd_f16_act)(xpad, wb, bias_p, H, W, Cin, O, s, z, apad, c_real, stream, ORN_ACT_SWISH);
+}
+extern "C" int HOOK(orn_debug_conv_dgrad_bf16_act, orn_debug_conv_dgrad_f16_act)(const void *dypad, const void *wd, int H, int W, int O, int C,
+                                                                               const void *zprev, void *dyprev, int sp, float *dx_f32, int c_real,
+                                                                               void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_conv_dgrad: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32,
+                                      (hipStream_t)stream, c_real, act);
 }
 extern "C" int HOOK(orn_debug_conv_dgrad_bf16, orn_debug_conv_dgrad_f16)(const void *dypad, const void *wd, int H, int W, int O, int C,
                                                                        const void *zprev, void *dyprev, int sp, float *dx_f32, int c_real,
                                                                        void *stream)
 {
-    return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32,
-                                      (hipStream_t)stream, c_real);
+    return HOOK(orn_debug_conv_dgrad_bf16_act, orn_debug_conv_dgrad_f16_act)(dypad, wd, H, W, O, C, zprev, dyprev, sp, dx_f32, c_real, stream,
+                                                                             ORN_ACT_SWISH);
 }
 
 // The last stage's head (include/orn_debug.h): the launchers above and the two forms of the dW / db finish, as the per-op path and the
@@ -561,19 +603,26 @@ extern "C" size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int l
 }
 #endif
 
+extern "C" int HOOK(orn_debug_head_fwd_bf16_act, orn_debug_head_fwd_f16_act)(const void *z, const float *w, const float *b, int C, int H, int W,
+                                                                             int sigmoid, float *out, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "head_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(z && w && b && out, "head_fwd: null pointer");
+    ORN_REQUIRE(C >= 32 && H >= 1 && W >= 1, "head_fwd: bad sizes C=%d %dx%d", C, H, W);
+    return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, act);
+}
 extern "C" int HOOK(orn_debug_head_fwd_bf16, orn_debug_head_fwd_f16)(const void *z, const float *w, const float *b, int C, int H, int W,
                                                                      int sigmoid, float *out, void *stream)
 {
-    ORN_REQUIRE(z && w && b && out, "head_fwd: null pointer");
-    ORN_REQUIRE(C >= 32 && H >= 1 && W >= 1, "head_fwd: bad sizes C=%d %dx%d", C, H, W);
-    return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream);
+    return HOOK(orn_debug_head_fwd_bf16_act, orn_debug_head_fwd_f16_act)(z, w, b, C, H, W, sigmoid, out, stream, ORN_ACT_SWISH);
 }
 
-extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void *z, const float *w, const float *out, float *dout, int C,
-                                                                     int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
-                                                                     float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
-                                                                     int loss_type, float *stats, void *stream)
+extern "C" int HOOK(orn_debug_head_bwd_bf16_act, orn_debug_head_bwd_f16_act)(const void *z, const float *w, const float *out, float *dout, int C,
+                                                                             int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
+                                                                             float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
+                                                                             int loss_type, float *stats, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "head_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(z && w && out && dout && dypad && dw && db && ws && (!target || stats), "head_bwd: null pointer");
     const size_t head_bytes = orn_debug_head16_bwd_ws_bytes(C);
     ORN_REQUIRE(head_bytes, "head_bwd: unsupported C=%d", C);
@@ -600,10 +649,10 @@ extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void 
                              nullptr, nullptr, sc, nullptr, &fj);
     if (rc == 0)
         rc = orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs, (h16 *)dypad, flag ? nullptr : dw,
-                                      flag ? nullptr : db, (float *)ws, st, sc, target ? &fj : nullptr);
+                                      flag ? nullptr : db, (float *)ws, st, sc, target ? &fj : nullptr, act);
     if (rc == 0 && flag) {
         const OrnHeadFinish hf = {(const float *)ws, orn_head_bwd_bf16_blocks(H, W), C, 1.0f / gs, dw, db, sc};
-        rc = orn_launch_wgrad_bf16_batch(0, nullptr, st, &hf, nullptr, 0);
+        rc = orn_launch_wgrad_bf16_batch(0, nullptr, st, &hf, nullptr, 0, act);     // (no stem job on it: nothing evaluates the activation)
     }
     if (flag) {
         hipError_t e = hipStreamSynchronize(st);
@@ -613,6 +662,14 @@ extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void 
         (void)hipFree(sc);
     }
     return rc;
+}
+extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void *z, const float *w, const float *out, float *dout, int C,
+                                                                     int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
+                                                                     float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
+                                                                     int loss_type, float *stats, void *stream)
+{
+    return HOOK(orn_debug_head_bwd_bf16_act, orn_debug_head_bwd_f16_act)(z, w, out, dout, C, H, W, sigmoid, sp, gs, dypad, dw, db, ws, ws_bytes, flag,
+                                                                         target, loss_type, stats, stream, ORN_ACT_SWISH);
 }
 
 }  // namespace HNS

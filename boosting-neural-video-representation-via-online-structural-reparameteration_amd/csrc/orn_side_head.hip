@@ -22,7 +22,7 @@ namespace HNS {
 
 // 4 lanes per pixel; lane `sub` takes the 8-channel groups sub, sub + 4, ... (the last group may be short).  With C % 32 == 0 this is
 // the summation order of k_head_fwd_nhwc_bf16.
-template <bool VEC>
+template <bool VEC, int ACT>
 __global__ void __launch_bounds__(256)
 k_side_head_fwd_h16(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ bias, int C, size_t HW, int sigmoid,
                     float *__restrict__ out, OrnScaleState *sc)
@@ -39,11 +39,11 @@ k_side_head_fwd_h16(const h16 *__restrict__ z, const float *__restrict__ w, cons
         const h16 *zp = z + pix * C;
         for (int c0 = sub * 8; c0 < C; c0 += 32) {
             if (VEC) {
-                head_accum8(*reinterpret_cast<const h16x8 *>(zp + c0), c0, C, sw, a0, a1, a2);
+                head_accum8<ACT>(*reinterpret_cast<const h16x8 *>(zp + c0), c0, C, sw, a0, a1, a2);
             } else {
                 const int ne = C - c0 < 8 ? C - c0 : 8;
                 for (int e = 0; e < ne; ++e) {
-                    const float a = orn_silu((float)zp[c0 + e]);
+                    const float a = OrnAct<ACT>::f((float)zp[c0 + e]);
                     a0 = fmaf(sw[c0 + e], a, a0);
                     a1 = fmaf(sw[C + c0 + e], a, a1);
                     a2 = fmaf(sw[2 * C + c0 + e], a, a2);
@@ -62,7 +62,7 @@ k_side_head_fwd_h16(const h16 *__restrict__ z, const float *__restrict__ w, cons
 // Accumulating backward.  gs: the gradient scale dypad carries.  Work-group (x, y): pixels [x * 64 SH_PPT, + 64 SH_PPT),
 // channels [y * SH_CHUNK, + SH_CHUNK); NQ = 8-channel groups per lane of that chunk.  partial [gridDim.x][3 C + 3]: dW[k][c] at
 // k C + c, db[k] at 3 C + k (written by the work-groups of chunk 0).
-template <int NQ, bool VEC>
+template <int NQ, bool VEC, int ACT>
 __global__ void __launch_bounds__(256)
 k_side_head_bwd_h16(const h16 *__restrict__ z, const float *__restrict__ w, const float *__restrict__ out, const float *__restrict__ dout,
                     int C, int H, int W, int sigmoid, int sp, float lw, float gs, h16 *__restrict__ dypad, float *__restrict__ partial,
@@ -123,11 +123,18 @@ k_side_head_bwd_h16(const h16 *__restrict__ z, const float *__restrict__ w, cons
             for (int e = 0; e < 8; ++e) {
                 if (!VEC && e >= ne) continue;
                 const float zz = (float)v[e];
-                const float sg = orn_sigmoid(zz);
-                const float a = zz * sg;
-                const float da = fmaf(sw[2 * SH_CHUNK + c0 + e], du[2], fmaf(sw[SH_CHUNK + c0 + e], du[1], sw[c0 + e] * du[0]));
+                float a;
                 // the stored 16-bit value + this head's term, added in fp32 and rounded once
-                d8[e] = (h16)((float)d8[e] + da * (sg * (1.0f + zz * (1.0f - sg))));
+                if constexpr (ACT == ORN_ACT_SWISH) {
+                    const float sg = orn_sigmoid(zz);
+                    a = zz * sg;
+                    const float da = fmaf(sw[2 * SH_CHUNK + c0 + e], du[2], fmaf(sw[SH_CHUNK + c0 + e], du[1], sw[c0 + e] * du[0]));
+                    d8[e] = (h16)((float)d8[e] + da * (sg * (1.0f + zz * (1.0f - sg))));
+                } else {
+                    a = OrnAct<ACT>::f(zz);
+                    const float da = fmaf(sw[2 * SH_CHUNK + c0 + e], du[2], fmaf(sw[SH_CHUNK + c0 + e], du[1], sw[c0 + e] * du[0]));
+                    d8[e] = (h16)((float)d8[e] + da * OrnAct<ACT>::df(zz));
+                }
                 dwacc[q][e][0] = fmaf(du[0], a, dwacc[q][e][0]);
                 dwacc[q][e][1] = fmaf(du[1], a, dwacc[q][e][1]);
                 dwacc[q][e][2] = fmaf(du[2], a, dwacc[q][e][2]);
@@ -181,15 +188,16 @@ static bool side_head_vec(int C, const void *z, const void *dypad)
 }
 
 int orn_launch_side_head_fwd_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
-                                 OrnScaleState *sc)
+                                 OrnScaleState *sc, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "side_head_fwd: unknown activation %d", act);
     ORN_REQUIRE(C >= 1 && C <= SH_MAXC, "side_head_fwd: C=%d outside [1, %d]", C, SH_MAXC);
     ORN_REQUIRE(HW >= 1 && HW <= ((size_t)1 << 30), "side_head_fwd: %zu pixels outside [1, 2^30]", HW);
     const dim3 grid(orn_cdiv((long)HW, 64));
     if (side_head_vec(C, z, nullptr))
-        hipLaunchKernelGGL(k_side_head_fwd_h16<true>, grid, dim3(256), 0, st, z, w, b, C, HW, sigmoid, out, sc);
+        ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_side_head_fwd_h16<true, A>), grid, dim3(256), 0, st, z, w, b, C, HW, sigmoid, out, sc));
     else
-        hipLaunchKernelGGL(k_side_head_fwd_h16<false>, grid, dim3(256), 0, st, z, w, b, C, HW, sigmoid, out, sc);
+        ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_side_head_fwd_h16<false, A>), grid, dim3(256), 0, st, z, w, b, C, HW, sigmoid, out, sc));
     ORN_LAUNCH_CHECK("side_head_fwd");
     return 0;
 }
@@ -370,8 +378,10 @@ namespace HNS {
 // gs: the gradient scale dypad carries (1 for bf16, the loss scale for fp16; sc, engine: the live scale of the device state instead, and
 // non-finite dw / db raise its flag); dw / db are finished un-scaled (lw stays: it is part of the objective)
 int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
-                                 int sp, float lw, float gs, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc)
+                                 int sp, float lw, float gs, h16 *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc,
+                                 int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "side_head_bwd: unknown activation %d", act);
     ORN_REQUIRE(C >= 1 && C <= SH_MAXC, "side_head_bwd: C=%d outside [1, %d]", C, SH_MAXC);
     ORN_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W <= ((size_t)1 << 30), "side_head_bwd: bad image size %dx%d", H, W);
     ORN_REQUIRE(sp >= 1 && H % sp == 0 && W % sp == 0, "side_head_bwd: %dx%d not divisible by the stride %d", H, W, sp);
@@ -383,8 +393,8 @@ int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out,
     const bool vec = side_head_vec(C, z, dypad);
 #define SH_LAUNCH(NQ_)                                                                                                                       \
     do {                                                                                                                                     \
-        if (vec) hipLaunchKernelGGL((k_side_head_bwd_h16<NQ_, true>), grid, dim3(256), 0, st, z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, dypad, ws, sc);  \
-        else hipLaunchKernelGGL((k_side_head_bwd_h16<NQ_, false>), grid, dim3(256), 0, st, z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, dypad, ws, sc);     \
+        if (vec) ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_side_head_bwd_h16<NQ_, true, A>), grid, dim3(256), 0, st, z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, dypad, ws, sc));  \
+        else ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL((k_side_head_bwd_h16<NQ_, false, A>), grid, dim3(256), 0, st, z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, dypad, ws, sc));     \
     } while (0)
     switch (nq) {
     case 1: SH_LAUNCH(1); break;
@@ -407,22 +417,37 @@ int orn_launch_side_head_bwd_h16(const h16 *z, const float *w, const float *out,
 #define HOOK(bf16_, f16_) bf16_
 #endif
 
+extern "C" int HOOK(orn_debug_side_head_fwd_bf16_act, orn_debug_side_head_fwd_f16_act)(const void *z, const float *w, const float *b, int C, int H,
+                                                                                       int W, int sigmoid, float *out, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "side_head_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(z && w && b && out && H >= 1 && W >= 1, "side_head_fwd: bad arguments");
+    return HNS::orn_launch_side_head_fwd_h16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, nullptr, act);
+}
 extern "C" int HOOK(orn_debug_side_head_fwd_bf16, orn_debug_side_head_fwd_f16)(const void *z, const float *w, const float *b, int C, int H, int W,
                                                                                int sigmoid, float *out, void *stream)
 {
-    ORN_REQUIRE(z && w && b && out && H >= 1 && W >= 1, "side_head_fwd: bad arguments");
-    return HNS::orn_launch_side_head_fwd_h16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, nullptr);
+    return HOOK(orn_debug_side_head_fwd_bf16_act, orn_debug_side_head_fwd_f16_act)(z, w, b, C, H, W, sigmoid, out, stream, ORN_ACT_SWISH);
 }
 
-extern "C" int HOOK(orn_debug_side_head_bwd_bf16, orn_debug_side_head_bwd_f16)(const void *z, const float *w, const float *out, const float *dout,
-                                                                               int C, int H, int W, int sigmoid, int sp, float lw, float gs,
-                                                                               void *dypad, float *dw, float *db, void *ws, size_t ws_bytes,
-                                                                               void *stream)
+extern "C" int HOOK(orn_debug_side_head_bwd_bf16_act, orn_debug_side_head_bwd_f16_act)(const void *z, const float *w, const float *out,
+                                                                                       const float *dout, int C, int H, int W, int sigmoid, int sp,
+                                                                                       float lw, float gs, void *dypad, float *dw, float *db, void *ws,
+                                                                                       size_t ws_bytes, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "side_head_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(z && w && out && dout && dypad && dw && db && ws, "side_head_bwd: null pointer");
     const size_t need = orn_debug_side_head_bwd_ws_bytes(C, H, W);
     ORN_REQUIRE(need, "side_head_bwd: bad sizes C=%d %dx%d", C, H, W);
     if (ws_bytes < need) { orn_set_error("side_head_bwd: workspace %zu < %zu", ws_bytes, need); return ORN_E_WS; }
     return HNS::orn_launch_side_head_bwd_h16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, (h16 *)dypad, dw, db, (float *)ws,
-                                             (hipStream_t)stream, nullptr);
+                                             (hipStream_t)stream, nullptr, act);
+}
+extern "C" int HOOK(orn_debug_side_head_bwd_bf16, orn_debug_side_head_bwd_f16)(const void *z, const float *w, const float *out, const float *dout,
+                                                                               int C, int H, int W, int sigmoid, int sp, float lw, float gs,
+                                                                               void *dypad, float *dw, float *db, void *ws, size_t ws_bytes,
+                                                                               void *stream)
+{
+    return HOOK(orn_debug_side_head_bwd_bf16_act, orn_debug_side_head_bwd_f16_act)(z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, dypad, dw, db, ws,
+                                                                                   ws_bytes, stream, ORN_ACT_SWISH);
 }

@@ -94,7 +94,7 @@ __device__ __forceinline__ void batch_store(const float (&v)[U], const bool (&ok
         return p.wf + (ok ? ((size_t)(o0 + n) * p.C + c) * 9 + tap : 0);                                        \
     }
 
-template <typename H16>
+template <typename H16, int ACT>
 __global__ void __launch_bounds__(1024) k_stage0_fwd(Stage0P p, MhPackAll pack)
 {
     ORN_PRIO_HIGH();
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(1024) k_stage0_fwd(Stage0P p, MhPackAll pack)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int px = px0 + r, h = s0_div(px, p.mW), w = px - h * W;
-        dst[((size_t)(h * s + si + 1) * (W * s + 2) + (w * s + sj + 1)) * p.Cp + n] = (H16)orn_silu_exact(v[r]);
+        dst[((size_t)(h * s + si + 1) * (W * s + 2) + (w * s + sj + 1)) * p.Cp + n] = (H16)OrnAct<ACT>::f_exact(v[r]);
     }
     S0_STAMP(4);
 }
@@ -177,6 +177,7 @@ __global__ void __launch_bounds__(1024) k_stage0_fwd(Stage0P p, MhPackAll pack)
 // o = n*s^2 + si*s + sj.  For a fixed pixel those 16 values are contiguous in the next block's channels-last dgrad slabs
 // and in z, so the gather costs 64 B per line instead of 4 (with 16 consecutive o per work-group it was 374 K cache-line
 // requests from 41 CUs: ~17 us).
+template <int ACT>
 __global__ void __launch_bounds__(1024) k_stage0_bwd(Stage0P p)
 {
     ORN_PRIO_HIGH();
@@ -229,7 +230,7 @@ __global__ void __launch_bounds__(1024) k_stage0_bwd(Stage0P p)
                 const int e = base + t + k * nt;
                 if (e < 16 * HW) {
                     const int px = e >> 4, r16 = e & 15, h = s0_div(px, p.mW), w = px - h * W;
-                    dys[r16 * XP + (h + 1) * XW + w + 1] = ok[k] ? gsum[k] * inv_gs * orn_silu_grad_exact(zz[k]) : 0.f;
+                    dys[r16 * XP + (h + 1) * XW + w + 1] = ok[k] ? gsum[k] * inv_gs * OrnAct<ACT>::df_exact(zz[k]) : 0.f;
                 }
             }
         }
@@ -358,8 +359,9 @@ int orn_stage0_slabs(int O, int s) { return s * s * orn_cdiv(O / (s * s), 16); }
 // precision: 1 bf16, 2 IEEE half (element type of xpad_next)
 int orn_launch_stage0_fwd(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
                           void *xpad_next, int Cp, int precision, hipStream_t st, int n_prep, const OrnPrepLayer *prep,
-                          const void *pack, int pack_t_blocks)
+                          const void *pack, int pack_t_blocks, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "stage0_fwd: unknown activation %d", act);
     Stage0P p;
     ORN_TRY(fill(p, x, wf, bf, C, O, H, W, s));
     ORN_REQUIRE(n_prep >= 0 && n_prep <= ORN_MAX_LAYERS, "stage0_fwd: bad rider count");
@@ -383,11 +385,11 @@ int orn_launch_stage0_fwd(const float *x, const float *wf, const float *bf, int 
     if (pack && pack_t_blocks > 0) pk = *(const MhPackAll *)pack; else pack_t_blocks = 0;
     const dim3 grid(p.fwd_blocks + p.prep_blocks + pack_t_blocks), block(orn_cdiv(H * W, 16) * 64);
     if (precision == 2) {
-        ORN_TRY(set_smem(k_stage0_fwd<_Float16>, smem));
-        hipLaunchKernelGGL(k_stage0_fwd<_Float16>, grid, block, smem, st, p, pk);
+        ORN_ACT_SWITCH(act, A, ORN_TRY(set_smem(k_stage0_fwd<_Float16, A>, smem));
+                       hipLaunchKernelGGL((k_stage0_fwd<_Float16, A>), grid, block, smem, st, p, pk));
     } else {
-        ORN_TRY(set_smem(k_stage0_fwd<__bf16>, smem));
-        hipLaunchKernelGGL(k_stage0_fwd<__bf16>, grid, block, smem, st, p, pk);
+        ORN_ACT_SWITCH(act, A, ORN_TRY(set_smem(k_stage0_fwd<__bf16, A>, smem));
+                       hipLaunchKernelGGL((k_stage0_fwd<__bf16, A>), grid, block, smem, st, p, pk));
     }
     ORN_LAUNCH_CHECK("stage0_fwd");
     return 0;
@@ -397,16 +399,18 @@ int orn_launch_stage0_fwd(const float *x, const float *wf, const float *bf, int 
 // slabs: orn_stage0_slabs(O, s) * C*H*W floats of scratch; dx [C][H][W] (null: leave the slabs to the caller), dwf, dbf
 // are overwritten.
 int orn_launch_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs, int C,
-                          int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, hipStream_t st, const OrnScaleState *sc)
+                          int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, hipStream_t st, const OrnScaleState *sc,
+                          int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "stage0_bwd: unknown activation %d", act);
     Stage0P p;
     ORN_TRY(fill(p, x, wf, nullptr, C, O, H, W, s));
     ORN_REQUIRE(z && dxn && nslab >= 1 && slabs && dwf && dbf, "stage0_bwd: null pointer");
     p.z = const_cast<float *>(z); p.dxn = dxn; p.nslab = nslab; p.Cp = Cp; p.inv_gs = inv_gs; p.sc = sc; p.dwf = dwf; p.dbf = dbf; p.dx_slabs = slabs;
     const size_t smem = smem_bytes(p.C16, H, W, true);
-    ORN_TRY(set_smem(k_stage0_bwd, smem));
     const int nwg = orn_stage0_slabs(O, s);
-    hipLaunchKernelGGL(k_stage0_bwd, dim3(nwg), dim3(orn_cdiv(H * W, 16) * 64), smem, st, p);
+    ORN_ACT_SWITCH(act, A, ORN_TRY(set_smem(k_stage0_bwd<A>, smem));
+                   hipLaunchKernelGGL(k_stage0_bwd<A>, dim3(nwg), dim3(orn_cdiv(H * W, 16) * 64), smem, st, p));
     ORN_LAUNCH_CHECK("stage0_bwd");
     if (!dx) return 0;                 // the consumer (orn_launch_stem_bwd with dh2_nslab) sums the slabs itself
     const size_t n = (size_t)C * H * W;
@@ -418,18 +422,30 @@ extern "C" int orn_debug_stage0_supported(int C, int O, int H, int W, int s) { r
 
 extern "C" int orn_debug_stage0_slabs(int O, int s) { return (O >= 1 && s >= 1 && O % (s * s) == 0) ? orn_stage0_slabs(O, s) : 0; }
 
+extern "C" int orn_debug_stage0_fwd_act(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
+                                        void *xpad_next, int Cp, int precision, void *stream, int act)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_stage0_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(x && wf && bf, "debug_stage0_fwd: null pointer");
+    return orn_launch_stage0_fwd(x, wf, bf, C, O, H, W, s, z, xpad_next, Cp, precision, (hipStream_t)stream, 0, nullptr, nullptr, 0, act);
+}
 extern "C" int orn_debug_stage0_fwd(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
                                     void *xpad_next, int Cp, int precision, void *stream)
 {
-    ORN_REQUIRE(x && wf && bf, "debug_stage0_fwd: null pointer");
-    return orn_launch_stage0_fwd(x, wf, bf, C, O, H, W, s, z, xpad_next, Cp, precision, (hipStream_t)stream, 0, nullptr, nullptr, 0);
+    return orn_debug_stage0_fwd_act(x, wf, bf, C, O, H, W, s, z, xpad_next, Cp, precision, stream, ORN_ACT_SWISH);
 }
 
-extern "C" int orn_debug_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
-                                    int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream)
+extern "C" int orn_debug_stage0_bwd_act(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
+                                        int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream, int act)
 {
+    ORN_REQUIRE(orn_act_known(act), "debug_stage0_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
     ORN_REQUIRE(x && wf, "debug_stage0_bwd: null pointer");
     ORN_REQUIRE(orn_stage0_supported(C, O, H, W, s), "stage0: unsupported C=%d O=%d H=%d W=%d s=%d", C, O, H, W, s);
     ORN_REQUIRE(O / (s * s) <= Cp && (uintptr_t)slabs % 16 == 0, "debug_stage0_bwd: Cp below O / s^2, or slabs not 16-byte aligned");
-    return orn_launch_stage0_bwd(x, wf, z, dxn, nslab, Cp, inv_gs, C, O, H, W, s, slabs, dx, dwf, dbf, (hipStream_t)stream, nullptr);
+    return orn_launch_stage0_bwd(x, wf, z, dxn, nslab, Cp, inv_gs, C, O, H, W, s, slabs, dx, dwf, dbf, (hipStream_t)stream, nullptr, act);
+}
+extern "C" int orn_debug_stage0_bwd(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
+                                    int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream)
+{
+    return orn_debug_stage0_bwd_act(x, wf, z, dxn, nslab, Cp, inv_gs, C, O, H, W, s, slabs, dx, dwf, dbf, stream, ORN_ACT_SWISH);
 }

@@ -61,12 +61,14 @@ int orn_launch_head_finish_bf16(const float *partial, int blocks, int C, float g
 // nothing but the deferred reduction consumes them.
 // The head's dW/db reduction (needed by Adam only) rides along as trailing work-groups: one graph node less.
 struct WgradBPAll { int n; int start[ORN_MAX_LAYERS + 1]; WgradBP p[ORN_MAX_LAYERS]; OrnHeadFinish hf; int hf_blocks; OrnStemL2Job l2; int side; };
+// ACT: the activation of the stem job it may carry (the wgrad and the head finish evaluate none)
+template <int ACT>
 __global__ void __launch_bounds__(256, 2) k_wgrad_nhwc_bf16_all(WgradBPAll a)
 {
     if (!a.side) ORN_PRIO_HIGH();         // (the side branch's launch keeps the default priority: orn_common.h)
     if ((int)blockIdx.x >= a.start[a.n] + a.hf_blocks) {        // stem backward, second linear layer: 16 output rows per work-group
         extern __shared__ __attribute__((aligned(16))) unsigned char smem_l2[];
-        orn_stem_l2_block(a.l2, (int)blockIdx.x - a.start[a.n] - a.hf_blocks, (int)threadIdx.x, reinterpret_cast<float *>(smem_l2));
+        orn_stem_l2_block<ACT>(a.l2, (int)blockIdx.x - a.start[a.n] - a.hf_blocks, (int)threadIdx.x, reinterpret_cast<float *>(smem_l2));
         return;
     }
     if ((int)blockIdx.x >= a.start[a.n]) {
@@ -131,13 +133,14 @@ struct WgradReduceAll {
     struct { const float *slabs, *bias_slabs; int S, O, Cn, s2, Cr; float gscale; float *dwf, *dbf; OrnScaleState *sc; } l[ORN_MAX_LAYERS];
     int n; OrnStemW0Job w0;        // blockIdx.y == n: the stem backward's last kernel, two output rows per work-group (needed by Adam only)
 };
+template <int ACT>
 __global__ void k_wgrad_bf16_reduce_all(WgradReduceAll a)
 {
     if ((int)blockIdx.y == a.n) {
         __shared__ float sh_w0[4];
         if (2 * (int)blockIdx.x >= a.w0.N) return;
         const int half = threadIdx.x >> 7;
-        orn_stem_w0_row(a.w0, (int)blockIdx.x * 2 + half, threadIdx.x & 127, sh_w0 + 2 * half);
+        orn_stem_w0_row<ACT>(a.w0, (int)blockIdx.x * 2 + half, threadIdx.x & 127, sh_w0 + 2 * half);
         return;
     }
     const auto &l = a.l[blockIdx.y];
@@ -181,7 +184,8 @@ static int wgrad_lds_setup()
     if (!attr_done) {
         const size_t smem = WB_LDS_BYTES;
         hipError_t e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16_all<ORN_ACT_SWISH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_nhwc_bf16_all<ORN_ACT_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) { orn_set_error("wgrad_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
         attr_done = true;
     }
@@ -208,9 +212,10 @@ static int wgrad_fill(WgradBP &p, const h16 *xpad, const h16 *dypad, int H, int 
 }
 
 // slabs only (no reduction), several layers in one launch
-int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side)
+int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side, int act)
 {
     if (n == 0 && !hf && !l2) return 0;
+    ORN_REQUIRE(orn_act_known(act), "wgrad_batch: unknown activation %d", act);
     ORN_REQUIRE(n <= ORN_MAX_LAYERS, "wgrad_batch: %d layers", n);
     WgradBPAll a;
     a.n = n;
@@ -228,7 +233,7 @@ int orn_launch_wgrad_bf16_batch(int n, const OrnWgradJob *J, hipStream_t st, con
     if (hf) { a.hf = *hf; a.hf_blocks = 3 * hf->C + 3; total += a.hf_blocks; }
     a.l2 = OrnStemL2Job{};
     if (l2) { a.l2 = *l2; total += orn_cdiv(l2->N, ORN_STEM_ROWS); }
-    hipLaunchKernelGGL(k_wgrad_nhwc_bf16_all, dim3(total), dim3(256), WB_LDS_BYTES, st, a);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_wgrad_nhwc_bf16_all<A>, dim3(total), dim3(256), WB_LDS_BYTES, st, a));
     ORN_LAUNCH_CHECK("wgrad_nhwc_bf16_all");
     return 0;
 }
@@ -250,9 +255,10 @@ int orn_launch_wgrad_bf16(const h16 *xpad, const h16 *dypad, int H, int W, int C
     return 0;
 }
 
-int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0)
+int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0, int act)
 {
     if (n == 0 && !w0) return 0;
+    ORN_REQUIRE(orn_act_known(act), "wgrad_reduce_all: unknown activation %d", act);
     ORN_REQUIRE(n <= ORN_MAX_LAYERS, "wgrad_reduce_all: %d layers", n);
     WgradReduceAll a;
     size_t mx = 0;
@@ -267,7 +273,7 @@ int orn_launch_wgrad_reduce_all(int n, const OrnWgradReduce *L, hipStream_t st, 
     a.n = n;
     a.w0 = OrnStemW0Job{};
     if (w0) { a.w0 = *w0; const size_t need = (size_t)orn_cdiv(w0->N, 2) * 256; if (need > mx) mx = need; }
-    hipLaunchKernelGGL(k_wgrad_bf16_reduce_all, dim3(orn_cdiv((long)mx, 256), n + (w0 ? 1 : 0)), dim3(256), 0, st, a);
+    ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_wgrad_bf16_reduce_all<A>, dim3(orn_cdiv((long)mx, 256), n + (w0 ? 1 : 0)), dim3(256), 0, st, a));
     ORN_LAUNCH_CHECK("wgrad_bf16_reduce_all");
     return 0;
 }

@@ -81,6 +81,7 @@ def build_desc(model, layout, total, loss_type='Fusion6', beta1=0.5, beta2=0.999
     d.embed_len, d.stem_dim = model.stem[0].in_features, model.stem[0].out_features
     d.fc_h, d.fc_w, d.fc_dim = model.fc_h, model.fc_w, model.fc_dim
     d.sigmoid = int(bool(model.sigmoid))
+    d.act = ops.act_id(getattr(model, 'act', 'swish'))      # --act: the stem's and every block's activation (ORN_ACT_*)
     d.loss_type = _lib.loss_id(loss_type)
     d.precision = precision
     d.beta1, d.beta2, d.eps = beta1, beta2, eps

@@ -62,7 +62,8 @@ class NeRVBlock(nn.Module):
         self.deploy = kargs['deploy']
         self.branch_type = kargs['branch_type']
         _only(kargs.get('norm', 'none'), ('none',), 'norm')
-        _only(kargs.get('act', 'swish'), ('swish',), 'act')
+        _only(kargs.get('act', 'swish'), ops.ACTS, 'act')
+        self.act = kargs.get('act', 'swish')
         self.out_channels = self.new_ngf * self.stride * self.stride
         C, O = self.ngf, self.out_channels
         if self.deploy:
@@ -156,7 +157,7 @@ class NeRVBlock(nn.Module):
             w, b = self.branch.weight, self.branch.bias
         else:       # ERB, ACB, RepVGG, ECB: the online merge
             w, b = self.get_equivalent_kernel_bias()
-        return ops.ConvPsSiluFn.apply(x, w, b, self.stride)
+        return ops.ConvPsSiluFn.apply(x, w, b, self.stride, getattr(self, 'act', 'swish'))
 
 
 class Generator(nn.Module):
@@ -166,15 +167,18 @@ class Generator(nn.Module):
         super().__init__()
         stem_dim, stem_num = [int(x) for x in kargs['stem_dim_num'].split('_')]
         self.fc_h, self.fc_w, self.fc_dim = [int(x) for x in kargs['fc_hw_dim'].split('_')]
-        _only(kargs.get('act', 'swish'), ('swish',), 'act')
+        _only(kargs.get('act', 'swish'), ops.ACTS, 'act')
+        self.act = kargs.get('act', 'swish')
         if stem_num != 1:
             raise NotImplementedError('stem_dim_num with more than one hidden layer is outside the hot path')
         if kargs.get('num_blocks', 1) != 1:
             raise NotImplementedError('num_blocks != 1 is outside the hot path')
         self.embed_length = kargs['embed_length']
         # nn.Sequential(Linear, act, Linear, act) -> keys stem.0.*, stem.2.* (model.py:183-188)
-        self.stem = nn.Sequential(nn.Linear(kargs['embed_length'], stem_dim), nn.SiLU(inplace=True),
-                                  nn.Linear(stem_dim, self.fc_h * self.fc_w * self.fc_dim), nn.SiLU(inplace=True))
+        # (the activation modules hold no parameters: the keys do not depend on --act)
+        act_mod = (lambda: nn.GELU()) if self.act == 'gelu' else (lambda: nn.SiLU(inplace=True))
+        self.stem = nn.Sequential(nn.Linear(kargs['embed_length'], stem_dim), act_mod(),
+                                  nn.Linear(stem_dim, self.fc_h * self.fc_w * self.fc_dim), act_mod())
         self.layers, self.head_layers = [nn.ModuleList() for _ in range(2)]
         ngf = self.fc_dim
         self.stride_list = list(kargs['stride_list'])
@@ -196,7 +200,7 @@ class Generator(nn.Module):
 
     def forward(self, input):
         s0, s2 = self.stem[0], self.stem[2]
-        output = ops.StemFn.apply(input, s0.weight, s0.bias, s2.weight, s2.bias)
+        output = ops.StemFn.apply(input, s0.weight, s0.bias, s2.weight, s2.bias, getattr(self, 'act', 'swish'))
         output = output.view(output.size(0), self.fc_dim, self.fc_h, self.fc_w)
         out_list = []
         for layer, head_layer in zip(self.layers, self.head_layers):

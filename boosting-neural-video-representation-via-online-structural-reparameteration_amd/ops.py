@@ -36,11 +36,25 @@ def pe_forward(pos: torch.Tensor, lbase: float, levels: int) -> torch.Tensor:
 
 
 # ---- A2 ------------------------------------------------------------------------------------
+# --act (model.py:24-45): what is built, by name -> ORN_ACT_* of include/orn.h
+ACTS = ('swish', 'gelu')
+
+
+def act_id(act) -> int:
+    """ORN_ACT_* of an --act name (or of an id already); NotImplementedError, naming what is built, for anything else."""
+    if isinstance(act, int) and 0 <= act < len(ACTS):
+        return act
+    if act not in ACTS:
+        raise NotImplementedError(f'act={act!r} is outside the MI355X hot path (built: {ACTS}); see SURVEY.md section 8 for the scope')
+    return ACTS.index(act)
+
+
 class StemFn(torch.autograd.Function):
-    """SiLU(W1 SiLU(W0 e + b0) + b1) (model.py:186-188)."""
+    """act(W1 act(W0 e + b0) + b1) (model.py:186-188); act: an --act name of ACTS (default swish)."""
 
     @staticmethod
-    def forward(ctx, embed, w0, b0, w1, b1):
+    def forward(ctx, embed, w0, b0, w1, b1, act='swish'):
+        ctx.act = act_id(act)
         embed, w0, b0, w1, b1 = map(_f32c, (embed, w0, b0, w1, b1))
         B, E = embed.shape
         Hd, Nout = w0.shape[0], w1.shape[0]
@@ -49,8 +63,8 @@ class StemFn(torch.autograd.Function):
         h1 = torch.empty(B, Hd, device=dev)
         pre2 = torch.empty(B, Nout, device=dev)
         h2 = torch.empty(B, Nout, device=dev)
-        check(lib().orn_stem_fwd(ptr(embed), ptr(w0), ptr(b0), ptr(w1), ptr(b1), B, E, Hd, Nout,
-                                 ptr(pre1), ptr(h1), ptr(pre2), ptr(h2), stream()), 'orn_stem_fwd')
+        check(lib().orn_stem_fwd_act(ptr(embed), ptr(w0), ptr(b0), ptr(w1), ptr(b1), B, E, Hd, Nout,
+                                     ptr(pre1), ptr(h1), ptr(pre2), ptr(h2), stream(), ctx.act), 'orn_stem_fwd_act')
         ctx.save_for_backward(embed, w1, pre1, h1, pre2)
         ctx.dims = (B, E, Hd, Nout)
         return h2
@@ -66,9 +80,9 @@ class StemFn(torch.autograd.Function):
         dw1 = torch.empty(Nout, Hd, device=dev)
         db1 = torch.empty(Nout, device=dev)
         ws = _ws(lib().orn_stem_bwd_ws_bytes(B, Hd, Nout), dev)
-        check(lib().orn_stem_bwd(ptr(embed), ptr(w1), ptr(pre1), ptr(h1), ptr(pre2), ptr(dh2), B, E, Hd, Nout,
-                                 ptr(dw0), ptr(db0), ptr(dw1), ptr(db1), ptr(ws), stream()), 'orn_stem_bwd')
-        return None, dw0, db0, dw1, db1
+        check(lib().orn_stem_bwd_act(ptr(embed), ptr(w1), ptr(pre1), ptr(h1), ptr(pre2), ptr(dh2), B, E, Hd, Nout,
+                                     ptr(dw0), ptr(db0), ptr(dw1), ptr(db1), ptr(ws), stream(), ctx.act), 'orn_stem_bwd_act')
+        return None, dw0, db0, dw1, db1, None
 
 
 # ---- A3 ------------------------------------------------------------------------------------
@@ -194,10 +208,11 @@ class BranchMergeFn(torch.autograd.Function):
 
 # ---- A4 ------------------------------------------------------------------------------------
 class ConvPsSiluFn(torch.autograd.Function):
-    """conv3x3(pad 1) + bias -> PixelShuffle(s) -> SiLU (model.py:539,567)."""
+    """conv3x3(pad 1) + bias -> PixelShuffle(s) -> act (model.py:539,567); act: an --act name of ACTS (default swish)."""
 
     @staticmethod
-    def forward(ctx, x, wf, bf, s):
+    def forward(ctx, x, wf, bf, s, act='swish'):
+        ctx.act = act_id(act)
         x, wf, bf = _f32c(x), _f32c(wf), _f32c(bf)
         B, C, H, W = x.shape
         O = wf.shape[0]
@@ -207,8 +222,8 @@ class ConvPsSiluFn(torch.autograd.Function):
         need_grad = any(ctx.needs_input_grad[:3])
         a = torch.empty(B, O // (s * s), H * s, W * s, device=dev)
         z = torch.empty_like(a) if need_grad else None
-        check(lib().orn_conv3x3_ps_silu_fwd(ptr(x), ptr(wf), ptr(bf), B, C, O, H, W, s, ptr(z), ptr(a), stream()),
-              'orn_conv3x3_ps_silu_fwd')
+        check(lib().orn_conv3x3_ps_silu_fwd_act(ptr(x), ptr(wf), ptr(bf), B, C, O, H, W, s, ptr(z), ptr(a), stream(), ctx.act),
+              'orn_conv3x3_ps_silu_fwd_act')
         if need_grad:
             ctx.save_for_backward(x, wf, z)
         ctx.dims = (B, C, O, H, W, s)
@@ -225,10 +240,10 @@ class ConvPsSiluFn(torch.autograd.Function):
         dbf = torch.empty(O, device=dev)
         nb = lib().orn_conv3x3_ps_silu_bwd_ws_bytes(B, C, O, H, W)
         ws = _ws(nb, dev)
-        check(lib().orn_conv3x3_ps_silu_bwd(ptr(x), ptr(wf), ptr(z), ptr(da), B, C, O, H, W, s, ptr(dx), ptr(dwf),
-                                            ptr(dbf), ptr(ws), c_size_t(ws.numel()), stream()),
-              'orn_conv3x3_ps_silu_bwd')
-        return dx, dwf, dbf, None
+        check(lib().orn_conv3x3_ps_silu_bwd_act(ptr(x), ptr(wf), ptr(z), ptr(da), B, C, O, H, W, s, ptr(dx), ptr(dwf),
+                                                ptr(dbf), ptr(ws), c_size_t(ws.numel()), stream(), ctx.act),
+              'orn_conv3x3_ps_silu_bwd_act')
+        return dx, dwf, dbf, None, None
 
 
 # ---- A5 ------------------------------------------------------------------------------------

@@ -42,11 +42,17 @@ extern "C" {
                                   * + ORN_BRANCH_ACB / _REPVGG / _ECB, orn_branch_ptrs, orn_branch_merge_fwd / _bwd_ws_bytes / _bwd, and, appended
                                   * to orn_engine_desc, branch_kind + branch[] (N7: the paper's comparison blocks through an online merge);
                                   * + orn_engine_set_stage_targets / _stage_target_stats / _stage_stats and, appended to orn_engine_desc, multi_res + lw +
-                                  * side_head_w[] / side_head_b[] (N8: a head and a loss at every stage) */
+                                  * side_head_w[] / side_head_b[] (N8: a head and a loss at every stage); + ORN_ACT_SWISH / ORN_ACT_GELU, the *_act entry points and, appended to
+                                  * orn_engine_desc, act (--act gelu) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
 #define ORN_MAX_LAYERS 8
+/* --act: the activation behind every block's PixelShuffle and inside the stem (model.py:24-45).  swish = z sigmoid(z); gelu = nn.GELU()
+ * without the tanh approximation, 0.5 z erfc(-z / sqrt 2).  Entry points named *_act take one of these as their last `int act`
+ * (ORN_E_ARG for any other value); the entry points without it are the swish form. */
+#define ORN_ACT_SWISH 0
+#define ORN_ACT_GELU 1
 
 #define ORN_OK 0
 #define ORN_E_ARG (-1)           /* bad pointer / size / unsupported shape */
@@ -74,6 +80,14 @@ ORN_API size_t orn_stem_bwd_ws_bytes(int B, int Hd, int Nout);
 ORN_API int orn_stem_bwd(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
                  const float *dh2, int B, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
                  float *db1, float *ws, void *stream);
+
+/* The same two with the activation of --act (ORN_ACT_*) in place of SiLU. */
+ORN_API int orn_stem_fwd_act(const float *embed, const float *w0, const float *b0, const float *w1, const float *b1,
+                 int B, int E, int Hd, int Nout, float *pre1, float *h1, float *pre2, float *h2,
+                 void *stream, int act);
+ORN_API int orn_stem_bwd_act(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                 const float *dh2, int B, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
+                 float *db1, float *ws, void *stream, int act);
 
 /* ---- A3  NeRVBlock.get_equivalent_kernel_bias (online ERB merge)     model.py:450-516 --------
  * T[O,C,3,3] (kept for the backward), wf[O,C,3,3], bf[O].  Bit-exact against oracle/merge_ref.c:
@@ -133,6 +147,13 @@ ORN_API int orn_conv3x3_ps_silu_bwd(const float *x, const float *wf, const float
                             int O, int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
                             size_t ws_bytes, void *stream);
 
+/* The same two with the activation of --act (ORN_ACT_*): a = act(z), dy = unshuffle(da * act'(z)).  Same workspace. */
+ORN_API int orn_conv3x3_ps_silu_fwd_act(const float *x, const float *wf, const float *bf, int B, int C, int O, int H,
+                            int W, int s, float *z, float *a, void *stream, int act);
+ORN_API int orn_conv3x3_ps_silu_bwd_act(const float *x, const float *wf, const float *z, const float *da, int B, int C,
+                            int O, int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
+                            size_t ws_bytes, void *stream, int act);
+
 /* ---- A4 on the bf16 MFMA path (fp32 accumulate): same contract as the two calls above for B = 1,
  * C <= 96 (zero-padded to 96 in the staging), O % 32 == 0, O % (s*s) == 0 and (O/(s*s)) % 8 == 0.  Inputs/outputs stay fp32 NCHW; the channels-last bf16
  * staging (DESIGN.md "data layout") lives in `ws`, which the caller must zero-fill once before the
@@ -178,6 +199,17 @@ ORN_API int orn_conv3x3_ps_silu_fwd_f16(const float *x, const float *wf, const f
                                 float *z, float *a, void *ws, size_t ws_bytes, void *stream);
 ORN_API int orn_conv3x3_ps_silu_bwd_f16(const float *x, const float *wf, const float *z, const float *da, int C, int O, int H,
                                 int W, int s, float *dx, float *dwf, float *dbf, void *ws, size_t ws_bytes, void *stream);
+
+/* The four fp32-layout block hooks of the 16-bit path with the activation of --act (ORN_ACT_*).  Same workspace. */
+ORN_API int orn_conv3x3_ps_silu_fwd_bf16_act(const float *x, const float *wf, const float *bf, int C, int O, int H, int W,
+                                 int s, float *z, float *a, void *ws, size_t ws_bytes, void *stream, int act);
+ORN_API int orn_conv3x3_ps_silu_bwd_bf16_act(const float *x, const float *wf, const float *z, const float *da, int C, int O,
+                                 int H, int W, int s, float *dx, float *dwf, float *dbf, void *ws,
+                                 size_t ws_bytes, void *stream, int act);
+ORN_API int orn_conv3x3_ps_silu_fwd_f16_act(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s,
+                                float *z, float *a, void *ws, size_t ws_bytes, void *stream, int act);
+ORN_API int orn_conv3x3_ps_silu_bwd_f16_act(const float *x, const float *wf, const float *z, const float *da, int C, int O, int H,
+                                int W, int s, float *dx, float *dwf, float *dbf, void *ws, size_t ws_bytes, void *stream, int act);
 
 /* ---- A5  head: 1x1 conv -> (tanh+1)/2 or sigmoid                      model.py:621-622 --------
  * a [B,C,H,W]; w [3,C,1,1]; b [3]; out [B,3,H,W]. */
@@ -323,6 +355,10 @@ typedef struct orn_engine_desc {
                                      * sum_{i < n-1} lw * loss(out_i, target_i) + loss(out_{n-1}, target_{n-1}); see orn_engine_set_stage_targets */
     float lw;                       /* weight of the stages below the last (--lw) */
     int64_t side_head_w[ORN_MAX_LAYERS], side_head_b[ORN_MAX_LAYERS];   /* heads of stages 0 .. n_layers-2: [3,C_i,1,1], [3]; head_w / head_b stay the last stage's */
+    /* appended (--act); all zero = the engine of before */
+    int32_t act;                    /* ORN_ACT_*: the activation of the stem and of every block, in every form of the engine (ORN_E_ARG for an
+                                     * unknown value).  The workspace does not depend on it */
+    int32_t reserved2_;
 } orn_engine_desc;
 
 /* One entry of the per-step schedule (device array, uploaded per epoch by the caller). */

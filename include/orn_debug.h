@@ -215,6 +215,58 @@ ORN_API int orn_debug_head_bwd_bf16(const void *z, const float *w, const float *
 ORN_API int orn_debug_head_bwd_f16(const void *z, const float *w, const float *out, float *dout, int C, int H, int W, int sigmoid,
                                    int sp, float gs, void *dypad, float *dw, float *db, void *ws, size_t ws_bytes, int *flag,
                                    const float *target, int loss_type, float *stats, void *stream);
+/* ---- the activation of --act (ORN_ACT_SWISH / ORN_ACT_GELU, include/orn.h) ----
+ * act_eval: f[i] = act(z[i]), df[i] = act'(z[i]) for n <= 2^30 device floats, through the device functions the kernels call: exact == 0
+ *          the pair of the 16-bit kernels (OrnAct<act>::f / df), exact != 0 the pair of the fp32 path (f_exact / df_exact);
+ *          tests/test_gpu_act_eval.py sweeps them against fp64.
+ * Every other *_act entry below is the entry of the same name without the suffix (above), same arguments and conventions, with the
+ * activation as one more trailing `int act`; the un-suffixed entries are these with ORN_ACT_SWISH.  An unknown act: ORN_E_ARG with a
+ * text, checked before anything else, nothing launched. */
+ORN_API int orn_debug_act_eval(int act, int exact, const float *z, size_t n, float *f, float *df, void *stream);
+ORN_API int orn_debug_conv_fwd_bf16_act(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
+                                        void *z, void *apad, int c_real, void *stream, int act);
+ORN_API int orn_debug_conv_fwd_f16_act(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s,
+                                       void *z, void *apad, int c_real, void *stream, int act);
+ORN_API int orn_debug_conv_dgrad_bf16_act(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev,
+                                          void *dyprev, int sp, float *dx_f32, int c_real, void *stream, int act);
+ORN_API int orn_debug_conv_dgrad_f16_act(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev,
+                                         void *dyprev, int sp, float *dx_f32, int c_real, void *stream, int act);
+ORN_API int orn_debug_head_fwd_bf16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                        void *stream, int act);
+ORN_API int orn_debug_head_fwd_f16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                       void *stream, int act);
+ORN_API int orn_debug_head_bwd_bf16_act(const void *z, const float *w, const float *out, float *dout, int C, int H, int W, int sigmoid,
+                                        int sp, float gs, void *dypad, float *dw, float *db, void *ws, size_t ws_bytes, int *flag,
+                                        const float *target, int loss_type, float *stats, void *stream, int act);
+ORN_API int orn_debug_head_bwd_f16_act(const void *z, const float *w, const float *out, float *dout, int C, int H, int W, int sigmoid,
+                                       int sp, float gs, void *dypad, float *dw, float *db, void *ws, size_t ws_bytes, int *flag,
+                                       const float *target, int loss_type, float *stats, void *stream, int act);
+ORN_API int orn_debug_side_head_fwd_bf16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                             void *stream, int act);
+ORN_API int orn_debug_side_head_fwd_f16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, float *out,
+                                            void *stream, int act);
+ORN_API int orn_debug_side_head_bwd_bf16_act(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W,
+                                             int sigmoid, int sp, float lw, float gs, void *dypad, float *dw, float *db, void *ws,
+                                             size_t ws_bytes, void *stream, int act);
+ORN_API int orn_debug_side_head_bwd_f16_act(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W,
+                                            int sigmoid, int sp, float lw, float gs, void *dypad, float *dw, float *db, void *ws,
+                                            size_t ws_bytes, void *stream, int act);
+ORN_API int orn_debug_stage0_fwd_act(const float *x, const float *wf, const float *bf, int C, int O, int H, int W, int s, float *z,
+                                     void *xpad_next, int Cp, int precision, void *stream, int act);
+ORN_API int orn_debug_stage0_bwd_act(const float *x, const float *wf, const float *z, const float *dxn, int nslab, int Cp, float inv_gs,
+                                     int C, int O, int H, int W, int s, float *slabs, float *dx, float *dwf, float *dbf, void *stream,
+                                     int act);
+ORN_API int orn_debug_stem_bwd_slabs_act(const float *embed, const float *w1, const float *pre1, const float *h1, const float *pre2,
+                                         const float *dh2_slabs, int nslab, int E, int Hd, int Nout, float *dw0, float *db0, float *dw1,
+                                         float *db1, float *ws, size_t ws_bytes, void *stream, int act);
+ORN_API int orn_debug_conv_fwd_f32_act(const float *x, const float *wf, const float *bf, int B, int C, int O, int H, int W, int s,
+                                       float *z, float *a, void *stream, int act);
+ORN_API int orn_debug_head_fwd_z_act(const float *z, const float *w, const float *b, int B, int C, int H, int W, int sigmoid, float *out,
+                                     void *stream, int act);
+ORN_API int orn_debug_conv_bwd_f32_head_act(const float *x, const float *wf, const float *z, const float *head_w, const float *head_out,
+                                            const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
+                                            float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
+                                            void *stream, int act);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);
