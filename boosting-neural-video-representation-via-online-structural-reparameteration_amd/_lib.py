@@ -183,6 +183,8 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_msssim_level_fwd': (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
                'orn_debug_msssim_level_bwd': (c_int, [c_int, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_float, c_float, P, P, P]),
                'orn_debug_loss_msssim_layout': (c_int, [c_int] * 5 + [POINTER(c_int64)]),
+               'orn_debug_loss_launch': (c_int, [P, P, P, c_size_t] + [c_int] * 5 + [c_float, P, P, P, P, c_size_t, P]),
+               'orn_debug_loss_layout': (c_int, [c_int] * 4 + [POINTER(c_int64)]),
                'orn_debug_side_head_bwd_ws_bytes': (c_size_t, [c_int] * 3),
                'orn_debug_side_head_fwd_bf16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),
                'orn_debug_side_head_fwd_f16': (c_int, [P, P, P] + [c_int] * 4 + [P, P]),

@@ -792,6 +792,35 @@ extern "C" int orn_debug_msssim_level_fwd(const float *x, const float *y, int pl
     return 0;
 }
 
+// orn_launch_loss itself with every argument the engine gives it: the frame table, the device frame index and the cached target maps
+extern "C" int orn_debug_loss_launch(const float *pred, const float *frames, const int *frame_idx, size_t frame_stride, int B, int Ch,
+                                     int H, int W, int loss_type, float loss_scale, const float *tstats, float *stats, float *dpred,
+                                     void *ws, size_t ws_bytes, void *stream)
+{
+    ORN_REQUIRE(pred && frames && stats && ws, "debug_loss_launch: null pointer");
+    ORN_REQUIRE(B > 0 && Ch > 0 && H > 0 && W > 0 && (long)B * Ch <= 65535, "debug_loss_launch: bad sizes");
+    const OrnLossSpec *sp = orn_loss_spec_of(loss_type);
+    ORN_REQUIRE(sp, "debug_loss_launch: unsupported loss_type %d", loss_type);
+    ORN_REQUIRE(sp->kind != ORN_LOSS_KIND_MSSSIM, "debug_loss_launch: loss_type %d is an MS-SSIM loss", loss_type);
+    ORN_REQUIRE(!tstats || sp->kind == ORN_LOSS_KIND_SSIM, "debug_loss_launch: only the SSIM kinds read target statistics");
+    const size_t need = orn_loss_ws_bytes_for(loss_type, B, Ch, H, W);
+    if (ws_bytes < need) {
+        orn_set_error("debug_loss_launch: workspace %zu < %zu", ws_bytes, need);
+        return ORN_E_WS;
+    }
+    return orn_launch_loss(pred, frames, frame_idx, frame_stride, B, Ch, H, W, loss_type, loss_scale, stats, dpred, (float *)ws,
+                           (hipStream_t)stream, nullptr, nullptr, nullptr, tstats);
+}
+
+extern "C" int orn_debug_loss_layout(int B, int Ch, int H, int W, int64_t *out)
+{
+    ORN_REQUIRE(out, "debug_loss_layout: null pointer");
+    ORN_REQUIRE(B > 0 && Ch > 0 && H > 0 && W > 0, "debug_loss_layout: bad sizes");
+    const LossGeom g = loss_geom(B, Ch, H, W);
+    out[0] = g.tw; out[1] = g.th; out[2] = (int64_t)g.off_pl; out[3] = (int64_t)g.total;
+    return 0;
+}
+
 extern "C" int orn_debug_loss_msssim_layout(int loss_type, int B, int Ch, int H, int W, int64_t *out)
 {
     const OrnLossSpec *sp = orn_loss_spec_of(loss_type);

@@ -2,7 +2,8 @@
  * counterpart.  The ablation flags make results WRONG (they exist to time parts of a kernel in isolation, tools/probes); the
  * conv entry points compute correct results (tests/test_gpu_conv16_forms.py checks every kernel form through them), and so does
  * the merge backward's (tests/test_gpu_merge16.py), the fused first block's and the slab-summing stem backward's
- * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py), the side heads'
+ * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py), the loss launcher's
+ * (tests/test_gpu_fusion6.py), the side heads'
  * (tests/test_gpu_side_head.py), the last stage's 16-bit head's (tests/test_gpu_head16.py) and the fp32 conv path's
  * (tests/test_gpu_conv32_forms.py). */
 #ifndef ORN_DEBUG_H_
@@ -112,6 +113,22 @@ ORN_API int orn_debug_msssim_level_bwd(int form, const float *x, const float *y,
                                        const int *frame_idx, size_t frame_stride, int planes, int H, int W, float g_l1, float g_l2,
                                        float *g, float *part_l1, void *stream);
 ORN_API int orn_debug_loss_msssim_layout(int loss_type, int B, int Ch, int H, int W, int64_t *out);
+/* The loss launcher of every step (orn_launch_loss: k_fusion6 / k_loss_grad + the finalize launch) with all the arguments the engine
+ * gives it, where orn_loss_fwd_bwd fixes frame_idx = NULL and tstats = NULL; tests/test_gpu_fusion6.py pins both kernels elementwise
+ * to fp64 through it.  The launcher itself picks the kernel form and decides the float4 load path (W % 4 == 0, 16-byte aligned pred
+ * and frames and, with a frame index, frame_stride % 4 == 0).
+ *   loss_launch: pred, dpred [B][Ch][H][W]; the target is frames + *frame_idx * frame_stride floats (frame_idx: device, NULL: frames
+ *          itself).  tstats (NULL: none): orn_loss_target_stats of the same table, SSIM kinds only, B == 1 (one frame's maps hold
+ *          Ch planes).  dpred NULL: no gradient, the same partials and stats.  stats[8], ws, ws_bytes as orn_loss_fwd_bwd.  Refused
+ *          with ORN_E_ARG and nothing launched: a null pointer, a size below 1, more than 65535 planes, an unknown or an MS-SSIM
+ *          loss_type, tstats with a loss that has no SSIM term; ORN_E_WS: a workspace below orn_loss_ws_bytes_for.
+ *   loss_layout: what the launch leaves in ws.  out[4] (host) = tiles_w, tiles_h (16x64 tiles of the image), the float offset of
+ *          part_l1, the workspace in floats: part_ssim [B*Ch][tiles] at offset 0 (SSIM kinds), part_l1 [B*Ch][tiles][2] = {sum |d|,
+ *          sum d^2}. */
+ORN_API int orn_debug_loss_launch(const float *pred, const float *frames, const int *frame_idx, size_t frame_stride, int B, int Ch,
+                                  int H, int W, int loss_type, float loss_scale, const float *tstats, float *stats, float *dpred,
+                                  void *ws, size_t ws_bytes, void *stream);
+ORN_API int orn_debug_loss_layout(int B, int Ch, int H, int W, int64_t *out);
 /* The side heads of a multi-resolution generator (model.py:597-625 without sin_res; orn_side_head.hip): the head of a stage below
  * the last one, whose backward ADDS to a gradient buffer the block above has already written.  tests/test_gpu_side_head.py pins
  * them elementwise to fp64.  w [3][C], b [3], out / dout [3][H][W] planar fp32; 1 <= C <= 512, H*W <= 2^30; sigmoid: 0 = (tanh + 1) / 2.
