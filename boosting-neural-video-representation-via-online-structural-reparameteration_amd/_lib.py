@@ -82,6 +82,24 @@ class EngineDesc(ctypes.Structure):
                 ('act', c_int32), ('reserved2_', c_int32)]
 
 
+class Wgrad16Job(ctypes.Structure):
+    """orn_debug_wgrad16_job (include/orn_debug.h): one problem of the batched weight-gradient launch and its reduction."""
+    _fields_ = [('xpad', c_void_p), ('dypad', c_void_p)] + [(f, c_int32) for f in ('H', 'W', 'C', 'O', 's', 'smax')] + \
+               [('slabs', c_void_p), ('dwf', c_void_p), ('dbf', c_void_p)]
+
+
+class Wgrad16Head(ctypes.Structure):
+    """orn_debug_wgrad16_head: the head's dW / db finish riding on the batched launch."""
+    _fields_ = [('partial', c_void_p), ('blocks', c_int32), ('C', c_int32), ('dw', c_void_p), ('db', c_void_p)]
+
+
+class Wgrad16Stem(ctypes.Structure):
+    """orn_debug_wgrad16_stem: the deferred B == 1 stem backward riding on both launches."""
+    _fields_ = [(f, c_void_p) for f in ('embed', 'w1', 'pre1', 'h1', 'pre2', 'dh2_slabs')] + \
+               [(f, c_int32) for f in ('nslab', 'E', 'Hd', 'Nout')] + \
+               [(f, c_void_p) for f in ('dw0', 'db0', 'dw1', 'db1', 'ws')] + [('ws_bytes', c_size_t)]
+
+
 P = c_void_p
 _SIGS = {
     'orn_version': (c_int, []),
@@ -204,7 +222,13 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_head_fwd_z': (c_int, [P, P, P] + [c_int] * 5 + [P, P]),
                'orn_debug_conv_bwd_f32_head_ws_bytes': (c_size_t, [c_int] * 4),
                'orn_debug_conv_bwd_f32_head': (c_int, [P] * 6 + [c_int] * 6 + [P] * 6 + [c_size_t, P]),
-               'orn_debug_act_eval': (c_int, [c_int, c_int, P, c_size_t, P, P, P])}
+               'orn_debug_act_eval': (c_int, [c_int, c_int, P, c_size_t, P, P, P]),
+               'orn_debug_wgrad16_split': (c_int, [c_int] * 4),
+               'orn_debug_wgrad16_ws_floats': (c_size_t, [c_int] * 3),
+               'orn_debug_wgrad16_step_bf16': (c_int, [c_int, POINTER(Wgrad16Job), POINTER(Wgrad16Head), POINTER(Wgrad16Stem), c_float,
+                                                       c_int, c_int, c_int, POINTER(c_int), P]),
+               'orn_debug_wgrad16_step_f16': (c_int, [c_int, POINTER(Wgrad16Job), POINTER(Wgrad16Head), POINTER(Wgrad16Stem), c_float,
+                                                      c_int, c_int, c_int, POINTER(c_int), P])}
 # the *_act twins of the debug entries that evaluate the block activation: the same arguments + a trailing int
 for _n in ('conv_fwd_bf16', 'conv_fwd_f16', 'conv_dgrad_bf16', 'conv_dgrad_f16', 'head_fwd_bf16', 'head_fwd_f16', 'head_bwd_bf16', 'head_bwd_f16',
            'side_head_fwd_bf16', 'side_head_fwd_f16', 'side_head_bwd_bf16', 'side_head_bwd_f16', 'stage0_fwd', 'stage0_bwd', 'stem_bwd_slabs',

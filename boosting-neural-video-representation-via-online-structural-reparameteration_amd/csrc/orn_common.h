@@ -98,9 +98,13 @@ __device__ __forceinline__ float orn_wave_sum(float v)
 // work-groups of a later launch: the 16-bit engine runs it inside the batched wgrad launch, since only Adam and the stem's last
 // kernel -- which then trails the slab-reduction launch -- consume its results):
 //   d[o] = (sum_s dy_slabs[s][o]) * act'(pre[o]);  db[o] = d[o];  dw[o][k] = d[o] * x[k];  partial[wg][k] = sum_o w[o][k] * d[o]
+// sc (optional, both jobs): a non-finite d[o] raises the flag of the step's scale state, as every other kernel that writes into the
+// gradient arena does (OrnScaleState, below)
 #define ORN_STEM_ROWS 16
+struct OrnScaleState;
+__device__ __forceinline__ void orn_flag_nonfinite(OrnScaleState *sc, float v);
 struct OrnStemL2Job {
-    const float *w, *x, *pre, *dy_slabs; int nslab; size_t slab_ld; int K, N; float *dw, *db, *partial;
+    const float *w, *x, *pre, *dy_slabs; int nslab; size_t slab_ld; int K, N; float *dw, *db, *partial; OrnScaleState *sc;
 };
 // t in [0, 256); sd: 16 floats of LDS; contains a work-group barrier (every thread of the work-group must call)
 template <int ACT = ORN_ACT_SWISH>
@@ -128,6 +132,7 @@ __device__ __forceinline__ void orn_stem_l2_block(const OrnStemL2Job &j, int blk
             if (lane == 0) {
                 const float d = o < N ? tot * OrnAct<ACT>::df_exact(pr[i]) : 0.f;
                 sd[r] = d;
+                orn_flag_nonfinite(j.sc, d);
                 if (o < N) j.db[o] = d;
             }
         }
@@ -152,7 +157,7 @@ __device__ __forceinline__ void orn_stem_l2_block(const OrnStemL2Job &j, int blk
     }
 }
 struct OrnStemW0Job {
-    const float *x; const int *row_idx; size_t row_stride; const float *pre, *dy_slabs; int nslab, K, N; float *dpre, *dw, *db;
+    const float *x; const int *row_idx; size_t row_stride; const float *pre, *dy_slabs; int nslab, K, N; float *dpre, *dw, *db; OrnScaleState *sc;
 };
 // t in [0, 128); sh: 2 floats of LDS private to the row's two waves; contains a work-group barrier (every thread must call)
 template <int ACT = ORN_ACT_SWISH>
@@ -169,7 +174,7 @@ __device__ __forceinline__ void orn_stem_w0_row(const OrnStemW0Job &j, int o, in
     __syncthreads();
     if (!ok) return;
     const float d = (sh[0] + sh[1]) * OrnAct<ACT>::df_exact(j.pre[o]);
-    if (t == 0) { j.dpre[o] = d; j.db[o] = d; }
+    if (t == 0) { j.dpre[o] = d; j.db[o] = d; orn_flag_nonfinite(j.sc, d); }
     for (int k = t; k < j.K; k += 128) j.dw[(size_t)o * j.K + k] = d * x[k];
 }
 

@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) k_stem_bwd_l2(OrnStemL2Job j)
 int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_stride, const float *w1, const float *pre1,
                         const float *h1, const float *pre2, const float *dh2, int B, int E, int Hd, int Nout,
                         float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab, OrnStemW0Job *defer_w0,
-                        OrnStemL2Job *defer_l2, int act)
+                        OrnStemL2Job *defer_l2, int act, OrnScaleState *sc)
 {
     ORN_REQUIRE(orn_act_known(act), "stem_bwd: unknown activation %d", act);
     // ws (orn_stem_bwd_ws_floats): dpre2 [B*Nout] | dpre1 [B*Hd] | dh1 [B*Hd] | partial [CHUNKS*B*Hd], at B == 1 [cdiv(Nout,16)][Hd]
@@ -248,14 +248,14 @@ int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_strid
     float *partial = dh1 + (size_t)B * Hd;
     if (B == 1) {
         const int nwg = orn_cdiv(Nout, ORN_STEM_ROWS);
-        const OrnStemL2Job l2 = {w1, h1, pre2, dh2, dh2_nslab, (size_t)Nout, Hd, Nout, dw1, db1, partial};
+        const OrnStemL2Job l2 = {w1, h1, pre2, dh2, dh2_nslab, (size_t)Nout, Hd, Nout, dw1, db1, partial, sc};
         if (defer_l2 && defer_w0) *defer_l2 = l2;      // the caller runs it as trailing work-groups of a later launch (and w0 behind that one)
         else {
             ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_stem_bwd_l2<A>, dim3(nwg), dim3(256), 0, st, l2));
             ORN_LAUNCH_CHECK("stem_bwd_l2");
         }
         if (defer_w0) {      // the caller appends this job to a later launch (orn_stem_w0_row)
-            *defer_w0 = OrnStemW0Job{embed, row_idx, row_stride, pre1, partial, nwg, E, Hd, dpre1, dw0, db0};
+            *defer_w0 = OrnStemW0Job{embed, row_idx, row_stride, pre1, partial, nwg, E, Hd, dpre1, dw0, db0, sc};
             return 0;
         }
         ORN_ACT_SWITCH(act, A, hipLaunchKernelGGL(k_linear_silu_bwd_w_slabs<A>, dim3(Hd), dim3(128), 0, st, embed, row_idx, row_stride, pre1,

@@ -339,7 +339,7 @@ static int step_back(orn_engine *e, const float *embeds, const float *dimg, OrnL
                                 e->stage0 ? e->scratch + e->stem_ws : e->dh2, 1, d.embed_len, d.stem_dim, Nout, G + d.stem_w0,
                                 G + d.stem_b0, G + d.stem_w1, G + d.stem_b1, e->scratch, st,
                                 e->stage0 ? orn_stage0_slabs(d.layer[0].O, d.layer[0].s) : 1, defer_w0 ? &w0job : nullptr, defer_w0 ? &l2job : nullptr,
-                                d.act));
+                                d.act, defer_w0 ? sc : nullptr));      // (the riders flag a non-finite stem gradient like the wgrad reduction beside them)
     if (ff < nl) ORN_TRY(fast_weight_grads(e, st, pipe, sc, &l2job, &w0job));
     if (pipe && !e->fork_behind_dgrad) ORN_TRY(side_branch_backward(e, st));     // fork: behind the lower blocks' slab reduction
     if (d.multi_res) {      // (behind the head's backward, which carries a 16-bit engine's loss finalize: the step's -- or, batched, the frame's -- record exists)

@@ -179,6 +179,7 @@ int orn_launch_fwd2(const h16 *xpad, const h16 *wb, const float *bias_p, int H, 
 int orn_launch_dgrad2(const h16 *dypad, const h16 *wd, int H, int W, int O, const h16 *zprev, h16 *dyprev, int sp, hipStream_t st,
                       int act);
 // orn_wgrad_bf16.hip
+int orn_wgrad_bf16_split(int H, int W, int O, int smax);      // slab count of a layer under the caller's cap (below 8: none)
 size_t orn_wgrad_bf16_ws_floats(int H, int W, int O);
 int orn_launch_wgrad_bf16(const h16 *xpad, const h16 *dypad, int H, int W, int C, int O, int s, float gscale,
                           float *slabs, float *dwf, float *dbf, hipStream_t st);

@@ -10,7 +10,8 @@ int orn_launch_stem_bwd(const float *embed, const int *row_idx, size_t row_strid
                         float *dw0, float *db0, float *dw1, float *db1, float *ws, hipStream_t st, int dh2_nslab,
                         OrnStemW0Job *defer_w0,    // defer_w0 (B == 1): the last kernel is returned as a job instead of launched
                         OrnStemL2Job *defer_l2,    // defer_l2 (with defer_w0): so is the first one (it then has to run in an EARLIER launch than w0)
-                        int act);            // ORN_ACT_*; a deferred job must be run by a launch instantiated for the same one
+                        int act,             // ORN_ACT_*; a deferred job must be run by a launch instantiated for the same one
+                        OrnScaleState *sc = nullptr);    // (B == 1) a non-finite row of the l2 block / of a deferred w0 job raises its flag
 // dh2_nslab > 1 (B == 1): dh2 holds that many partial rows of Nout floats, summed in fixed order by the first kernel
 size_t orn_stem_bwd_ws_floats(int B, int Hd, int Nout);
 int orn_launch_head_fwd(const float *a, const float *w, const float *b, int B, int C, size_t HW, int sigmoid,

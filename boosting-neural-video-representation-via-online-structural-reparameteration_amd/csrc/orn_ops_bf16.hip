@@ -672,6 +672,80 @@ extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void 
                                                                          target, loss_type, stats, stream, ORN_ACT_SWISH);
 }
 
+// The two weight-gradient launches of a step (include/orn_debug.h) through the table the engine calls them through, in the order and
+// with the argument structs of fast_weight_grads / side_branch_backward (orn_engine_step.hip).  Everything is checked before the first
+// launch or allocation; the slab rule's two host functions live in the bf16 build.
+#ifndef ORN_FP16
+extern "C" int orn_debug_wgrad16_split(int H, int W, int O, int smax) { return orn_wgrad_bf16_split(H, W, O, smax); }
+extern "C" size_t orn_debug_wgrad16_ws_floats(int H, int W, int O) { return orn_wgrad_bf16_ws_floats(H, W, O); }
+#endif
+extern "C" int HOOK(orn_debug_wgrad16_step_bf16, orn_debug_wgrad16_step_f16)(int n, const orn_debug_wgrad16_job *jobs,
+                                                                             const orn_debug_wgrad16_head *head,
+                                                                             const orn_debug_wgrad16_stem *stem, float gs, int use_state,
+                                                                             int side, int act, int *flag, void *stream)
+{
+    ORN_REQUIRE(orn_act_known(act), "debug_wgrad16_step: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
+    ORN_REQUIRE(n >= 0 && n <= ORN_MAX_LAYERS, "debug_wgrad16_step: %d jobs (0..%d)", n, ORN_MAX_LAYERS);
+    ORN_REQUIRE((n == 0 || jobs) && (!use_state || flag), "debug_wgrad16_step: null pointer");
+    ORN_REQUIRE(gs > 0.f, "debug_wgrad16_step: gradient scale %g", (double)gs);
+    for (int i = 0; i < n; ++i) {
+        const orn_debug_wgrad16_job &j = jobs[i];
+        ORN_REQUIRE(j.xpad && j.dypad && j.slabs && j.dwf && j.dbf, "debug_wgrad16_step: null pointer in job %d", i);
+        ORN_REQUIRE(j.H >= 1 && j.W >= 1 && j.s >= 1, "debug_wgrad16_step: job %d: bad sizes %dx%d s=%d", i, j.H, j.W, j.s);
+        ORN_REQUIRE(j.C >= 1 && j.C <= 96 && j.O >= 32 && j.O % 32 == 0 && j.O % (j.s * j.s) == 0, "wgrad_bf16: unsupported C=%d O=%d", j.C, j.O);
+    }
+    if (head) {
+        ORN_REQUIRE(head->partial && head->dw && head->db, "debug_wgrad16_step: null pointer in the head finish");
+        ORN_REQUIRE(head->blocks >= 1 && head->C >= 1, "debug_wgrad16_step: head finish of %d blocks, C=%d", head->blocks, head->C);
+    }
+    if (stem) {
+        const orn_debug_wgrad16_stem &t = *stem;
+        ORN_REQUIRE(t.embed && t.w1 && t.pre1 && t.h1 && t.pre2 && t.dh2_slabs && t.dw0 && t.db0 && t.dw1 && t.db1 && t.ws,
+                    "debug_wgrad16_step: null pointer in the stem job");
+        ORN_REQUIRE(t.nslab >= 1 && t.E > 0 && t.Hd > 0 && t.Nout > 0, "debug_wgrad16_step: bad stem sizes");
+        if (t.ws_bytes < orn_stem_bwd_ws_bytes(1, t.Hd, t.Nout) || (uintptr_t)t.ws % 4 != 0) {
+            orn_set_error("debug_wgrad16_step: stem workspace of %zu bytes, needs orn_stem_bwd_ws_bytes = %zu, 4-byte aligned", t.ws_bytes,
+                          orn_stem_bwd_ws_bytes(1, t.Hd, t.Nout));
+            return ORN_E_WS;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    OrnScaleState *sc = nullptr;
+    OrnScaleState s0 = {};
+    if (use_state) {                                    // the engine's form: the scale lives in a state entry on the device
+        s0.gs = s0.gs_max = gs;
+        s0.inv_gs = 1.0f / gs;
+        ORN_HIP(hipMalloc(&sc, sizeof(s0)));
+        const hipError_t e = hipMemcpy(sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { orn_set_error("debug_wgrad16_step: %s", hipGetErrorString(e)); (void)hipFree(sc); return (int)e; }
+    }
+    int rc = 0;
+    OrnStemW0Job w0job;
+    OrnStemL2Job l2job;
+    if (stem)                                           // deferred: both kernels come back as jobs, nothing is launched here
+        rc = orn_launch_stem_bwd(stem->embed, nullptr, 0, stem->w1, stem->pre1, stem->h1, stem->pre2, stem->dh2_slabs, 1, stem->E, stem->Hd,
+                                 stem->Nout, stem->dw0, stem->db0, stem->dw1, stem->db1, stem->ws, st, stem->nslab, &w0job, &l2job, act, sc);
+    OrnWgradJob wj[ORN_MAX_LAYERS];
+    OrnWgradReduce wr[ORN_MAX_LAYERS];
+    for (int i = 0; i < n; ++i) {
+        const orn_debug_wgrad16_job &j = jobs[i];
+        wj[i] = OrnWgradJob{j.xpad, j.dypad, j.H, j.W, j.C, j.O, j.s, j.slabs, j.smax};
+        wr[i] = OrnWgradReduce{j.slabs, j.H, j.W, j.C, j.O, j.s, 1.0f / gs, j.dwf, j.dbf, sc, j.smax};
+    }
+    OrnHeadFinish hf = {};
+    if (head) hf = OrnHeadFinish{head->partial, head->blocks, head->C, 1.0f / gs, head->dw, head->db, sc};
+    if (rc == 0) rc = ops.wgrad_batch(n, wj, st, head ? &hf : nullptr, stem ? &l2job : nullptr, side ? 1 : 0, act);
+    if (rc == 0) rc = ops.wgrad_reduce_all(n, wr, st, stem ? &w0job : nullptr, act);
+    if (use_state) {
+        hipError_t e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(&s0, sc, sizeof(s0), hipMemcpyDeviceToHost);
+        if (rc == 0 && e != hipSuccess) { orn_set_error("debug_wgrad16_step: %s", hipGetErrorString(e)); rc = (int)e; }
+        if (rc == 0) *flag = s0.flag;
+        (void)hipFree(sc);
+    }
+    return rc;
+}
+
 }  // namespace HNS
 
 const OrnHalfOps *

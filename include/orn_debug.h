@@ -4,8 +4,8 @@
  * the merge backward's (tests/test_gpu_merge16.py), the fused first block's and the slab-summing stem backward's
  * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py), the loss launcher's
  * (tests/test_gpu_fusion6.py), the side heads'
- * (tests/test_gpu_side_head.py), the last stage's 16-bit head's (tests/test_gpu_head16.py) and the fp32 conv path's
- * (tests/test_gpu_conv32_forms.py). */
+ * (tests/test_gpu_side_head.py), the last stage's 16-bit head's (tests/test_gpu_head16.py), the fp32 conv path's
+ * (tests/test_gpu_conv32_forms.py) and the batched weight-gradient and slab-reduction launches' (tests/test_gpu_wgrad16_batch.py). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -284,6 +284,51 @@ ORN_API int orn_debug_conv_bwd_f32_head_act(const float *x, const float *wf, con
                                             const float *head_dout, int C, int O, int H, int W, int sigmoid, int preflip, float *dx,
                                             float *dwf, float *dbf, float *head_dw, float *head_db, void *ws, size_t ws_bytes,
                                             void *stream, int act);
+/* ---- the two weight-gradient launches of every 16-bit step (k_wgrad_nhwc_bf16_all, k_wgrad_bf16_reduce_all; orn_wgrad_bf16.hip) ----
+ * wgrad16_step: exactly what the engine's fast_weight_grads / side_branch_backward enqueue, through the OrnHalfOps members they call
+ * (wgrad_batch, then wgrad_reduce_all), on the caller's buffers; tests/test_gpu_wgrad16_batch.py pins both launches elementwise to fp64.
+ *   jobs:  n in 0..ORN_MAX_LAYERS problems, launched and reduced in the order given.  xpad [H+2][W+2][96], dypad [H+2][W+2][O] (+ 128
+ *          elements of slack) as orn_wgrad_nhwc_bf16; smax: the caller's slab cap (OrnWgradJob::smax, handed to the reduction too; below 8:
+ *          none); slabs: at least orn_debug_wgrad16_ws_floats(H, W, O) floats, of which the first S * (9 * O * 96 + O) are written,
+ *          S = orn_debug_wgrad16_split(H, W, O, smax); dwf [O][C][3][3], dbf [O]: overwritten, every element, un-scaled by 1 / gs.
+ *   head:  (NULL: none) the head's dW / db finish as trailing work-groups of the first launch: partial [blocks][3 C + 3] as the head
+ *          backward leaves them, dw [3][C], db [3] = their column sums / gs.
+ *   stem:  (NULL: none) the B == 1 stem backward in its deferred form, arguments as orn_debug_stem_bwd_slabs_act: its first kernel
+ *          trails the first launch (behind the head's work-groups), its last kernel is one more y slice of the second.  A non-finite
+ *          row of either kernel raises the flag of the scale state.
+ *   gs > 0: the scale the 16-bit gradients carry.  use_state == 0: 1 / gs travels by value, no scale state (flag may be NULL).
+ *          use_state != 0, the engine's form: a scale state of the entry's own (allocated and freed inside, `stream` synchronised) holds
+ *          gs and 1 / gs; *flag: its flag word after the call (1: a dwf, dbf, head dw / db or stem element was not finite).  Same bits.
+ *   side:  1: the launch keeps the default wave priority, as on the engine's side stream.  act: of the stem job.
+ *   Refused with ORN_E_ARG and nothing launched: a null pointer where one is needed, n outside 0..ORN_MAX_LAYERS, H, W or s below 1, the
+ *   launcher's own "wgrad_bf16: unsupported" conditions (C outside 1..96, O % 32 != 0, O % s^2 != 0), head blocks or C below 1, stem sizes
+ *   below 1, gs <= 0, an unknown act; ORN_E_WS: a stem workspace below orn_stem_bwd_ws_bytes(1, Hd, Nout).
+ * wgrad16_split / wgrad16_ws_floats: orn_wgrad_bf16_split and orn_wgrad_bf16_ws_floats themselves (no GPU is touched);
+ * tests/test_wgrad16_split_host.py keeps S * (9 * O * 96 + O) <= ws_floats for every cap. */
+typedef struct orn_debug_wgrad16_job {
+    const void *xpad, *dypad;
+    int32_t H, W, C, O, s, smax;
+    float *slabs, *dwf, *dbf;
+} orn_debug_wgrad16_job;
+typedef struct orn_debug_wgrad16_head {
+    const float *partial;
+    int32_t blocks, C;
+    float *dw, *db;
+} orn_debug_wgrad16_head;
+typedef struct orn_debug_wgrad16_stem {
+    const float *embed, *w1, *pre1, *h1, *pre2, *dh2_slabs;
+    int32_t nslab, E, Hd, Nout;
+    float *dw0, *db0, *dw1, *db1, *ws;
+    size_t ws_bytes;
+} orn_debug_wgrad16_stem;
+ORN_API int orn_debug_wgrad16_split(int H, int W, int O, int smax);
+ORN_API size_t orn_debug_wgrad16_ws_floats(int H, int W, int O);
+ORN_API int orn_debug_wgrad16_step_bf16(int n, const orn_debug_wgrad16_job *jobs, const orn_debug_wgrad16_head *head,
+                                        const orn_debug_wgrad16_stem *stem, float gs, int use_state, int side, int act, int *flag,
+                                        void *stream);
+ORN_API int orn_debug_wgrad16_step_f16(int n, const orn_debug_wgrad16_job *jobs, const orn_debug_wgrad16_head *head,
+                                       const orn_debug_wgrad16_stem *stem, float gs, int use_state, int side, int act, int *flag,
+                                       void *stream);
 #ifdef ORN_CONV_STAMP
 /* Diagnostic build -DORN_CONV_STAMP only: buffer of 128 uint64 per work-group that receives the conv kernel's phase stamps. */
 ORN_API void orn_debug_set_stamps(void *buf);

@@ -31,13 +31,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+# the wgrad's operands, fp64 accumulation and per-element check are shared with test_gpu_wgrad16_batch.py
+from wgrad16_ref import DT, FAST_C, check32, wgrad_channels, wgrad_ref
+from wgrad16_ref import oprime as _oprime, padded as _padded, rand as _rand, scales as _scales
+
 pytestmark = pytest.mark.gpu
 
-FAST_C = 96                    # channels per pixel of every 16-bit channels-last buffer (ORN_FAST_C)
 TH, TW = 8, 32                 # pixel tile of the conv kernels (CB_TH x CB_TW, C2_TH x C2_TW)
 SENT = 7.0                     # finite sentinel, exact in bf16 and fp16
 GUARD = 1024                   # elements of sentinel behind every output
-DT = {'bf16': torch.bfloat16, 'fp16': torch.float16}
 
 # c of the bound above, per form and build: at most 3x the worst ratio measured on an MI355X (the comment gives it).
 C_TOL = {                      # worst measured (MI355X, this module): bf16 / fp16
@@ -105,15 +107,6 @@ def _guard_ok(buf, n, what):
     assert bool((g == SENT).all()), f'{what}: {int((g != SENT).sum())} guard elements behind the output were written'
 
 
-def _rand(shape, gen, chan_scale):
-    """Seeded, not symmetric (a positive mean), a different scale per channel (last dim)."""
-    return (torch.randn(shape, generator=gen, device='cuda') + 0.25) * chan_scale
-
-
-def _scales(n, gen, lo=-1.5, hi=1.5):
-    return torch.exp2(torch.rand(n, generator=gen, device='cuda') * (hi - lo) + lo)
-
-
 def _tile_rows(H, seed, th=TH):
     """Row ranges (of th rows) to compare: all of them on small images; else the first, the last (ragged) and a seeded sample
     of at least 5 % of the interior tile rows."""
@@ -151,25 +144,10 @@ def _check16(k, r, A, half, form, what, gain=1.0, extra=0.0):
 
 def _check32(k, r, A, half, form, what):
     """fp32 output k against r: |k - r| <= c * A."""
-    k = k.double()
-    assert bool(torch.isfinite(k).all()), f'{what}: {int((~torch.isfinite(k)).sum())} non-finite outputs'
-    d = (k - r).abs()
-    ratio = float((d / A.clamp_min(1e-300)).max())
-    _record(form, half, ratio, what)
-    bad = d > C_TOL[form][half] * A
-    if bool(bad.any()):
-        i = int(torch.nonzero(bad.flatten())[0])
-        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements out of bound; first at flat index {i} '
-                             f'(shape {tuple(bad.shape)}): kernel {float(k.flatten()[i])!r} reference {float(r.flatten()[i])!r}')
+    check32(k, r, A, C_TOL[form][half], what, record=lambda ratio: _record(form, half, ratio, what))
 
 
 # ---- operands ---------------------------------------------------------------------------------------------------------------
-def _oprime(O, s):
-    """o' of every PyTorch output channel o: o' = (o % s^2) * Cn + o / s^2 (orn.h: o' = (i*s+j)*Cn + n, o = n*s^2 + i*s + j)."""
-    o = torch.arange(O, device='cuda')
-    return (o % (s * s)) * (O // (s * s)) + o // (s * s)
-
-
 def _weights(O, c_real, s, half, gen):
     """PyTorch-layout wf [O][c_real][3][3] (16-bit-rounded, as k_prep_weights_bf16 casts it), bf [O], and the kernels' layouts
     made by a mirror of k_prep_weights_bf16: wb [9][O'][96], wd [9][96][O'] (taps flipped), bias' [O'], channels >= c_real zero
@@ -193,17 +171,6 @@ def _weights(O, c_real, s, half, gen):
     bias_p = torch.empty(O, device='cuda')
     bias_p[op] = bf
     return wf, bf, wb_buf, wd_buf, bias_p
-
-
-def _padded(H, W, Cp, c_real, half, gen, slack=0, scale=None):
-    """[H+2][W+2][Cp] zero-bordered, random in channels < c_real, zero above; `slack` NaN elements behind it."""
-    n = (H + 2) * (W + 2) * Cp
-    buf = torch.full((n + slack,), float('nan'), dtype=DT[half], device='cuda')
-    x = buf[:n].view(H + 2, W + 2, Cp)
-    x.zero_()
-    sc = scale if scale is not None else _scales(c_real, gen)
-    x[1:H + 1, 1:W + 1, :c_real] = _rand((H, W, c_real), gen, sc).to(DT[half])
-    return buf, x
 
 
 def _conv_ref(xs, w, b=None):
@@ -439,39 +406,14 @@ def _run_wgrad(L, half, H, W, C, O, s, seed):
     _guard_ok(wbuf, nw, 'dwf')
     _guard_ok(bbuf, O, 'dbf')
     dwf = dwf.view(O, C, 3, 3)
-    op = _oprime(O, s)
     # output channels compared: all of them below ~50 M pixel-channel products, else the first 16 and last 16 o' (the ragged
     # last 128-channel tile) and a seeded sample of 32 more (all C and taps of each)
-    if H * W * O <= 50_000_000:
-        sel = torch.arange(O)
-    else:
-        g = torch.Generator().manual_seed(seed)
-        opsel = torch.cat([torch.arange(16), torch.arange(O - 16, O), torch.randperm(O - 32, generator=g)[:32] + 16])
-        inv = torch.empty(O, dtype=torch.long)
-        inv[op.cpu()] = torch.arange(O)
-        sel = inv[opsel].sort().values
-    ops = op.cpu()[sel]
-    r = torch.zeros(len(sel), C, 9, dtype=torch.float64)
-    A = torch.zeros_like(r)
-    rb = torch.zeros(O, dtype=torch.float64)
-    Ab = torch.zeros_like(rb)
-    step = max(1, 2_000_000 // (W * max(C, 96)))
-    for h0 in range(0, H, step):
-        h1 = min(H, h0 + step)
-        dyf = dypad[1 + h0:1 + h1, 1:W + 1].double().cpu().reshape(-1, O)
-        rb += dyf.sum(0)
-        Ab += dyf.abs().sum(0)
-        dy = dyf[:, ops]
-        xs = xpad[h0:h1 + 2, :, :C].double().cpu()
-        for tap in range(9):
-            i, j = divmod(tap, 3)
-            xt = xs[i:i + h1 - h0, j:j + W].reshape(-1, C)
-            r[:, :, tap] += dy.T @ xt
-            A[:, :, tap] += dy.abs().T @ xt.abs()
+    sel = wgrad_channels(H, W, O, s, seed)
+    r, A, rb, Ab = wgrad_ref(xpad, dypad, H, W, C, O, s, sel)
     where = f'wgrad {half} H={H} W={W} C={C} O={O} s={s} S={_wgrad_split(H, W, O)}'
     _check32(dwf.reshape(O, C, 9)[sel].cpu(), r, A, half, 'wgrad', 'dwf ' + where)
     # dbf[o] = sum of dy over pixels, channel o' of o
-    _check32(dbf.cpu(), rb[op.cpu()], Ab[op.cpu()], half, 'wgrad', 'dbf ' + where)
+    _check32(dbf.cpu(), rb, Ab, half, 'wgrad', 'dbf ' + where)
 
 
 WGRAD_CASES = [
