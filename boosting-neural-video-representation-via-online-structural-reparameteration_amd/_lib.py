@@ -1,7 +1,7 @@
 """ctypes binding of liborn.so (include/orn.h).  Fails loudly when the library is missing."""
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORN_MAX_LAYERS = 8
@@ -82,6 +82,11 @@ class EngineDesc(ctypes.Structure):
                 ('act', c_int32), ('reserved2_', c_int32)]
 
 
+class StageOut(ctypes.Structure):
+    """orn_stage_out (include/orn.h, N9): what one stage of orn_engine_eval_stages leaves behind; all NULL = stage not wanted."""
+    _fields_ = [(f, c_void_p) for f in ('targets', 'rgb8', 'img', 'stats', 'msssim')]
+
+
 class Wgrad16Job(ctypes.Structure):
     """orn_debug_wgrad16_job (include/orn_debug.h): one problem of the batched weight-gradient launch and its reduction."""
     _fields_ = [('xpad', c_void_p), ('dypad', c_void_p)] + [(f, c_int32) for f in ('H', 'W', 'C', 'O', 's', 'smax')] + \
@@ -152,6 +157,8 @@ _SIGS = {
     'orn_engine_decode_frames': (c_int, [P, P, P, c_int32, P, P, P, P, P]),
     'orn_engine_eval_frames_ws_bytes': (c_size_t, [POINTER(EngineDesc), c_int]),
     'orn_engine_eval_frames': (c_int, [P, P, P, c_int32, P, P, P, P, P, P, c_size_t, P]),
+    'orn_engine_eval_stages_ws_bytes': (c_size_t, [POINTER(EngineDesc), c_uint32, c_int]),
+    'orn_engine_eval_stages': (c_int, [P, P, P, c_int32, POINTER(StageOut), P, c_size_t, P]),
     'orn_engine_train_step': (c_int, [P, P, P, P, P, P, c_int32, P]),
     'orn_engine_train_steps_graph': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
     'orn_engine_train_steps': (c_int, [P, P, P, P, P, P, c_int32, c_int32, P]),
@@ -190,6 +197,8 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                'orn_debug_merge_h16_bwd': (c_int, [c_int, P, P, P, P, P]),
                'orn_debug_decode_out_ws_bytes': (c_size_t, []),
                'orn_debug_decode_out_f32': (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+               'orn_debug_stage_out_bf16': (c_int, [P, P, P] + [c_int] * 4 + [P, P, P, P, P, c_size_t, P]),
+               'orn_debug_stage_out_f16': (c_int, [P, P, P] + [c_int] * 4 + [P, P, P, P, P, c_size_t, P]),
                'orn_debug_stage0_supported': (c_int, [c_int] * 5),
                'orn_debug_stage0_slabs': (c_int, [c_int] * 2),
                'orn_debug_stage0_fwd': (c_int, [P, P, P] + [c_int] * 5 + [P, P, c_int, c_int, P]),
@@ -231,7 +240,7 @@ _DEBUG_SIGS = {'orn_debug_set': (None, [c_int]), 'orn_debug_set_stamps': (None, 
                                                       c_int, c_int, c_int, POINTER(c_int), P])}
 # the *_act twins of the debug entries that evaluate the block activation: the same arguments + a trailing int
 for _n in ('conv_fwd_bf16', 'conv_fwd_f16', 'conv_dgrad_bf16', 'conv_dgrad_f16', 'head_fwd_bf16', 'head_fwd_f16', 'head_bwd_bf16', 'head_bwd_f16',
-           'side_head_fwd_bf16', 'side_head_fwd_f16', 'side_head_bwd_bf16', 'side_head_bwd_f16', 'stage0_fwd', 'stage0_bwd', 'stem_bwd_slabs',
+           'side_head_fwd_bf16', 'side_head_fwd_f16', 'side_head_bwd_bf16', 'side_head_bwd_f16', 'stage_out_bf16', 'stage_out_f16', 'stage0_fwd', 'stage0_bwd', 'stem_bwd_slabs',
            'conv_fwd_f32', 'head_fwd_z', 'conv_bwd_f32_head'):
     _DEBUG_SIGS[f'orn_debug_{_n}_act'] = (_DEBUG_SIGS[f'orn_debug_{_n}'][0], _DEBUG_SIGS[f'orn_debug_{_n}'][1] + [c_int])
 del _n

@@ -203,5 +203,7 @@ void drop_graphs(orn_engine *e);      // the graph cache is dropped whenever wha
 // side_sc (training forward of a multi-resolution engine): the step's scale-state entry -- behind every block below the last, its
 // stage's head and loss run (side_forward)
 enum { MERGE_NONE = -1 };
-int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set = 0, bool head = true,
+// top: the last block that runs (n_layers - 1: the whole forward).  Below that (orn_engine_eval_stages) the forward ends behind block
+// `top`'s conv, which fills no input buffer for the block above it; neither those blocks nor the last head are launched.
+int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int top, int set = 0, bool head = true,
             OrnScaleState *side_sc = nullptr);

@@ -19,7 +19,7 @@ static int side_forward(orn_engine *e, int i, const int *frame_idx, hipStream_t 
                            orn_loss_spec_of(d.loss_type)->kind == ORN_LOSS_KIND_SSIM ? s.tstats : nullptr, nullptr);
 }
 
-int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int set, bool head, OrnScaleState *side_sc)
+int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z, hipStream_t st, int top, int set, bool head, OrnScaleState *side_sc)
 {
     const bool merge = set != MERGE_NONE;
     const orn_engine_desc &d = e->d;
@@ -29,6 +29,7 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
     const OrnLinearJob lin2 = {e->h1, nullptr, 0, P + d.stem_w1, P + d.stem_b1, 1, d.stem_dim, Nout, e->pre2, e->h2};
     const float *x = e->h2;
     const int nl = d.n_layers, ff = e->ff;
+    assert(top >= 0 && top < nl);
     const void *pack_t = nullptr;
     int pack_t_blocks = 0;
     if (d.erb && merge) {
@@ -55,7 +56,7 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
         for (int i = ff; i < ff + np; ++i) pl[i - ff] = prep_layer(e, i);
         ORN_TRY(e->ops->prep_all(np, pl, st));
     }
-    for (int i = 0; i < nl; ++i) {
+    for (int i = 0; i <= top; ++i) {       // (top < nl - 1, orn_engine_eval_stages: the blocks above it and the last head are not launched)
         const orn_layer_desc &l = d.layer[i];
         LayerBuf &b = e->L[i];
         if (i < ff) {
@@ -83,16 +84,18 @@ int forward(orn_engine *e, const float *embeds, const int *row_idx, bool keep_z,
             if (i == ff && !e->stage0) ORN_TRY(e->ops->to_nhwc(x, l.C, ORN_FAST_C, l.H, l.W, b.xpad, st));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i], st);
             const bool last = (i + 1 == nl);
+            const bool fill_next = i < top;            // the next block's input: the last block and an early exit's top have none to fill
             // pipelined step: the side branch of the previous step still reads the last block's input buffer (its weight gradient)
             // until ev_wgrad, and writes that block's merged kernel (and the head's parameters) until ev_join
             if (e->side_busy && i + 3 == nl && e->side_below) ORN_HIP(hipStreamWaitEvent(st, e->ev_below, 0));   // (this conv overwrites the input of the block below the last)
             if (e->side_busy && i + 2 == nl) ORN_HIP(hipStreamWaitEvent(st, e->ev_wgrad, 0));
             if (e->side_busy && last) { ORN_HIP(hipStreamWaitEvent(st, e->ev_join, 0)); e->side_busy = false; }
-            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, last ? nullptr : e->L[i + 1].xpad, st, l.C, d.act));
+            ORN_TRY(e->ops->conv_fwd(b.xpad, b.wb, b.biasp, l.H, l.W, ORN_FAST_C, l.O, l.s, b.zb, fill_next ? e->L[i + 1].xpad : nullptr, st, l.C, d.act));
             if (e->prof) (void)hipEventRecord(e->prof_ev[2 * i + 1], st);
         }
         if (side_sc && i + 1 < nl) ORN_TRY(side_forward(e, i, row_idx, st, side_sc));
     }
+    if (top + 1 < nl) return 0;
     if (ff < nl) {
         if (head)
             ORN_TRY(e->ops->head_fwd(e->L[nl - 1].zb, P + d.head_w, P + d.head_b, e->Cn_last, (size_t)e->Hout * e->Wout, d.sigmoid, e->img, st,
@@ -111,7 +114,7 @@ extern "C" int orn_engine_decode(orn_engine *e, const float *embed, float *img, 
     ORN_REQUIRE(e && embed && img, "engine_decode: null pointer");
     ORN_REQUIRE_CLOSED(e, "engine_decode");
     hipStream_t st = (hipStream_t)stream;
-    ORN_TRY(forward(e, embed, nullptr, false, st));
+    ORN_TRY(forward(e, embed, nullptr, false, st, e->d.n_layers - 1));
     hipError_t rc = hipMemcpyAsync(img, e->img, (size_t)3 * e->Hout * e->Wout * 4, hipMemcpyDeviceToDevice, st);
     if (rc != hipSuccess) { orn_set_error("engine_decode: copy failed: %s", hipGetErrorString(rc)); return (int)rc; }
     return 0;
@@ -132,7 +135,7 @@ static int decode_frames(orn_engine *e, const float *embeds, const int32_t *rows
     float *ms_ws = msssim ? ws + orn_align((size_t)chunk * 3 * HW * 4) / 4 : nullptr;
     if (stats && n > 0) ORN_HIP(hipMemsetAsync(e->dec_ws + 2 * ORN_DECODE_MAX_BLOCKS, 0, 64 * 4, st));      // the ticket starts at zero
     for (int32_t k = 0; k < n; ++k) {
-        ORN_TRY(forward(e, embeds, rows + k, false, st, k == 0 ? 0 : MERGE_NONE, false));
+        ORN_TRY(forward(e, embeds, rows + k, false, st, d.n_layers - 1, k == 0 ? 0 : MERGE_NONE, false));
         float *planes = img ? img + (size_t)k * HW * 3 : (msssim ? ws + (size_t)(k % chunk) * HW * 3 : nullptr);
         const OrnDecodeOut o = {targets, rows + k, rgb8 ? rgb8 + (size_t)k * HW * 3 : nullptr, planes,
                                 stats ? stats + (size_t)k * 4 : nullptr, e->dec_ws};
@@ -186,4 +189,119 @@ extern "C" int orn_engine_eval_frames(orn_engine *e, const float *embeds, const 
     while (chunk > 0 && orn_engine_eval_frames_ws_bytes(&e->d, chunk) > ws_bytes) --chunk;
     if (chunk < 1) { orn_set_error("engine_eval_frames: workspace %zu < %zu", ws_bytes, orn_engine_eval_frames_ws_bytes(&e->d, 1)); return ORN_E_WS; }
     return decode_frames(e, embeds, rows, n, targets, rgb8, img, stats, msssim, (float *)ws, chunk, (hipStream_t)stream);
+}
+
+// ---- N9  every stage of a multi-resolution fit: one forward per frame up to the highest stage asked for ----
+// The caller's workspace, in floats: per stage with an MS-SSIM column `chunk` image slots [3][H_i][W_i], then ONE MS-SSIM workspace,
+// the largest any of those stages needs for a chunk (their launches follow each other on one stream).  It starts with 64 unused
+// floats, so that a valid request never sizes to 0, the error value.
+struct StagesWs { size_t slot[ORN_MAX_LAYERS], ms, total; };
+static size_t stages_ws_layout(const orn_engine_desc *d, uint32_t msssim_stages, int chunk, StagesWs *out)
+{
+    if (chunk <= 0 || chunk > 65535 / 3 || (d->n_layers < 32 && (msssim_stages >> d->n_layers) != 0)) return 0;
+    const StageGeo g = stage_geometry(d);
+    StagesWs L = {};
+    size_t off = 64, ms_max = 0;
+    for (int i = 0; i < d->n_layers; ++i) {
+        if (!((msssim_stages >> i) & 1u)) continue;
+        if ((g.H[i] < g.W[i] ? g.H[i] : g.W[i]) <= 160) return 0;
+        const size_t ms = orn_msssim_frames_ws_bytes(chunk, 3, g.H[i], g.W[i]);
+        if (!ms) return 0;
+        L.slot[i] = off;
+        off += al((size_t)chunk * 3 * g.H[i] * g.W[i]);
+        if (ms > ms_max) ms_max = ms;
+    }
+    L.ms = off;
+    off += al(ms_max / 4);
+    L.total = off * 4;
+    if (out) *out = L;
+    return L.total;
+}
+
+extern "C" size_t orn_engine_eval_stages_ws_bytes(const orn_engine_desc *d, uint32_t msssim_stages, int chunk)
+{
+    if (check_desc(d) != 0) return 0;
+    return stages_ws_layout(d, msssim_stages, chunk, nullptr);
+}
+
+extern "C" int orn_engine_eval_stages(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n, const orn_stage_out *out, void *ws,
+                                      size_t ws_bytes, void *stream)
+{
+    ORN_REQUIRE(e && embeds && out, "engine_eval_stages: null engine / embeds / out");
+    ORN_REQUIRE_CLOSED(e, "engine_eval_stages");
+    ORN_REQUIRE(n >= 0 && (rows || n == 0), "engine_eval_stages: n=%d frames need a device array of n row indices", n);
+    const orn_engine_desc &d = e->d;
+    const int nl = d.n_layers;
+    const StageGeo g = stage_geometry(&d);
+    int top = -1;
+    uint32_t ms_mask = 0;
+    bool any_stats = false;
+    for (int i = 0; i < nl; ++i) {
+        const orn_stage_out &s = out[i];
+        if (!(s.rgb8 || s.img || s.stats || s.msssim)) continue;       // (a target table alone asks for nothing)
+        ORN_REQUIRE(!(s.stats || s.msssim) || s.targets, "engine_eval_stages: stage %d: stats and msssim need targets", i);
+        if (s.msssim) {
+            ORN_REQUIRE((g.H[i] < g.W[i] ? g.H[i] : g.W[i]) > 160, "engine_eval_stages: stage %d: msssim: image side must exceed 160 (got %dx%d)", i,
+                        g.H[i], g.W[i]);
+            ms_mask |= 1u << i;
+        }
+        any_stats = any_stats || s.stats;
+        top = i;
+    }
+    ORN_REQUIRE(top >= 0, "engine_eval_stages: no stage wanted (every member of every out[i] is null)");
+    if (!d.multi_res)
+        for (int i = 0; i + 1 < nl; ++i)
+            if (out[i].rgb8 || out[i].img || out[i].stats || out[i].msssim) {
+                orn_set_error("engine_eval_stages: stage %d is below the last, and the engine was created with multi_res = 0 (no side heads; its first two "
+                              "blocks may be fused)", i);
+                return ORN_E_STATE;
+            }
+    if (n == 0) return 0;
+    int chunk = 0;
+    StagesWs L = {};
+    if (ms_mask) {
+        ORN_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "engine_eval_stages: msssim needs a 16-byte aligned workspace");
+        chunk = n < 65535 / 3 ? n : 65535 / 3;
+        while (chunk > 0 && stages_ws_layout(&d, ms_mask, chunk, &L) > ws_bytes) --chunk;
+        if (chunk < 1) { orn_set_error("engine_eval_stages: workspace %zu < %zu", ws_bytes, stages_ws_layout(&d, ms_mask, 1, nullptr)); return ORN_E_WS; }
+    }
+    assert(!e->side_busy);          // orn_engine_train_steps joins its side branch before it returns
+    hipStream_t st = (hipStream_t)stream;
+    float *wsf = (float *)ws;
+    // the ticket starts at zero; every output launch of every stage leaves it there for the next one on this stream
+    if (any_stats) ORN_HIP(hipMemsetAsync(e->dec_ws + 2 * ORN_DECODE_MAX_BLOCKS, 0, 64 * 4, st));
+    for (int32_t k = 0; k < n; ++k) {
+        ORN_TRY(forward(e, embeds, rows + k, false, st, top, k == 0 ? 0 : MERGE_NONE, false));
+        for (int i = 0; i <= top; ++i) {
+            const orn_stage_out &s = out[i];
+            if (!(s.rgb8 || s.img || s.stats || s.msssim)) continue;
+            const size_t HW = (size_t)g.H[i] * g.W[i];
+            float *planes = s.img ? s.img + (size_t)k * HW * 3 : (s.msssim ? wsf + L.slot[i] + (size_t)(k % chunk) * HW * 3 : nullptr);
+            const OrnDecodeOut o = {s.targets, rows + k, s.rgb8 ? s.rgb8 + (size_t)k * HW * 3 : nullptr, planes,
+                                    s.stats ? s.stats + (size_t)k * 4 : nullptr, e->dec_ws};
+            if (i + 1 == nl) {               // the last stage: the output stage of orn_engine_decode_frames
+                if (e->ff < nl)
+                    ORN_TRY(e->ops->decode_out(e->L[i].zb, e->params + d.head_w, e->params + d.head_b, e->Cn_last, HW, d.sigmoid, o, st, d.act));
+                else
+                    ORN_TRY(orn_launch_decode_out_f32(e->img, HW, o, st));
+            } else if (i >= e->ff) {         // a 16-bit block's side stage: head + output stage in one kernel
+                ORN_TRY(e->ops->stage_out(e->L[i].zb, e->params + d.side_head_w[i], e->params + d.side_head_b[i], g.C[i], HW, d.sigmoid, o, st, d.act));
+            } else {                         // an fp32 block's side stage: the training forward's head, then the planar output stage
+                ORN_TRY(orn_launch_side_head_fwd_f32(e->L[i].a, e->params + d.side_head_w[i], e->params + d.side_head_b[i], g.C[i], HW, d.sigmoid,
+                                                     e->stage[i].img, st, nullptr));
+                ORN_TRY(orn_launch_decode_out_f32(e->stage[i].img, HW, o, st));
+            }
+        }
+        if (ms_mask && ((k + 1) % chunk == 0 || k + 1 == n)) {
+            const int32_t k0 = k / chunk * chunk;
+            for (int i = 0; i <= top; ++i) {
+                const orn_stage_out &s = out[i];
+                if (!s.msssim) continue;
+                const size_t HW = (size_t)g.H[i] * g.W[i];
+                ORN_TRY(orn_launch_msssim_frames(s.img ? s.img + (size_t)k0 * HW * 3 : wsf + L.slot[i], s.targets, rows + k0, k + 1 - k0, 3, g.H[i],
+                                                 g.W[i], s.msssim + k0, wsf + L.ms, st));
+            }
+        }
+    }
+    return 0;
 }

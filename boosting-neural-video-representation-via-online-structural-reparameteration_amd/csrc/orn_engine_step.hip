@@ -240,7 +240,7 @@ static int step_front(orn_engine *e, const float *embeds, const orn_step_sched *
         ORN_LAUNCH_CHECK("advance");
     }
     const int *fidx = &step_cur(e, o)->frame;
-    return forward(e, embeds, fidx, true, st, (o.batch > 0 && o.bframe > 0) ? (int)MERGE_NONE : (o.pipe && e->side_busy) ? 1 : 0, true,
+    return forward(e, embeds, fidx, true, st, d.n_layers - 1, (o.batch > 0 && o.bframe > 0) ? (int)MERGE_NONE : (o.pipe && e->side_busy) ? 1 : 0, true,
                    d.multi_res ? e->sc + o.cur : nullptr);
 }
 

@@ -191,6 +191,8 @@ void set_debug_wgrad(int flags);
 // orn_decode_out.hip
 int orn_launch_decode_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st,
                               int act);
+int orn_launch_stage_out_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st,
+                             int act);      // a side stage's head + output stage (any C in 1..512)
 // orn_side_head.hip
 int orn_launch_side_head_fwd_h16(const h16 *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
                                  OrnScaleState *sc, int act);

@@ -254,6 +254,9 @@ struct OrnHalfOps {
     int (*side_head_fwd)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st, OrnScaleState *sc, int act);
     int (*side_head_bwd)(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp, float lw,
                          float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc, int act);
+    // per-stage evaluation (orn_engine_eval_stages): a side stage's head on its block's z + the output stage in one kernel (same per-pixel
+    // arithmetic as side_head_fwd)
+    int (*stage_out)(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st, int act);
 };
 const OrnHalfOps *orn_half_ops_bf16();
 const OrnHalfOps *orn_half_ops_f16();

@@ -391,10 +391,12 @@ static int a_side_head_fwd(const void *z, const float *w, const float *b, int C,
 static int a_side_head_bwd(const void *z, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid, int sp, float lw,
                            float gs, void *dypad, float *dw, float *db, float *ws, hipStream_t st, OrnScaleState *sc, int act)
 { return orn_launch_side_head_bwd_h16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, lw, gs, (h16 *)dypad, dw, db, ws, st, sc, act); }
+static int a_stage_out(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st, int act)
+{ return orn_launch_stage_out_h16((const h16 *)z, w, b, C, HW, sigmoid, o, st, act); }
 
 const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
                         a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out,
-                        a_side_head_fwd, a_side_head_bwd};
+                        a_side_head_fwd, a_side_head_bwd, a_stage_out};
 
 // ================================================================================================
 // test / per-op hooks: the 16-bit block on PyTorch-layout fp32 tensors (conversions included).  Built in both element

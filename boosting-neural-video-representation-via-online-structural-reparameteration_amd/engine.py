@@ -236,22 +236,114 @@ class _Decoding:
         self._decode_keep = (embeds, frames, rows)          # alive until the stream has drained
         return out
 
-    def _target_frames(self, frames: torch.Tensor, what: str = '') -> torch.Tensor:
-        """Target frames as the engine reads them: fp32 [N,3,h,w] on the device at the decoder's output size.  fp32 [N,3,H,W] or
-        uint8 [N,H,W,3] (as PIL decodes it) of another size are pooled there as the reference pools every target,
+    def _target_frames(self, frames: torch.Tensor, what: str = '', hw=None) -> torch.Tensor:
+        """Target frames as the engine reads them: fp32 [N,3,h,w] on the device at `hw` (default: the decoder's output size).  fp32
+        [N,3,H,W] or uint8 [N,H,W,3] (as PIL decodes it) of another size are pooled there as the reference pools every target,
         F.adaptive_avg_pool2d(data, output.shape[-2:]) (main_train.py:239,420; main_eval.py:467,807), by ops.ingest_frames."""
+        hw = tuple(self.out_hw if hw is None else hw)
         if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
             raise OrnError(f'{what}frames must be a [N,3,H,W] tensor (or uint8 [N,H,W,3]), got {tuple(getattr(frames, "shape", ()))}')
         if frames.dtype == torch.uint8:
             if frames.shape[3] != 3:
                 raise OrnError(f'{what}uint8 frames {tuple(frames.shape)} are not [N,H,W,3]')
-            return ops.ingest_frames(frames.to(self.device), self.out_hw)
+            return ops.ingest_frames(frames.to(self.device), hw)
         if frames.shape[1] != 3:
             raise OrnError(f'{what}frames {tuple(frames.shape)} are not [N,3,H,W]')
         frames = frames.to(self.device, torch.float32).contiguous()
-        if tuple(frames.shape[2:]) != tuple(self.out_hw):
-            frames = ops.ingest_frames(frames, self.out_hw)
+        if tuple(frames.shape[2:]) != hw:
+            frames = ops.ingest_frames(frames, hw)
         return frames
+
+    def stage_targets(self, frames=None, stages: Optional[Sequence[int]] = None) -> dict:
+        """{stage: target table fp32 [N,3,H_i,W_i]} as decode_stages reads them.  frames: a list with one table per stage of `stages`
+        (any table not at its stage's size is pooled there), or ONE tensor, pooled to every stage from itself as the reference pools
+        every stage's target from the source (main_train.py:420); None: the resident tables (TrainEngine.set_video), where there are any."""
+        hws = self.stage_hw()
+        stages = list(range(len(hws))) if stages is None else list(stages)
+        out = {}
+        if frames is None:
+            resident = list(getattr(self, 'stage_frames', None) or []) + [self.frames]
+            for s in stages:
+                if len(resident) == len(hws) and resident[s] is not None:
+                    out[s] = resident[s]
+                elif s == len(hws) - 1 and self.frames is not None:
+                    out[s] = self.frames
+            return out
+        if isinstance(frames, (list, tuple)):
+            if len(frames) != len(stages):
+                raise OrnError(f'decode_stages: {len(frames)} frame tables for {len(stages)} stages (one per requested stage, or one tensor)')
+            return {s: self._target_frames(t, f'decode_stages: stage {s}: ', hws[s]) for s, t in zip(stages, frames)}
+        return {s: self._target_frames(frames, 'decode_stages: ', hws[s]) for s in stages}
+
+    def decode_stages(self, stages=None, rows=None, embeds=None, frames=None, rgb8=True, f32=False, stats=True, msssim=False,
+                      chunk=None) -> dict:
+        """decode_frames for any stage of a multi-resolution fit (orn_engine_eval_stages; main_train.py:378-438): one forward per frame
+        up to the highest stage asked for -- the blocks above it and the last head do not run -- and one output launch per stage.
+        stages: an int, a sequence, or None for all.  frames: as stage_targets (one table per requested stage, or one tensor pooled to
+        every stage; default: the resident tables).  Returns {stage: dict} with decode_frames' keys at that stage's size: 'rgb8'
+        [n,H_i,W_i,3], 'img' [n,3,H_i,W_i], 'stats' [n,4], 'msssim' [n] (zeros for a stage less than 160 high, utils.msssim_fn's rule).
+        The last stage's entries are the bytes decode_frames gives.  Needs a multi-resolution engine (a TrainEngine of such a model,
+        or Decoder(stages=True)) for any stage below the last.  No host sync."""
+        hws = self.stage_hw()
+        nl = len(hws)
+        sel = list(range(nl)) if stages is None else [stages] if isinstance(stages, int) else [int(s) for s in stages]
+        if not sel or len(set(sel)) != len(sel) or min(sel) < 0 or max(sel) >= nl:
+            raise OrnError(f'decode_stages: stages {sel} must be distinct indices in [0, {nl})')
+        embeds = self.embeds if embeds is None else embeds.to(self.device, torch.float32).contiguous()
+        if embeds is None:
+            raise OrnError('decode_stages: no embeds given and no video resident (set_video)')
+        if embeds.dim() != 2 or embeds.shape[1] != self.desc.embed_len:
+            raise OrnError(f'decode_stages: embeds {tuple(embeds.shape)} vs (*, {self.desc.embed_len})')
+        need = stats or msssim
+        targets = self.stage_targets(frames, sel) if need else {}
+        if need and any(s not in targets for s in sel):
+            raise OrnError(f'decode_stages: stats and msssim need target frames of stages {[s for s in sel if s not in targets]} '
+                           '(frames=, or set_video on a multi-resolution TrainEngine)')
+        if rows is None:
+            rows = torch.arange(embeds.shape[0], dtype=torch.int32)
+        rows = torch.as_tensor(rows).to(torch.int32).reshape(-1)
+        n = int(rows.numel())
+        limit = min([embeds.shape[0]] + [t.shape[0] for t in targets.values()])
+        if n and (int(rows.min()) < 0 or int(rows.max()) >= limit):        # the device would read out of bounds
+            raise OrnError(f'decode_stages: row index out of range [0, {limit})')
+        rows = rows.to(self.device).contiguous()
+        recs = (_lib.StageOut * _lib.ORN_MAX_LAYERS)()
+        result, mask, wanted, zero_col = {}, 0, False, False
+        for s in sel:
+            H, W = hws[s]
+            out = result[s] = {}
+            if rgb8:
+                out['rgb8'] = torch.empty(n, H, W, 3, dtype=torch.uint8, device=self.device)
+            if f32:
+                out['img'] = torch.empty(n, 3, H, W, device=self.device)
+            if stats:
+                out['stats'] = torch.empty(n, 4, device=self.device)
+            ms = None
+            if msssim and H < 160:                          # utils.msssim_fn (utils.py:201-211): no MS-SSIM below 160 rows
+                out['msssim'] = torch.zeros(n, device=self.device)
+                zero_col = True
+            elif msssim:
+                ms = out['msssim'] = torch.empty(n, device=self.device)
+                mask |= 1 << s
+            r = recs[s]
+            r.rgb8, r.img, r.stats, r.msssim = (_lib.ptr(t) for t in (out.get('rgb8'), out.get('img'), out.get('stats'), ms))
+            if stats or ms is not None:
+                r.targets = _lib.ptr(targets[s])
+            wanted = wanted or rgb8 or f32 or stats or ms is not None
+        ws = None
+        if mask and n:
+            c = max(1, min(n, chunk or 8))
+            nbytes = lib().orn_engine_eval_stages_ws_bytes(byref(self.desc), mask, c)
+            if nbytes == 0:
+                raise OrnError(f'decode_stages: MS-SSIM needs images larger than 160 x 160 (stages {[hws[s] for s in sel]})')
+            ws = getattr(self, '_stages_ws_buf', None)
+            if ws is None or ws.numel() < nbytes:
+                ws = self._stages_ws_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if wanted or not zero_col:      # (zero columns alone need no decode; no output at all is the library's error)
+            check(lib().orn_engine_eval_stages(self._h, _lib.ptr(embeds), _lib.ptr(rows), c_int32(n), recs, _lib.ptr(ws),
+                                               c_size_t(ws.numel() if ws is not None else 0), _lib.stream()), 'orn_engine_eval_stages')
+        self._decode_keep = (embeds, targets, rows)         # alive until the stream has drained
+        return result
 
     def _eval_ws(self, chunk: int) -> torch.Tensor:
         """The workspace of orn_engine_eval_frames for `chunk` frames, cached on the object (kept alive; it only grows)."""
@@ -277,12 +369,16 @@ class Decoder(_Decoding):
     """Decode-only engine for a fitted model (loaded from a train-mode or a `_deploy` checkpoint, checkpoint.load_into): the
     parameter arena and the workspace, no gradient or Adam arenas -- the training entry points refuse such an engine.
     precision: 'fp16' | 'bf16' run the blocks on 16-bit MFMA as the training engine does (the arithmetic a fit at that
-    precision was evaluated with); 'fp32' is the reference's."""
+    precision was evaluated with); 'fp32' is the reference's.  stages=True (multi-resolution models only): the engine also knows the
+    heads of the stages below the last, for decode_stages."""
 
-    def __init__(self, model, precision: str = 'fp16', device: Optional[torch.device] = None):
+    def __init__(self, model, precision: str = 'fp16', device: Optional[torch.device] = None, stages: bool = False):
+        if stages and not is_multi_res(model):
+            raise OrnError('Decoder(stages=True) needs a multi-resolution model (a head on every stage; Generator(sin_res=False))')
         self._rehome(model, device, grads=False)
-        # (a multi-resolution model decodes its last stage: the single-resolution engine on the tensors the two share)
-        self._create(precision, False, 'L2', multi_res=False)
+        # (by default a multi-resolution model decodes its last stage: the single-resolution engine on the tensors the two share;
+        # stages=True describes every stage's head, so that decode_stages reaches the stages below the last)
+        self._create(precision, False, 'L2', multi_res=bool(stages))
 
 
 class TrainEngine(_Decoding):

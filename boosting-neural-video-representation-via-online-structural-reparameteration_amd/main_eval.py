@@ -6,6 +6,11 @@ quantisation + Huffman size estimate (--quant_bit) -> decode every frame (PSNR, 
 orn_engine_eval_frames call, PSNR of the float image and of the 8-bit pixels, the per-frame MS-SSIM and the `--dump_images`
 bytes computed on the device); the default `eager` is the per-op fp32 module forward, frame by frame.
 
+`--decode_stage all|K` (with `--decoder engine`, without `--single_res`): a multi-resolution fit is a scalable bitstream.  `all`
+evaluates every stage in one call (engine.Decoder(stages=True).decode_stages, orn_engine_eval_stages) and prints one value per stage;
+`K` decodes stage K alone -- the blocks above it and the last head do not run -- with PSNR, MS-SSIM where the size allows, FPS,
+`--dump_images` and bpp at that stage's size.
+
 `--finetune` (main_eval.py:213-545): load the TRAIN-mode checkpoint, prune the stem Linear weights and every conv
 branch weight together (global L1), fine-tune `--finetune_epochs` on the native engine, then deploy/quantise/evaluate.
 The reference's behaviour is kept, quirks included: Q1 -- with ERB the online merge reads `.weight`
@@ -93,7 +98,67 @@ def eval_parser():
     p.add_argument('--cycles', type=int, default=1)
     p.add_argument('--video', default=None, help='which video of a multi-video training job (--dataset a,b,c or a multi-rank '
                                                   '--synthetic job: synthetic<k>) to evaluate; default: the first')
+    p.add_argument('--decode_stage', default=None, metavar='all|K',
+                   help='--decoder engine, multi-resolution fits: evaluate every stage in one call (all), or decode stage K alone '
+                        '(0 = the smallest image; the blocks above K do not run)')
     return p
+
+
+def check_decode_stage(args):
+    """None (flag absent), 'all' or the stage index of --decode_stage; ValueError for a combination that has no such decode.  Reads
+    nothing but args."""
+    ds = getattr(args, 'decode_stage', None)
+    if ds is None:
+        return None
+    if args.decoder != 'engine':
+        raise ValueError(f'--decode_stage {ds} needs --decoder engine: the per-stage decode is the native engine\'s')
+    if args.single_res:
+        raise ValueError(f'--decode_stage {ds} with --single_res: a single-resolution generator has one stage, the output')
+    if ds == 'all':
+        return 'all'
+    try:
+        k = int(ds)
+    except ValueError:
+        raise ValueError(f'--decode_stage {ds!r}: expected all or a stage index') from None
+    if not 0 <= k < len(args.strides):
+        raise ValueError(f'--decode_stage {k}: the generator has stages 0..{len(args.strides) - 1} (--strides)')
+    return k
+
+
+def _stage_decode(model, args, embeds, tables, outf, n_param, bits, which):
+    """--decode_stage: `tables` holds the target table of every stage decoded.  all: every stage in one call, the usual line for the last stage
+    and one more with a value per stage; K: stage K alone, everything at its size."""
+    from . import engine as oeng
+    dec = oeng.Decoder(model, precision=args.precision, stages=True)
+    hws = dec.stage_hw()
+    sel = list(range(len(hws))) if which == 'all' else [which]
+    n = embeds.shape[0]
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = dec.decode_stages(stages=sel, embeds=embeds, frames=[tables[s] for s in sel], rgb8=True, f32=False, stats=True, msssim=True)
+    torch.cuda.synchronize()
+    fps = n / (time.time() - t0)
+    show = sel[-1]                                          # the stage the Eval line, the images and the return value belong to
+    st = out[show]['stats'].double().mean(0)
+    psnr, psnr8 = float(st[1]), float(st[3])
+    if args.dump_images:
+        from PIL import Image
+        visual_dir = os.path.join(outf, 'visualize')
+        os.makedirs(visual_dir, exist_ok=True)
+        print(f'Saving predictions to {visual_dir}')
+        for k, arr in enumerate(out[show]['rgb8'].cpu().numpy()):
+            Image.fromarray(arr).save(os.path.join(visual_dir, f'pred_{k}.png'))
+    if which == 'all':
+        cols = [out[s]['stats'].double().mean(0) for s in sel]
+        print('Eval stages PSNR: [' + ', '.join(f'{float(c[1]):.2f}' for c in cols) + '], 8-bit PSNR: ['
+              + ', '.join(f'{float(c[3]):.2f}' for c in cols) + '], MS-SSIM: [' + ', '.join(f'{float(out[s]["msssim"].mean()):.4f}' for s in sel) + ']')
+    tag = 'all stages' if which == 'all' else f'stage {which}, {hws[which][0]}x{hws[which][1]}'
+    msg = (f'Eval: PSNR {psnr:.2f} dB, 8-bit PSNR {psnr8:.2f} dB, MS-SSIM {float(out[show]["msssim"].mean()):.4f}, '
+           f'decode {fps:.1f} FPS (engine, {args.precision}, {tag}), params {n_param / 1e6:.3f} M')
+    if bits is not None:
+        msg += f', bpp {bits / (n * hws[show][0] * hws[show][1]):.4f}'
+    print(msg)
+    return psnr
 
 
 def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
@@ -126,6 +191,7 @@ def _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw):
 
 def main(argv=None):
     args = eval_parser().parse_args(argv)
+    decode_stage = check_decode_stage(args)
     if args.finetune and args.batchSize > 1:
         # the fine-tune's loop takes one frame per optimiser step; a -b it ignored would silently be another recipe
         raise ValueError(f'--finetune with -b/--batchSize {args.batchSize}: the prune fine-tune steps one frame at a time; use -b 1 '
@@ -200,6 +266,20 @@ def main(argv=None):
     frames, pos = load_frames(args, hw, 'cuda', args.dataset, vid_index, args.test_gap)       # val_dataset: CustomDataSet(frame_gap=test_gap)
     n = frames.shape[0]
     embeds = PE(pos)
+    if decode_stage is not None:
+        # every stage's target is pooled from the source like the last stage's (main_train.py:420); synthetic frames ARE the source, at
+        # the decoder's size
+        from . import engine as oeng
+        shws = oeng.stage_hw(model)
+        tables = {}
+        for s in (range(len(shws)) if decode_stage == 'all' else [decode_stage]):
+            if tuple(shws[s]) == tuple(hw):
+                tables[s] = frames
+            elif args.synthetic:
+                tables[s] = ops.ingest_frames(frames, tuple(shws[s]))
+            else:
+                tables[s] = load_frames(args, shws[s], 'cuda', args.dataset, vid_index, args.test_gap)[0]
+        return _stage_decode(model, args, embeds, tables, outf, n_param, bits, decode_stage)
     if args.decoder == 'engine':
         return _engine_decode(model, args, embeds, frames, outf, n_param, bits, hw)
     psnrs = []

@@ -246,7 +246,10 @@ def adam_state_dict(model, eng, args, applied=None):
 def evaluate(model, eng, args, val=None, gap=None):
     """main_train.py:377-438: forward over the validation samples -- CustomDataSet(frame_gap=test_gap): sample k is entry
     k * test_gap, floor(N / test_gap) of them -- PSNR per frame, decoder FPS.  val: (frames, embeds) when the validation
-    samples are not a subset of the resident training frames (frame_gap > 1)."""
+    samples are not a subset of the resident training frames (frame_gap > 1).  --decoder engine on a multi-resolution engine: every
+    stage's mean PSNR and MS-SSIM are left in eng.stage_eval (the reference's psnr_list / msssim_list; None otherwise); the returned
+    triple is the last stage's."""
+    eng.stage_eval = None
     frames, embeds = val if val is not None else (eng.frames, eng.embeds)
     gap = args.test_gap if gap is None else gap
     idx = list(range(frames.shape[0])) if val is not None else [k * gap for k in range(frames.shape[0] // gap)]
@@ -254,9 +257,19 @@ def evaluate(model, eng, args, val=None, gap=None):
         # one call: the merge runs once, PSNR and MS-SSIM per frame stay on the device (orn_engine_eval_frames)
         torch.cuda.synchronize()
         t0 = time.time()
-        out = eng.decode_frames(rows=idx, embeds=embeds, frames=frames, rgb8=False, stats=True, msssim=True)
+        stages = None
+        if getattr(eng, 'multi_res', False):
+            # every stage from one forward per frame (orn_engine_eval_stages); validation frames that are not resident are pooled to
+            # every stage from the table given
+            stages = eng.decode_stages(rows=idx, embeds=embeds, frames=None if val is None else frames, rgb8=False, stats=True, msssim=True)
+            out = stages[max(stages)]
+        else:
+            out = eng.decode_frames(rows=idx, embeds=embeds, frames=frames, rgb8=False, stats=True, msssim=True)
         torch.cuda.synchronize()
         dt = time.time() - t0
+        if stages is not None:
+            eng.stage_eval = ([float(stages[s]['stats'][:, 1].mean()) for s in sorted(stages)],
+                              [float(stages[s]['msssim'].mean()) for s in sorted(stages)])
         return float(out['stats'][:, 1].mean()), len(idx) / dt, float(out['msssim'].mean())
     psnrs = []
     torch.cuda.synchronize()
@@ -470,6 +483,9 @@ def fit_video(args, name, vid_index, rank, _inject=None):
         is_val_best = False
         if is_eval:
             val_psnr, fps, val_msssim = evaluate(model, eng, args, val)
+            if getattr(eng, 'stage_eval', None):                     # one value per stage, as the reference prints them
+                say('Eval stages PSNR: [' + ', '.join(f'{v:.2f}' for v in eng.stage_eval[0]) + '], MS-SSIM: ['
+                    + ', '.join(f'{v:.4f}' for v in eng.stage_eval[1]) + ']')
             is_val_best = val_psnr > float(best.val_psnr)               # main_train.py:310-312
             if is_val_best:
                 best.val_psnr = torch.tensor(val_psnr)

@@ -43,7 +43,8 @@ extern "C" {
                                   * to orn_engine_desc, branch_kind + branch[] (N7: the paper's comparison blocks through an online merge);
                                   * + orn_engine_set_stage_targets / _stage_target_stats / _stage_stats and, appended to orn_engine_desc, multi_res + lw +
                                   * side_head_w[] / side_head_b[] (N8: a head and a loss at every stage); + ORN_ACT_SWISH / ORN_ACT_GELU, the *_act entry points and, appended to
-                                  * orn_engine_desc, act (--act gelu) */
+                                  * orn_engine_desc, act (--act gelu); + orn_stage_out, orn_engine_eval_stages_ws_bytes, orn_engine_eval_stages (N9: decode and
+                                  * evaluate any stage of a multi-resolution fit) */
 /* Every entry point below is exported with default visibility; the library is built with -fvisibility=hidden, so these (and
  * the probe-only ones of orn_debug.h) are its whole dynamic symbol table. */
 #define ORN_API __attribute__((visibility("default")))
@@ -447,7 +448,8 @@ ORN_API int orn_engine_set_target_stats(orn_engine *e, const float *stats);
  * gradient buffer that block i + 1's dgrad has already written (orn_side_head.hip; 16-bit layers: the stored half + the term in fp32,
  * rounded once).  The last stage, every conv, merge and Adam launch are those of a single-resolution engine; lw = 0 gives its bits.
  * Forms: orn_engine_train_step, orn_engine_train_steps (always the serial form here), _graph, _batch.  The split step
- * (orn_engine_step_forward) returns ORN_E_ARG: a caller's objective takes one image.  Decode and evaluation run no side head.
+ * (orn_engine_step_forward) returns ORN_E_ARG: a caller's objective takes one image.  orn_engine_decode / _decode_frames / _eval_frames give the last stage alone; every stage's image
+ * comes from orn_engine_eval_stages (N9), which runs the side heads' forward inside its output kernel.
  * A 16-bit engine keeps its first block apart from the second (no fused first pair), so that the block's output exists in a layout a
  * head can read.  A non-finite pre-activation of a side head, side loss or side-head gradient raises the step's flag like any other.
  * orn_engine_create refuses (ORN_E_ARG, the stage named) a descriptor whose loss does not take a stage's size: an SSIM kind needs
@@ -463,6 +465,42 @@ ORN_API int orn_engine_set_target_stats(orn_engine *e, const float *stats);
 ORN_API int orn_engine_set_stage_targets(orn_engine *e, int32_t stage, const float *frames);
 ORN_API int orn_engine_set_stage_target_stats(orn_engine *e, int32_t stage, const float *stats);
 ORN_API int orn_engine_set_stage_stats(orn_engine *e, float *out, int32_t n_slots);
+/* ---- N9  decode and evaluate any stage of a multi-resolution fit          main_train.py:378-438 (psnr_fn / msssim_fn over output_list) ----
+ * A multi-resolution fit is a scalable bitstream: the image of stage i needs the blocks 0..i and that stage's head only.
+ * orn_engine_eval_stages is orn_engine_eval_frames with one output record per stage, out[0 .. n_layers): per frame ONE forward that
+ * runs up to `top`, the highest stage with any output asked for -- the blocks above it and the last head are not launched, and block
+ * `top`'s conv fills no input buffer for the block above -- then one output launch per wanted stage.  The weight-only work of the
+ * forward runs for frame 0 only, as in orn_engine_decode_frames.
+ *   Side stage of a 16-bit block: one kernel (k_stage_out_nhwc, orn_decode_out.hip) reads the block's channels-last pre-activation,
+ *     applies the stage's head with the per-pixel arithmetic of the training forward's side head (so the fp32 value is the image that
+ *     step's loss saw, bit for bit, wherever the conv launcher picks the kernel form it picks in training; a conv that fills no
+ *     next-block buffer may take another form on large images, and the values then differ by 16-bit rounding of the block's output)
+ *     and writes what is asked for; no fp32 image goes through memory on the way to the bytes.
+ *   Side stage of an fp32 block (every stage of an fp32 engine; the first block of a 16-bit multi-resolution engine): the training
+ *     forward's fp32 side head into the engine's own stage image, then the planar output stage.
+ *   The last stage ends in the output stage of orn_engine_decode_frames: its rgb8 / img / stats / msssim are the bytes
+ *     orn_engine_eval_frames writes on the same engine.
+ * Per stage, each output optional as in orn_engine_decode_frames (sizes H_i x W_i: the stage's): rgb8, img, stats [n][4], and msssim
+ * [n] through the batched MS-SSIM at that stage's size after every chunk of frames, on the caller's img or on slots in ws (the values
+ * do not depend on the chunk).  targets: the stage's own table, indexed by rows[k] like `embeds`.
+ * ws: orn_engine_eval_stages_ws_bytes(d, mask of the stages with an msssim column, chunk >= 1) bytes, 16-byte aligned, read only when
+ * an msssim column is asked for (the largest chunk that fits is used); 0 for a bad descriptor, chunk < 1, or a mask naming a stage
+ * that does not exist or whose smaller side is <= 160.  The engine's own workspace keeps its size.
+ * Refused before anything is enqueued: no stage wanted; stats / msssim without targets; msssim on a stage with a side <= 160
+ * (ORN_E_ARG); a stage below the last on an engine created with multi_res = 0, which has no side heads and may run its first two
+ * blocks fused (ORN_E_STATE); a workspace too small for one frame (ORN_E_WS); an open split step (ORN_E_STATE).
+ * The engine may be decode-only (null grads / Adam arenas) with multi_res = 1.  No sync, capturable, one stream at a time.  It changes
+ * no parameter, gradient or optimiser state. */
+typedef struct orn_stage_out {          /* one per stage; all members NULL = stage not wanted */
+    const float *targets;               /* [*][3][H_i][W_i] fp32, indexed by rows[k] (needed by stats / msssim) */
+    uint8_t *rgb8;                      /* [n][H_i][W_i][3] */
+    float *img;                         /* [n][3][H_i][W_i] */
+    float *stats;                       /* [n][4], as orn_engine_decode_frames */
+    float *msssim;                      /* [n]; min(H_i, W_i) must exceed 160 */
+} orn_stage_out;
+ORN_API size_t orn_engine_eval_stages_ws_bytes(const orn_engine_desc *d, uint32_t msssim_stages, int chunk);
+ORN_API int orn_engine_eval_stages(orn_engine *e, const float *embeds, const int32_t *rows, int32_t n,
+                                   const orn_stage_out *out /* [n_layers] */, void *ws, size_t ws_bytes, void *stream);
 /* One eager training step with HIP events around the conv launches, on the launch stream; synchronises it.  ms_out (host,
  * 2*n_layers + 2 floats): [i] forward conv of layer i, [n_layers + i] dgrad launch of layer i (0: none), [2*n_layers] the
  * batched wgrad launch of the 16-bit layers, [2*n_layers + 1] its split-K reduction (0 in fp32 mode, where each layer's

@@ -47,6 +47,20 @@ ORN_API int orn_debug_merge_h16_bwd(int n, const int *co, const float *const *in
 ORN_API size_t orn_debug_decode_out_ws_bytes(void);
 ORN_API int orn_debug_decode_out_f32(const float *img, int H, int W, const float *target, uint8_t *rgb8, float *img_out,
                                      float *stats, void *ws, size_t ws_bytes, void *stream);
+/* The output stage of a SIDE stage of orn_engine_eval_stages (include/orn.h N9; k_stage_out_nhwc, orn_decode_out.hip) on a caller's
+ * channels-last pre-activation z [H][W][C] (bf16 / IEEE half, 2-byte aligned; 16-byte loads where C % 8 == 0 and z is 16-byte
+ * aligned) and head w [3][C], b [3]; 1 <= C <= 512, H*W <= 2^30; sigmoid: 0 = (tanh + 1) / 2.  Outputs and workspace as
+ * orn_debug_decode_out_f32: rgb8 [H][W][3], img [3][H][W] -- bit-identical to orn_debug_side_head_fwd_* on the same inputs --,
+ * stats[4] against target [3][H][W]; the ticket word (float index 2 * 8192 of ws) is zero again after the launch.  ORN_E_ARG, with
+ * nothing enqueued, for a bad argument.  The _act twins take ORN_ACT_* last.  tests/test_gpu_stage_out.py. */
+ORN_API int orn_debug_stage_out_bf16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, const float *target,
+                                     uint8_t *rgb8, float *img, float *stats, void *ws, size_t ws_bytes, void *stream);
+ORN_API int orn_debug_stage_out_f16(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, const float *target,
+                                    uint8_t *rgb8, float *img, float *stats, void *ws, size_t ws_bytes, void *stream);
+ORN_API int orn_debug_stage_out_bf16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, const float *target,
+                                         uint8_t *rgb8, float *img, float *stats, void *ws, size_t ws_bytes, void *stream, int act);
+ORN_API int orn_debug_stage_out_f16_act(const void *z, const float *w, const float *b, int C, int H, int W, int sigmoid, const float *target,
+                                        uint8_t *rgb8, float *img, float *stats, void *ws, size_t ws_bytes, void *stream, int act);
 /* The fused fp32 first block of a 16-bit engine (orn_stage0.hip) through the launchers the engine calls, with no rider and no
  * pack work-groups; tests/test_gpu_stage0.py pins both kernels elementwise through them.  x [C][H][W], wf [O][C][3][3], bf [O]
  * (fp32, device); Cn = O / s^2 post-shuffle channels.
