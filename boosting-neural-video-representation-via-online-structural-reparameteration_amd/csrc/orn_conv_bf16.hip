@@ -439,12 +439,3 @@ void set_stamps(void *buf) { g_conv_stamps = (unsigned long long *)buf; set_stam
 #endif
 
 }  // namespace HNS
-
-#ifndef ORN_FP16
-// probe-only switches (include/orn_debug.h) reach both builds
-namespace orn_f16 { void set_debug(int flags); void set_stamps(void *buf); }
-extern "C" void orn_debug_set(int flags) { orn_bf16::set_debug(flags); orn_f16::set_debug(flags); }
-#ifdef ORN_CONV_STAMP
-extern "C" void orn_debug_set_stamps(void *buf) { orn_bf16::set_stamps(buf); orn_f16::set_stamps(buf); }
-#endif
-#endif

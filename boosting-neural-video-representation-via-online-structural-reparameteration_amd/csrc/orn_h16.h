@@ -1,7 +1,9 @@
 // What the files of the 16-bit MFMA fast path share: the element type of the build, the tile constants and small device helpers
 // of the conv kernels, the diagnostic-build macros, and the launchers one of these files calls in another.
 // Every file that includes this header is compiled twice: as is (bf16, namespace orn_bf16) and with -DORN_FP16 (IEEE half,
-// namespace orn_f16: 11-bit significand, same MFMA rate; gradients then travel scaled by 2^20, see the engine).
+// namespace orn_f16: 11-bit significand, same MFMA rate; gradients then travel scaled by 2^20, see the engine).  Such a file holds
+// only code that names h16 -- typed kernels and their launchers; what is the same in both builds lives in a once-built file and reaches
+// these launchers through OrnHalfOps (orn_internal.h).
 #pragma once
 #include "orn_internal.h"
 #include <type_traits>

@@ -130,11 +130,18 @@ int orn_head_bwd_fused_f32_blocks(int H, int W);
 int orn_launch_head_bwd_fused_f32(const float *z, const float *w, const float *out, const float *dout, int Cn, int H, int W,
                                   int sigmoid, float *dy, float *dbp, float *dw, float *db, float *hws, hipStream_t st, int act);
 
-// orn_side_head.hip: the heads of the stages below the last one (multi-resolution engine; include/orn.h, N8).  16-bit entries
-// (OrnHalfOps::side_head_fwd / _bwd): z is the block's channels-last pre-activation, dypad its padded un-shuffled gradient buffer,
-// which the backward ADDS to; fp32 entries: the NCHW activation and the gradient with respect to it.  sc: the step's scale-state
-// entry (the scale is read from it, a non-finite pre-activation / dw / db raises its flag).  ws: orn_side_head_bwd_ws_floats floats.
+// orn_side_head.hip, orn_side_head_f32.hip: the heads of the stages below the last one (multi-resolution engine; include/orn.h, N8).
+// 16-bit entries (OrnHalfOps::side_head_fwd / _bwd): z is the block's channels-last pre-activation, dypad its padded un-shuffled gradient
+// buffer, which the backward ADDS to; fp32 entries (orn_side_head_f32.hip): the NCHW activation and the gradient with respect to it.
+// sc: the step's scale-state entry (the scale is read from it, a non-finite pre-activation / dw / db raises its flag).
+// ws: orn_side_head_bwd_ws_floats floats.
+#define SH_MAXC 512              // LDS copy of W [3][C] + b
+#define SH_PPT 8                 // 16-bit backward: a work-group takes SH_PPT x 64 pixels (the larger of the two layouts' partial tables)
 size_t orn_side_head_bwd_ws_floats(int C, int H, int W);
+// column sums of either layout's partials [rows][3 C + 3] times inv -> dw, db.  sc (engine): non-finite sums raise its flag; scaled: the
+// partials carry its scale (inv is then read from it)
+int orn_launch_side_head_finish(const float *partial, int rows, int C, float inv, float *dw, float *db, hipStream_t st, OrnScaleState *sc,
+                                bool scaled);
 int orn_launch_side_head_fwd_f32(const float *a, const float *w, const float *b, int C, size_t HW, int sigmoid, float *out, hipStream_t st,
                                  OrnScaleState *sc);
 int orn_launch_side_head_bwd_f32(const float *a, const float *w, const float *out, const float *dout, int C, int H, int W, int sigmoid,
@@ -212,9 +219,14 @@ int orn_launch_msssim_frames(const float *pred, const float *targets, const int3
                              float *ws, hipStream_t st);
 
 // The 16-bit MFMA fast path (channels-last buffers, see the header of orn_conv_bf16.hip): orn_conv_fwd_bf16.hip, orn_conv_bf16.hip
-// (dgrad), orn_conv2_bf16.hip (both, large images), orn_wgrad_bf16.hip and orn_ops_bf16.hip, with orn_h16.h between them.  These
-// files are built twice (bf16 and, with -DORN_FP16, IEEE half); the engine reaches either build through the type-erased table
-// that orn_ops_bf16.hip fills.
+// (dgrad), orn_conv2_bf16.hip (both, large images), orn_wgrad_bf16.hip, orn_side_head.hip, orn_decode_out.hip and orn_ops_bf16.hip,
+// with orn_h16.h between them.  These files are built twice (bf16 and, with -DORN_FP16, IEEE half) and hold only code that names the
+// element type h16: the typed kernels and their launchers.  Everything else reaches either build through the type-erased table that
+// orn_ops_bf16.hip fills -- the engine, and the test entry points of include/orn_debug.h (orn_debug.hip); the fp32 kernels that serve
+// the same stages are built once (orn_side_head_f32.hip, orn_decode_out_f32.hip).
+// Limits of the launchers behind the table that argument checks outside these files repeat:
+#define STAGE_OUT_MAXC SH_MAXC   // stage_out: LDS copy of W [3][C] + b, as the side heads
+static inline bool orn_head_bwd_c_ok(int C) { return C == 32 || C == 64 || C == 96 || C == 128; }   // head_bwd: one instantiation per C / 32
 struct OrnPrepLayer { const float *wf, *bf; int O, C, s; void *wb, *wd; float *biasp; int Cp; };   // Cp: channel stride (0: = C)
 // deferred split-K reduction of a layer's wgrad slabs (wgrad called with dwf == nullptr leaves them in `slabs`)
 struct OrnWgradReduce { const float *slabs; int H, W, C, O, s; float gscale; float *dwf, *dbf; OrnScaleState *sc; int smax; };   // sc (optional): 1/scale from the device state, non-finite results raise its flag
@@ -228,7 +240,7 @@ struct OrnWgradJob { const void *xpad, *dypad; int H, W, C, O, s; float *slabs; 
 #define ORN_DECODE_MAX_BLOCKS 8192
 #define ORN_DECODE_WS_FLOATS (2 * ORN_DECODE_MAX_BLOCKS + 64)
 struct OrnDecodeOut { const float *targets; const int32_t *row; uint8_t *rgb8; float *img, *stats; float *ws; };
-// fp32 engine: the same stage from the planar image the fp32 head wrote
+// fp32 engine: the same stage from the planar image the fp32 head wrote (orn_decode_out_f32.hip)
 int orn_launch_decode_out_f32(const float *src, size_t HW, const OrnDecodeOut &o, hipStream_t st);
 struct OrnHalfOps {
     int (*conv_fwd)(const void *xpad, const void *wb, const float *bias_p, int H, int W, int Cin, int O, int s, void *z, void *apad,
@@ -236,6 +248,7 @@ struct OrnHalfOps {
     int (*conv_dgrad)(const void *dypad, const void *wd, int H, int W, int O, int C, const void *zprev, void *dyprev, int sp,
                       float *dx_f32, hipStream_t st, int c_real, int act);   // c_real: output channels that are not zero padding
     size_t (*wgrad_ws_floats)(int H, int W, int O);
+    int (*wgrad_split)(int H, int W, int O, int smax);   // slab count of a layer under the caller's cap (below 8: none)
     int (*wgrad_batch)(int n, const OrnWgradJob *J, hipStream_t st, const OrnHeadFinish *hf, const OrnStemL2Job *l2, int side, int act);   // side: launched on the engine's side stream (default wave priority)   // several layers' slabs in one launch (+ optional head finish, + the stem backward's first kernel)
     int (*wgrad_reduce_all)(int n, const OrnWgradReduce *L, hipStream_t st, const OrnStemW0Job *w0, int act);   // all layers' reductions in one launch (+ the stem backward's last kernel)
     int (*prep_all)(int n, const OrnPrepLayer *L, hipStream_t st);

@@ -1,8 +1,8 @@
 // A4 fast path, everything around the conv kernels: the 16-bit operand copies of the merged kernels (weight prep), the layout
 // converters between fp32 NCHW and padded channels-last 16-bit, the bias gradient, the A5 head (model.py:621-622) forward /
-// backward on the channels-last pre-activation of the last block, the type-erased operation table the engine calls through
-// (OrnHalfOps, one per compiled element type) and the per-op C ABI of include/orn.h and orn_debug.h.  Buffer layouts:
-// orn_conv_bf16.hip.
+// backward on the channels-last pre-activation of the last block, the type-erased operation table that everything outside the
+// twice-built files calls through (OrnHalfOps, one per compiled element type: the engine and the test entry points of orn_debug.hip)
+// and the typed per-op C ABI of include/orn.h.  Buffer layouts: orn_conv_bf16.hip.
 // Compiled twice (orn_h16.h): bf16 and, with -DORN_FP16, IEEE half.
 #include "orn_h16.h"
 
@@ -347,7 +347,7 @@ int orn_launch_head_bwd_bf16(const h16 *z, const float *w, const float *out, con
                              const OrnLossFinalJob *fin, int act)
 {
     ORN_REQUIRE(orn_act_known(act), "head_bwd_bf16: unknown activation %d", act);
-    ORN_REQUIRE(C == 96 || C == 32 || C == 64 || C == 128, "head_bwd_bf16: unsupported C=%d", C);
+    ORN_REQUIRE(orn_head_bwd_c_ok(C), "head_bwd_bf16: unsupported C=%d", C);
     ORN_REQUIRE(H % sp == 0 && W % sp == 0, "head_bwd_bf16: H,W not divisible by stride");
     int blocks = orn_cdiv((long)H * W, 64);
     if (blocks > HB_BLOCKS) blocks = HB_BLOCKS;
@@ -394,13 +394,14 @@ static int a_side_head_bwd(const void *z, const float *w, const float *out, cons
 static int a_stage_out(const void *z, const float *w, const float *b, int C, size_t HW, int sigmoid, const OrnDecodeOut &o, hipStream_t st, int act)
 { return orn_launch_stage_out_h16((const h16 *)z, w, b, C, HW, sigmoid, o, st, act); }
 
-const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all, orn_launch_prep_weights_bf16_all, a_to_nhwc,
-                        a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats, orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out,
-                        a_side_head_fwd, a_side_head_bwd, a_stage_out};
+const OrnHalfOps ops = {a_conv_fwd, a_conv_dgrad, orn_wgrad_bf16_ws_floats, orn_wgrad_bf16_split, orn_launch_wgrad_bf16_batch, orn_launch_wgrad_reduce_all,
+                        orn_launch_prep_weights_bf16_all, a_to_nhwc, a_to_nchw_f32, orn_dgrad_f32_slabs, a_head_fwd, orn_head_bwd_bf16_ws_floats,
+                        orn_head_bwd_bf16_blocks, a_head_bwd, a_decode_out, a_side_head_fwd, a_side_head_bwd, a_stage_out};
 
 // ================================================================================================
-// test / per-op hooks: the 16-bit block on PyTorch-layout fp32 tensors (conversions included).  Built in both element
-// types: the bf16 build exports orn_*_bf16, the IEEE-half build the orn_*_f16 twins (same arguments, half buffers).
+// per-op hooks of include/orn.h: the 16-bit block on PyTorch-layout fp32 tensors (conversions included).  Built in both element
+// types: the bf16 build exports orn_*_bf16, the IEEE-half build the orn_*_f16 twins (same arguments, half buffers).  HOOK names
+// them; the two _ws_bytes functions have no element type in them and exist once, in the bf16 build.
 // ================================================================================================
 #ifdef ORN_FP16
 #define HOOK(bf16_, f16_) f16_
@@ -554,198 +555,6 @@ extern "C" int HOOK(orn_dgrad_nhwc_bf16, orn_dgrad_nhwc_f16)(const void *dypad, 
 {
     return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp,
                                       nullptr, (hipStream_t)stream, C, ORN_ACT_SWISH);      // the raw entry is the swish form (include/orn.h)
-}
-
-// Test entry points (include/orn_debug.h): the two conv launchers with the engine's full argument lists, so that a test reaches
-// every kernel form they select (the narrow c_real forms, the split dgrad + finish, the fp32 hand-off) with the engine's buffers.
-extern "C" int HOOK(orn_debug_conv_fwd_bf16_act, orn_debug_conv_fwd_f16_act)(const void *xpad, const void *wb, const float *bias_p, int H, int W,
-                                                                           int Cin, int O, int s, void *z, void *apad, int c_real, void *stream,
-                                                                           int act)
-{
-    ORN_REQUIRE(orn_act_known(act), "debug_conv_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
-    return orn_launch_conv_bf16_fwd((const h16 *)xpad, (const h16 *)wb, bias_p, H, W, Cin, O, s, (h16 *)z, (h16 *)apad,
-                                    (hipStream_t)stream, c_real, act);
-}
-extern "C" int HOOK(orn_debug_conv_fwd_bf16, orn_debug_conv_fwd_f16)(const void *xpad, const void *wb, const float *bias_p, int H, int W,
-                                                                   int Cin, int O, int s, void *z, void *apad, int c_real, void *stream)
-{
-    return HOOK(orn_debug_conv_fwd_bf16_act, orn_debug_conv_fwd_f16_act)(xpad, wb, bias_p, H, W, Cin, O, s, z, apad, c_real, stream, ORN_ACT_SWISH);
-}
-extern "C" int HOOK(orn_debug_conv_dgrad_bf16_act, orn_debug_conv_dgrad_f16_act)(const void *dypad, const void *wd, int H, int W, int O, int C,
-                                                                               const void *zprev, void *dyprev, int sp, float *dx_f32, int c_real,
-                                                                               void *stream, int act)
-{
-    ORN_REQUIRE(orn_act_known(act), "debug_conv_dgrad: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
-    return orn_launch_conv_bf16_dgrad((const h16 *)dypad, (const h16 *)wd, H, W, O, C, (const h16 *)zprev, (h16 *)dyprev, sp, dx_f32,
-                                      (hipStream_t)stream, c_real, act);
-}
-extern "C" int HOOK(orn_debug_conv_dgrad_bf16, orn_debug_conv_dgrad_f16)(const void *dypad, const void *wd, int H, int W, int O, int C,
-                                                                       const void *zprev, void *dyprev, int sp, float *dx_f32, int c_real,
-                                                                       void *stream)
-{
-    return HOOK(orn_debug_conv_dgrad_bf16_act, orn_debug_conv_dgrad_f16_act)(dypad, wd, H, W, O, C, zprev, dyprev, sp, dx_f32, c_real, stream,
-                                                                             ORN_ACT_SWISH);
-}
-
-// The last stage's head (include/orn_debug.h): the launchers above and the two forms of the dW / db finish, as the per-op path and the
-// engine call them.  The sizes are the launchers' own functions; the un-typed ones live in the bf16 build.
-#ifdef ORN_FP16
-extern "C" size_t orn_debug_head16_bwd_ws_bytes(int C);
-extern "C" size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int loss_type);
-#else
-extern "C" int orn_debug_head16_bwd_blocks(int H, int W) { return (H >= 1 && W >= 1) ? orn_head_bwd_bf16_blocks(H, W) : 0; }
-extern "C" size_t orn_debug_head16_bwd_ws_bytes(int C)
-{
-    return (C == 32 || C == 64 || C == 96 || C == 128) ? orn_head_bwd_bf16_ws_floats(C) * sizeof(float) : 0;
-}
-extern "C" size_t orn_debug_head16_bwd_rider_ws_bytes(int C, int H, int W, int loss_type)
-{
-    const size_t head = orn_debug_head16_bwd_ws_bytes(C), loss = orn_loss_ws_bytes_for(loss_type, 1, 3, H, W);
-    return head && loss ? orn_align(head) + loss : 0;
-}
-#endif
-
-extern "C" int HOOK(orn_debug_head_fwd_bf16_act, orn_debug_head_fwd_f16_act)(const void *z, const float *w, const float *b, int C, int H, int W,
-                                                                             int sigmoid, float *out, void *stream, int act)
-{
-    ORN_REQUIRE(orn_act_known(act), "head_fwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
-    ORN_REQUIRE(z && w && b && out, "head_fwd: null pointer");
-    ORN_REQUIRE(C >= 32 && H >= 1 && W >= 1, "head_fwd: bad sizes C=%d %dx%d", C, H, W);
-    return orn_launch_head_fwd_bf16((const h16 *)z, w, b, C, (size_t)H * W, sigmoid, out, (hipStream_t)stream, act);
-}
-extern "C" int HOOK(orn_debug_head_fwd_bf16, orn_debug_head_fwd_f16)(const void *z, const float *w, const float *b, int C, int H, int W,
-                                                                     int sigmoid, float *out, void *stream)
-{
-    return HOOK(orn_debug_head_fwd_bf16_act, orn_debug_head_fwd_f16_act)(z, w, b, C, H, W, sigmoid, out, stream, ORN_ACT_SWISH);
-}
-
-extern "C" int HOOK(orn_debug_head_bwd_bf16_act, orn_debug_head_bwd_f16_act)(const void *z, const float *w, const float *out, float *dout, int C,
-                                                                             int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
-                                                                             float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
-                                                                             int loss_type, float *stats, void *stream, int act)
-{
-    ORN_REQUIRE(orn_act_known(act), "head_bwd: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
-    ORN_REQUIRE(z && w && out && dout && dypad && dw && db && ws && (!target || stats), "head_bwd: null pointer");
-    const size_t head_bytes = orn_debug_head16_bwd_ws_bytes(C);
-    ORN_REQUIRE(head_bytes, "head_bwd: unsupported C=%d", C);
-    ORN_REQUIRE(H >= 1 && W >= 1 && sp >= 1 && H % sp == 0 && W % sp == 0, "head_bwd: %dx%d not divisible by the stride %d", H, W, sp);
-    ORN_REQUIRE(gs > 0.f, "head_bwd: gradient scale %g", (double)gs);
-    const size_t need = target ? orn_debug_head16_bwd_rider_ws_bytes(C, H, W, loss_type) : head_bytes;
-    ORN_REQUIRE(need, "head_bwd: loss_type %d does not take a %dx%d image", loss_type, H, W);
-    ORN_REQUIRE(!target || (uintptr_t)ws % 16 == 0, "head_bwd: the rider needs a 16-byte aligned workspace");
-    if (ws_bytes < need) { orn_set_error("head_bwd: workspace %zu < %zu", ws_bytes, need); return ORN_E_WS; }
-    hipStream_t st = (hipStream_t)stream;
-    OrnScaleState *sc = nullptr;
-    OrnScaleState s0 = {};
-    if (flag) {                                         // the engine's form: the scale lives in a state entry on the device
-        s0.gs = s0.gs_max = gs;
-        s0.inv_gs = 1.0f / gs;
-        ORN_HIP(hipMalloc(&sc, sizeof(s0)));
-        const hipError_t e = hipMemcpy(sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { orn_set_error("head_bwd: %s", hipGetErrorString(e)); (void)hipFree(sc); return (int)e; }
-    }
-    int rc = 0;
-    OrnLossFinalJob fj = {};
-    if (target)                                         // the loss writes dout and leaves its finalize stage to the head backward
-        rc = orn_launch_loss(out, target, nullptr, 0, 1, 3, H, W, loss_type, gs, stats, dout, (float *)((char *)ws + orn_align(head_bytes)), st,
-                             nullptr, nullptr, sc, nullptr, &fj);
-    if (rc == 0)
-        rc = orn_launch_head_bwd_bf16((const h16 *)z, w, out, dout, C, H, W, sigmoid, sp, gs, (h16 *)dypad, flag ? nullptr : dw,
-                                      flag ? nullptr : db, (float *)ws, st, sc, target ? &fj : nullptr, act);
-    if (rc == 0 && flag) {
-        const OrnHeadFinish hf = {(const float *)ws, orn_head_bwd_bf16_blocks(H, W), C, 1.0f / gs, dw, db, sc};
-        rc = orn_launch_wgrad_bf16_batch(0, nullptr, st, &hf, nullptr, 0, act);     // (no stem job on it: nothing evaluates the activation)
-    }
-    if (flag) {
-        hipError_t e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipMemcpy(&s0, sc, sizeof(s0), hipMemcpyDeviceToHost);
-        if (rc == 0 && e != hipSuccess) { orn_set_error("head_bwd: %s", hipGetErrorString(e)); rc = (int)e; }
-        if (rc == 0) *flag = s0.flag;
-        (void)hipFree(sc);
-    }
-    return rc;
-}
-extern "C" int HOOK(orn_debug_head_bwd_bf16, orn_debug_head_bwd_f16)(const void *z, const float *w, const float *out, float *dout, int C,
-                                                                     int H, int W, int sigmoid, int sp, float gs, void *dypad, float *dw,
-                                                                     float *db, void *ws, size_t ws_bytes, int *flag, const float *target,
-                                                                     int loss_type, float *stats, void *stream)
-{
-    return HOOK(orn_debug_head_bwd_bf16_act, orn_debug_head_bwd_f16_act)(z, w, out, dout, C, H, W, sigmoid, sp, gs, dypad, dw, db, ws, ws_bytes, flag,
-                                                                         target, loss_type, stats, stream, ORN_ACT_SWISH);
-}
-
-// The two weight-gradient launches of a step (include/orn_debug.h) through the table the engine calls them through, in the order and
-// with the argument structs of fast_weight_grads / side_branch_backward (orn_engine_step.hip).  Everything is checked before the first
-// launch or allocation; the slab rule's two host functions live in the bf16 build.
-#ifndef ORN_FP16
-extern "C" int orn_debug_wgrad16_split(int H, int W, int O, int smax) { return orn_wgrad_bf16_split(H, W, O, smax); }
-extern "C" size_t orn_debug_wgrad16_ws_floats(int H, int W, int O) { return orn_wgrad_bf16_ws_floats(H, W, O); }
-#endif
-extern "C" int HOOK(orn_debug_wgrad16_step_bf16, orn_debug_wgrad16_step_f16)(int n, const orn_debug_wgrad16_job *jobs,
-                                                                             const orn_debug_wgrad16_head *head,
-                                                                             const orn_debug_wgrad16_stem *stem, float gs, int use_state,
-                                                                             int side, int act, int *flag, void *stream)
-{
-    ORN_REQUIRE(orn_act_known(act), "debug_wgrad16_step: unknown activation %d (ORN_ACT_SWISH, ORN_ACT_GELU)", act);
-    ORN_REQUIRE(n >= 0 && n <= ORN_MAX_LAYERS, "debug_wgrad16_step: %d jobs (0..%d)", n, ORN_MAX_LAYERS);
-    ORN_REQUIRE((n == 0 || jobs) && (!use_state || flag), "debug_wgrad16_step: null pointer");
-    ORN_REQUIRE(gs > 0.f, "debug_wgrad16_step: gradient scale %g", (double)gs);
-    for (int i = 0; i < n; ++i) {
-        const orn_debug_wgrad16_job &j = jobs[i];
-        ORN_REQUIRE(j.xpad && j.dypad && j.slabs && j.dwf && j.dbf, "debug_wgrad16_step: null pointer in job %d", i);
-        ORN_REQUIRE(j.H >= 1 && j.W >= 1 && j.s >= 1, "debug_wgrad16_step: job %d: bad sizes %dx%d s=%d", i, j.H, j.W, j.s);
-        ORN_REQUIRE(j.C >= 1 && j.C <= 96 && j.O >= 32 && j.O % 32 == 0 && j.O % (j.s * j.s) == 0, "wgrad_bf16: unsupported C=%d O=%d", j.C, j.O);
-    }
-    if (head) {
-        ORN_REQUIRE(head->partial && head->dw && head->db, "debug_wgrad16_step: null pointer in the head finish");
-        ORN_REQUIRE(head->blocks >= 1 && head->C >= 1, "debug_wgrad16_step: head finish of %d blocks, C=%d", head->blocks, head->C);
-    }
-    if (stem) {
-        const orn_debug_wgrad16_stem &t = *stem;
-        ORN_REQUIRE(t.embed && t.w1 && t.pre1 && t.h1 && t.pre2 && t.dh2_slabs && t.dw0 && t.db0 && t.dw1 && t.db1 && t.ws,
-                    "debug_wgrad16_step: null pointer in the stem job");
-        ORN_REQUIRE(t.nslab >= 1 && t.E > 0 && t.Hd > 0 && t.Nout > 0, "debug_wgrad16_step: bad stem sizes");
-        if (t.ws_bytes < orn_stem_bwd_ws_bytes(1, t.Hd, t.Nout) || (uintptr_t)t.ws % 4 != 0) {
-            orn_set_error("debug_wgrad16_step: stem workspace of %zu bytes, needs orn_stem_bwd_ws_bytes = %zu, 4-byte aligned", t.ws_bytes,
-                          orn_stem_bwd_ws_bytes(1, t.Hd, t.Nout));
-            return ORN_E_WS;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    OrnScaleState *sc = nullptr;
-    OrnScaleState s0 = {};
-    if (use_state) {                                    // the engine's form: the scale lives in a state entry on the device
-        s0.gs = s0.gs_max = gs;
-        s0.inv_gs = 1.0f / gs;
-        ORN_HIP(hipMalloc(&sc, sizeof(s0)));
-        const hipError_t e = hipMemcpy(sc, &s0, sizeof(s0), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { orn_set_error("debug_wgrad16_step: %s", hipGetErrorString(e)); (void)hipFree(sc); return (int)e; }
-    }
-    int rc = 0;
-    OrnStemW0Job w0job;
-    OrnStemL2Job l2job;
-    if (stem)                                           // deferred: both kernels come back as jobs, nothing is launched here
-        rc = orn_launch_stem_bwd(stem->embed, nullptr, 0, stem->w1, stem->pre1, stem->h1, stem->pre2, stem->dh2_slabs, 1, stem->E, stem->Hd,
-                                 stem->Nout, stem->dw0, stem->db0, stem->dw1, stem->db1, stem->ws, st, stem->nslab, &w0job, &l2job, act, sc);
-    OrnWgradJob wj[ORN_MAX_LAYERS];
-    OrnWgradReduce wr[ORN_MAX_LAYERS];
-    for (int i = 0; i < n; ++i) {
-        const orn_debug_wgrad16_job &j = jobs[i];
-        wj[i] = OrnWgradJob{j.xpad, j.dypad, j.H, j.W, j.C, j.O, j.s, j.slabs, j.smax};
-        wr[i] = OrnWgradReduce{j.slabs, j.H, j.W, j.C, j.O, j.s, 1.0f / gs, j.dwf, j.dbf, sc, j.smax};
-    }
-    OrnHeadFinish hf = {};
-    if (head) hf = OrnHeadFinish{head->partial, head->blocks, head->C, 1.0f / gs, head->dw, head->db, sc};
-    if (rc == 0) rc = ops.wgrad_batch(n, wj, st, head ? &hf : nullptr, stem ? &l2job : nullptr, side ? 1 : 0, act);
-    if (rc == 0) rc = ops.wgrad_reduce_all(n, wr, st, stem ? &w0job : nullptr, act);
-    if (use_state) {
-        hipError_t e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipMemcpy(&s0, sc, sizeof(s0), hipMemcpyDeviceToHost);
-        if (rc == 0 && e != hipSuccess) { orn_set_error("debug_wgrad16_step: %s", hipGetErrorString(e)); rc = (int)e; }
-        if (rc == 0) *flag = s0.flag;
-        (void)hipFree(sc);
-    }
-    return rc;
 }
 
 }  // namespace HNS

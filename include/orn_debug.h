@@ -5,7 +5,11 @@
  * (tests/test_gpu_stage0.py), the MS-SSIM level kernels' (tests/test_gpu_msssim_levels.py), the loss launcher's
  * (tests/test_gpu_fusion6.py), the side heads'
  * (tests/test_gpu_side_head.py), the last stage's 16-bit head's (tests/test_gpu_head16.py), the fp32 conv path's
- * (tests/test_gpu_conv32_forms.py) and the batched weight-gradient and slab-reduction launches' (tests/test_gpu_wgrad16_batch.py). */
+ * (tests/test_gpu_conv32_forms.py) and the batched weight-gradient and slab-reduction launches' (tests/test_gpu_wgrad16_batch.py).
+ * Where they are defined: the entries of the 16-bit fast path (conv, head, wgrad16, side_head, stage_out, decode_out, orn_debug_set) in
+ * csrc/orn_debug.hip, built once, each body written once against the type-erased table the engine calls through and exported under its
+ * bf16 / f16 names; every other entry in the once-built file of the kernels it reaches (orn_stage0.hip, orn_elementwise.hip,
+ * orn_conv_f32.hip, orn_loss.hip, orn_loss_msssim.hip, orn_merge_h16.hip). */
 #ifndef ORN_DEBUG_H_
 #define ORN_DEBUG_H_
 #include "orn.h"
@@ -143,7 +147,7 @@ ORN_API int orn_debug_loss_launch(const float *pred, const float *frames, const 
                                   int H, int W, int loss_type, float loss_scale, const float *tstats, float *stats, float *dpred,
                                   void *ws, size_t ws_bytes, void *stream);
 ORN_API int orn_debug_loss_layout(int B, int Ch, int H, int W, int64_t *out);
-/* The side heads of a multi-resolution generator (model.py:597-625 without sin_res; orn_side_head.hip): the head of a stage below
+/* The side heads of a multi-resolution generator (model.py:597-625 without sin_res; orn_side_head.hip, fp32: orn_side_head_f32.hip): the head of a stage below
  * the last one, whose backward ADDS to a gradient buffer the block above has already written.  tests/test_gpu_side_head.py pins
  * them elementwise to fp64.  w [3][C], b [3], out / dout [3][H][W] planar fp32; 1 <= C <= 512, H*W <= 2^30; sigmoid: 0 = (tanh + 1) / 2.
  *   fwd (16 bit): z [H][W][C] channels-last pre-activation (bf16 / IEEE half); out = act(W SiLU(z) + b), every element written.

@@ -1,5 +1,5 @@
-"""The side-head kernels of the multi-resolution generator (csrc/orn_side_head.hip) elementwise against fp64, through the entry
-points of include/orn_debug.h: the forward on a block's stored output, and the backward that ADDS its term to a gradient buffer
+"""The side-head kernels of the multi-resolution generator (csrc/orn_side_head.hip; the fp32 layout's and the dW / db finish:
+csrc/orn_side_head_f32.hip) elementwise against fp64, through the entry points of include/orn_debug.h (csrc/orn_debug.hip): the forward on a block's stored output, and the backward that ADDS its term to a gradient buffer
 another kernel has already written.
 
 The fp64 reference starts from the SAME stored inputs (the 16-bit z and gradient buffer, the fp32 w, b, out, dout), so what is
